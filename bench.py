@@ -32,7 +32,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 from bench_blocks.common import (GOLDEN, HBM_PEAK_GBS, MASK, N_PUBLIC, R_FR, HAND_WRITTEN_HOT, Instance, block_roofline, dominant_by_time, oracle_proof, traffic_ratio, valu_fraction,  # noqa: E402,F401
-                                 seed_at)
+                                 seed_at, dump_outputs)
 from bench_blocks.export_path import export_path_block, export_path_groth16_block  # noqa: E402
 from bench_blocks.launch import needs_self_launch, self_launch  # noqa: E402
 from bench_blocks.inner_boundary import inner_boundary_block, two_slice_recombination  # noqa: E402
@@ -70,7 +70,11 @@ def main():
     ap.add_argument("--verify-2p24-oracle", action="store_true", help="(default since round 6; kept for old command lines) check the 2^24 proof bytes against the CPU oracle")
     ap.add_argument("--no-verify-2p24-oracle", action="store_true", help="skip the CPU oracle's proof of the 2^24 instance (~40 s on the 16 CPUs a GPU box gives; --no-cpu-baseline skips it too)")
     ap.add_argument("--dry-launch", action="store_true", help="with --gpus N > 1 and no launcher around: print the torch.distributed.run command this script would start and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the proof of the last one (what a caller of zk.prove receives) "
+                    "as DIR/proof.npy (float64, one value per byte); the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python3 bench.py --gpus N` typed as is: become the launcher (a child torch.distributed.run with N ranks) BEFORE anything touches the GPU -- no torch.cuda
     # call, no libzkmi load above this line.  Under an existing launcher (RANK / WORLD_SIZE set) this is skipped and we are one of the ranks.
@@ -156,6 +160,8 @@ def main():
         proof = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, proof)
     # the roofline pass: the same number of the same proofs once more with a hipEvent pair around every launch, on the stream it is launched on
     _lib.profile(True)
     _lib.profile_reset()

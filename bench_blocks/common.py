@@ -84,6 +84,13 @@ class Instance:
                 b.free()
 
 
+def dump_outputs(d, proof):
+    """bench.py --dump-outputs DIR: what the timed path returned in its last step, as its caller receives it -- the 128 proof bytes (Ar | Bs | Krs
+    compressed) -- written as DIR/proof.npy, one float64 per byte (exact), so that two builds can be compared output for output."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "proof.npy"), np.frombuffer(proof, dtype=np.uint8).astype(np.float64))
+
+
 def oracle_proof(inst, log_n):
     """The CPU oracle proves the SAME instance on this box's host cores (test infrastructure: the checker and the timed CPU baseline)."""
     from oracle import oracle as orc  # the CPU oracle is used ONLY in these legs, after the timed GPU region

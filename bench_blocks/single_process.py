@@ -9,7 +9,7 @@ import time
 import numpy as np
 
 from .common import *  # noqa: F401,F403
-from .common import ROOT, N_PUBLIC, HBM_PEAK_GBS, R_FR, seed_at
+from .common import ROOT, N_PUBLIC, HBM_PEAK_GBS, R_FR, seed_at, dump_outputs
 
 
 def single_process_main(args, zk, lib):
@@ -40,6 +40,8 @@ def single_process_main(args, zk, lib):
         proof = step()
     lib.check(L.zk_dev_sync())
     ms = (time.perf_counter() - t0) / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, proof)
     metric = "Groth16 prove ms + BN254 G1 MSM scalar-muls/sec at 2^20 / 2^24 constraints"
     try:
         metric = json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
