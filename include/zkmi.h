@@ -322,6 +322,31 @@ int zk_bn254_plonk_verify(const uint8_t proof[548] /* ZK_PLONK_PROOF_BYTES */, c
                           const zk_fr *public_inputs, size_t n_public, int *accepted);
 int zk_bn254_pairing_check(const zk_g1_affine *p, const zk_g2_affine *q, size_t n, int *is_one);
 
+/* ---- Pairings and batch Groth16 verification on the DEVICE.
+ * zk_gt is bn254.GT's memory image: E12 {C0 E6{B0, B1, B2}, C1 E6{...}}, each E2 {A0, A1}, Montgomery (384 bytes) -- gnark's tower Fp6 = Fp2[v]/(v^3 - xi),
+ * Fp12 = Fp6[w]/(w^2 - v), xi = 9 + u.
+ *   zk_bn254_pair      : prod_i e(p_i, q_i), the reduced optimal ate pairing, exactly f^((q^12 - 1) / r) with f = prod_i of the Miller values of the host
+ *                        pairing (csrc/pairing.hpp); computed on the device (one Miller loop per lane, a product tree, one final exponentiation).
+ *   zk_bn254_pair_host : the same value on the host (pairing.hpp).  n == 0 gives one; a point at infinity on either side contributes one.  Inputs are
+ *                        affine Montgomery images and are not validated (as zk_bn254_pairing_check).  The value is NOT claimed to equal gnark-crypto's
+ *                        bn254.Pair: its final exponentiation may compute a fixed power of this one; products tested against one agree either way.
+ *   zk_bn254_groth16_verify_batch : groth16.Verify for n_proofs proofs (n_proofs x 128 bytes, Proof.WriteTo) against ONE verifying key (bytes or hex);
+ *                        public_inputs: n_proofs x n_public Montgomery fr.Elements, row-major, without the constant wire.  accepted[i] equals what
+ *                        zk_bn254_groth16_verify says of proof i, except that a malformed proof encoding (flags, x >= q, no square root, a G2 point outside
+ *                        the r-torsion) -- ZK_ERR_ARG there -- is a 0 here and does not affect the other proofs.  *n_accepted = the number of ones.
+ *                        A malformed key is ZK_ERR_ARG / ZK_ERR_LEN, n_public + 1 != len(K) is ZK_ERR_LEN, as in the host verifier.
+ *                        The valid proofs are first checked together: one random linear combination with r_i = the low 128 bits of
+ *                        SHA-256("zkmi-groth16-batch" || SHA-256(vk bytes) || SHA-256(proofs || public inputs) || u64 i little-endian), forced non-zero --
+ *                        derived, not random, so results are reproducible; a batch with an invalid proof passes with probability about 2^-128 in the
+ *                        random-oracle model.  If that check fails, every valid proof is checked on its own on the device.  Proofs go through in chunks of
+ *                        at most 2^16; the device workspace is about 5 KB + 96 (n_public + 1) bytes per proof of a chunk.
+ * Both device entries return ZK_ERR_NO_DEVICE without a GPU, after argument validation; there is no CPU fallback. */
+typedef struct { zk_fp c[12]; } zk_gt;
+int zk_bn254_pair(const zk_g1_affine *p, const zk_g2_affine *q, size_t n, zk_gt *out);
+int zk_bn254_pair_host(const zk_g1_affine *p, const zk_g2_affine *q, size_t n, zk_gt *out);
+int zk_bn254_groth16_verify_batch(const uint8_t *proofs, size_t n_proofs, const void *vk, size_t vk_len, int vk_is_hex, const zk_fr *public_inputs,
+                                  size_t n_public, uint8_t *accepted, size_t *n_accepted);
+
 /* The two halves of zk_bn254_groth16_prove, exposed so that one proof can be range-sharded over several GPUs
  * (one process per GPU): every rank runs the five MSMs on ITS slice of the bases / wire values / h, the un-normalised
  * XYZZ sums (4 x G1 = 64 limbs, then G2 = 32 limbs; order A, B1, K, Z, B2) are all-gathered, and any rank finishes.

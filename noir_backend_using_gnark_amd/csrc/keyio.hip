@@ -128,7 +128,8 @@ __device__ __forceinline__ bool fp_lex_largest_dev(const Fp& canonical) {  // va
     return false;
 }
 // G1Affine.SetBytes on a compressed encoding: y = sqrt(x^3 + 3) = (x^3 + 3)^((q + 1) / 4)  (q = 3 mod 4), sign by the flag
-__global__ __launch_bounds__(256) void k_g1_decompress(const uint32_t* __restrict__ raw, size_t n, Affine<Fp>* __restrict__ out, int* __restrict__ status) {
+__global__ __launch_bounds__(256) void k_g1_decompress(const uint32_t* __restrict__ raw, size_t n, Affine<Fp>* __restrict__ out, int* __restrict__ status,
+                                                     uint8_t* __restrict__ bad) {  // bad (may be null): 1 per invalid encoding
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Fp x = load_be32<Fp>(raw + 8 * i);
@@ -136,12 +137,16 @@ __global__ __launch_bounds__(256) void k_g1_decompress(const uint32_t* __restric
     x.l[7] &= 0x3fffffffu;
     Affine<Fp> p = Affine<Fp>::inf();
     if (flag == 1) {  // infinity: the rest must be zero
-        if (!x.is_zero()) atomicOr(status, 4);
+        if (!x.is_zero()) {
+            atomicOr(status, 4);
+            if (bad) bad[i] = 1;
+        }
         out[i] = p;
         return;
     }
     if (flag == 0 || geq_mod<FpParams>(x.l)) {  // an uncompressed encoding inside a compressed slice / x >= q
         atomicOr(status, 4);
+        if (bad) bad[i] = 1;
         out[i] = p;
         return;
     }
@@ -151,6 +156,7 @@ __global__ __launch_bounds__(256) void k_g1_decompress(const uint32_t* __restric
     Fp y = fp_pow_qm3_4(rhs, true);  // rhs^((q + 1) / 4)
     if (y.sqr() != rhs) {  // not on the curve
         atomicOr(status, 4);
+        if (bad) bad[i] = 1;
         out[i] = p;
         return;
     }
@@ -276,7 +282,7 @@ __device__ bool g2_subgroup_tail29(const Affine<Fp2>* __restrict__ pp, const XYZ
     return f2_eq29(f2_mulFK29<40>(lhs.x, d.zz), f2_mulFK29<40>(d.x, lhs.zz)) && f2_eq29(f2_mulFK29<40>(lhs.y, d.zzz), f2_mulFK29<40>(d.y, lhs.zzz));
 }
 __global__ __launch_bounds__(128) void k_g2_decompress(const uint32_t* __restrict__ raw, size_t n, Fp2 bt, PsiConsts psi, Affine<Fp2>* __restrict__ out,
-                                                       int* __restrict__ status) {
+                                                       int* __restrict__ status, uint8_t* __restrict__ bad) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Fp x1 = load_be32<Fp>(raw + 16 * i), x0 = load_be32<Fp>(raw + 16 * i + 8);
@@ -284,12 +290,16 @@ __global__ __launch_bounds__(128) void k_g2_decompress(const uint32_t* __restric
     x1.l[7] &= 0x3fffffffu;
     Affine<Fp2> p = Affine<Fp2>::inf();
     if (flag == 1) {
-        if (!x1.is_zero() || !x0.is_zero()) atomicOr(status, 8);
+        if (!x1.is_zero() || !x0.is_zero()) {
+            atomicOr(status, 8);
+            if (bad) bad[i] = 1;
+        }
         out[i] = p;
         return;
     }
     if (flag == 0 || geq_mod<FpParams>(x1.l) || geq_mod<FpParams>(x0.l)) {
         atomicOr(status, 8);
+        if (bad) bad[i] = 1;
         out[i] = p;
         return;
     }
@@ -297,6 +307,7 @@ __global__ __launch_bounds__(128) void k_g2_decompress(const uint32_t* __restric
     Fp2 rhs = x.sqr() * x + bt, y;
     if (!f2_sqrt_dev(rhs, psi.half, &y)) {
         atomicOr(status, 8);
+        if (bad) bad[i] = 1;
         out[i] = p;
         return;
     }
@@ -308,7 +319,8 @@ __global__ __launch_bounds__(128) void k_g2_decompress(const uint32_t* __restric
 // second half of G2Affine.SetBytes, a kernel of its own (the square root and the subgroup test in one kernel need 512 registers: one wave per SIMD; apart, each
 // runs with two or more): a point outside the r-torsion subgroup becomes the point at infinity and sets status bit 16
 template <bool FULL>
-__global__ __launch_bounds__(128) void k_g2_subgroup(Affine<Fp2>* __restrict__ pts, size_t n, const XYZZ<Fp2>* __restrict__ x0p, PsiConsts psi, int* __restrict__ status) {
+__global__ __launch_bounds__(128) void k_g2_subgroup(Affine<Fp2>* __restrict__ pts, size_t n, const XYZZ<Fp2>* __restrict__ x0p, PsiConsts psi, int* __restrict__ status,
+                                                     uint8_t* __restrict__ bad) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (pts[i].is_inf()) return;
@@ -322,6 +334,7 @@ __global__ __launch_bounds__(128) void k_g2_subgroup(Affine<Fp2>* __restrict__ p
     }
     if (!member) {
         atomicOr(status, 16);
+        if (bad) bad[i] = 1;
         pts[i] = Affine<Fp2>::inf();
     }
 }
@@ -382,8 +395,8 @@ int fr_to_be_dev(Slot* s, hipStream_t st, const void* d_in, size_t n, void* d_ra
     if (n) ZK_LAUNCH(s, st, "fr_to_be", k_fr_to_be, dim3(grid1(n)), dim3(256), 0, (const Fr*)d_in, n, (uint32_t*)d_raw);
     return ZK_OK;
 }
-int g1_decompress_dev(Slot* s, hipStream_t st, const void* d_raw, size_t n, void* d_out, int* d_status) {
-    if (n) ZK_LAUNCH(s, st, "g1_decompress", k_g1_decompress, dim3(grid1(n)), dim3(256), 0, (const uint32_t*)d_raw, n, (Affine<Fp>*)d_out, d_status);
+int g1_decompress_dev(Slot* s, hipStream_t st, const void* d_raw, size_t n, void* d_out, int* d_status, uint8_t* d_bad) {
+    if (n) ZK_LAUNCH(s, st, "g1_decompress", k_g1_decompress, dim3(grid1(n)), dim3(256), 0, (const uint32_t*)d_raw, n, (Affine<Fp>*)d_out, d_status, d_bad);
     return ZK_OK;
 }
 int g1_compress_dev(Slot* s, hipStream_t st, const void* d_pts, size_t n, void* d_raw) {
@@ -392,7 +405,7 @@ int g1_compress_dev(Slot* s, hipStream_t st, const void* d_pts, size_t n, void* 
 }
 
 static HFp2 f2_pow(HFp2 a, const uint64_t e[4]);
-int g2_decompress_dev(Slot* s, hipStream_t st, const void* d_raw, size_t n, void* d_out, int* d_status) {
+int g2_decompress_dev(Slot* s, hipStream_t st, const void* d_raw, size_t n, void* d_out, int* d_status, uint8_t* d_bad) {
     HFp nine = HFp::zero(), three = HFp::one() + HFp::one() + HFp::one();
     for (int i = 0; i < 3; i++) nine = nine + three;
     const HFp2 bt = HFp2{three, HFp::zero()} * HFp2{nine, HFp::one()}.inv();
@@ -409,15 +422,15 @@ int g2_decompress_dev(Slot* s, hipStream_t st, const void* d_raw, size_t n, void
     memcpy(&psi.half, &half, sizeof half);
     static const int full = ZK_EXP("ZKMI_G2_FULL_SUBGROUP_CHECK", 0);
     if (n) {
-        ZK_LAUNCH(s, st, "g2_decompress", k_g2_decompress, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, (const uint32_t*)d_raw, n, btd, psi, (Affine<Fp2>*)d_out, d_status);
+        ZK_LAUNCH(s, st, "g2_decompress", k_g2_decompress, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, (const uint32_t*)d_raw, n, btd, psi, (Affine<Fp2>*)d_out, d_status, d_bad);
         const dim3 grid((unsigned)((n + 127) / 128));
         if (full) {
-            ZK_LAUNCH(s, st, "g2_subgroup", (k_g2_subgroup<true>), grid, dim3(128), 0, (Affine<Fp2>*)d_out, n, (const XYZZ<Fp2>*)nullptr, psi, d_status);
+            ZK_LAUNCH(s, st, "g2_subgroup", (k_g2_subgroup<true>), grid, dim3(128), 0, (Affine<Fp2>*)d_out, n, (const XYZZ<Fp2>*)nullptr, psi, d_status, d_bad);
         } else {
             XYZZ<Fp2>* x0p = (XYZZ<Fp2>*)s->alloc(n * sizeof(XYZZ<Fp2>));  // [x0] P of every point, between the two kernels of the test (the caller reserved it: G2_DECOMPRESS_SCRATCH)
             if (!x0p) return set_err(ZK_ERR_ARG, "G2 decompression: the slot's workspace has no room for %zu scratch points", n);
             ZK_LAUNCH(s, st, "g2_x0_mul", k_g2_x0_mul, grid, dim3(128), 0, (const Affine<Fp2>*)d_out, n, x0p);
-            ZK_LAUNCH(s, st, "g2_subgroup", (k_g2_subgroup<false>), grid, dim3(128), 0, (Affine<Fp2>*)d_out, n, (const XYZZ<Fp2>*)x0p, psi, d_status);
+            ZK_LAUNCH(s, st, "g2_subgroup", (k_g2_subgroup<false>), grid, dim3(128), 0, (Affine<Fp2>*)d_out, n, (const XYZZ<Fp2>*)x0p, psi, d_status, d_bad);
         }
     }
     return ZK_OK;

@@ -13,13 +13,14 @@ int hex_encode_dev(Slot* s, hipStream_t st, const void* d_bytes, size_t n_bytes,
 int fr_from_be_dev(Slot* s, hipStream_t st, const void* d_raw, size_t n, void* d_out, int* d_status);
 int fr_to_be_dev(Slot* s, hipStream_t st, const void* d_in, size_t n, void* d_raw);
 // n x 32-byte compressed G1 points (G1Affine.Bytes()) <-> affine Montgomery images; *d_status |= 4 on an invalid encoding
-int g1_decompress_dev(Slot* s, hipStream_t st, const void* d_raw, size_t n, void* d_out, int* d_status);
+// d_bad (decompress only, may be NULL): d_bad[i] = 1 for every invalid point i (the caller zeroes it), for callers that need a verdict per point
+int g1_decompress_dev(Slot* s, hipStream_t st, const void* d_raw, size_t n, void* d_out, int* d_status, uint8_t* d_bad = nullptr);
 int g1_compress_dev(Slot* s, hipStream_t st, const void* d_pts, size_t n, void* d_raw);
 // n x 64-byte compressed G2 points <-> affine Montgomery images; *d_status |= 8 on an invalid encoding, |= 16 on a point outside the r-torsion.
 // d_idx (compress only, may be NULL): gather -- point i of the output is d_pts[d_idx[i]]
 // (takes n * G2_DECOMPRESS_SCRATCH bytes from the slot's arena, 256-byte aligned per call: the caller's reserve() includes them)
 static constexpr size_t G2_DECOMPRESS_SCRATCH = 256;
-int g2_decompress_dev(Slot* s, hipStream_t st, const void* d_raw, size_t n, void* d_out, int* d_status);
+int g2_decompress_dev(Slot* s, hipStream_t st, const void* d_raw, size_t n, void* d_out, int* d_status, uint8_t* d_bad = nullptr);
 int g2_compress_dev(Slot* s, hipStream_t st, const void* d_pts, const uint32_t* d_idx, size_t n, void* d_raw);
 int g1_compress_idx_dev(Slot* s, hipStream_t st, const void* d_pts, const uint32_t* d_idx, size_t n, void* d_raw);
 // one byte per point of a wire-indexed array: 1 = the point at infinity (gnark's InfinityA / InfinityB)

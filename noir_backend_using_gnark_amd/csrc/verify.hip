@@ -14,6 +14,7 @@
 #include "keyio.hpp"
 #include "pairing.hpp"
 #include "proofio.hpp"
+#include "verify.hpp"
 
 namespace zkmi {
 namespace {
@@ -97,6 +98,24 @@ bool kzg_check(const G1& digest, const G1& h, const HFr& value, const HFr& point
 }
 
 }  // namespace
+
+// VerifyingKey.ReadFrom: [alpha]1 [beta]1 [beta]2 [gamma]2 [delta]1 [delta]2 u32 len(K) K, compressed (groth16_verify and the batch verifier)
+int groth16_vk_parse(const void* vk, size_t vk_len, int vk_is_hex, Groth16Vk* out) {
+    std::vector<uint8_t>& kb = out->bytes;
+    if (!blob_bytes(vk, vk_len, vk_is_hex, &kb)) return set_err(ZK_ERR_ARG, "verifying key: invalid hex text");
+    if (kb.size() < 292) return set_err(ZK_ERR_LEN, "verifying key: %zu bytes, at least 292 expected", kb.size());
+    const size_t nk = ((size_t)kb[288] << 24) | ((size_t)kb[289] << 16) | ((size_t)kb[290] << 8) | kb[291];
+    if (kb.size() != 292 + 32 * nk) return set_err(ZK_ERR_LEN, "verifying key: %zu bytes, the count says %zu K points (%zu bytes)", kb.size(), nk, 292 + 32 * nk);
+    if (!g1_decompress_host(kb.data(), &out->alpha) || !g1_decompress_host(kb.data() + 32, &out->beta1) || !g1_decompress_host(kb.data() + 192, &out->delta1))
+        return set_err(ZK_ERR_ARG, "verifying key: invalid G1 point");
+    if (!g2_decompress_host(kb.data() + 64, &out->beta) || !g2_decompress_host(kb.data() + 128, &out->gamma) || !g2_decompress_host(kb.data() + 224, &out->delta))
+        return set_err(ZK_ERR_ARG, "verifying key: invalid G2 point");
+    out->K.resize(nk);
+    for (size_t i = 0; i < nk; i++)
+        if (!g1_decompress_host(kb.data() + 292 + 32 * i, &out->K[i])) return set_err(ZK_ERR_ARG, "verifying key: invalid K point %zu", i);
+    return ZK_OK;
+}
+
 }  // namespace zkmi
 
 using namespace zkmi;
@@ -110,20 +129,14 @@ extern "C" {
 int zk_bn254_groth16_verify(const uint8_t proof[128], const void* vk, size_t vk_len, int vk_is_hex, const zk_fr* public_inputs, size_t n_public, int* accepted) {
     if (!proof || !vk || !accepted || (n_public && !public_inputs)) return set_err(ZK_ERR_ARG, "null pointer");
     *accepted = 0;
-    std::vector<uint8_t> kb;
-    if (!blob_bytes(vk, vk_len, vk_is_hex, &kb)) return set_err(ZK_ERR_ARG, "verifying key: invalid hex text");
-    if (kb.size() < 292) return set_err(ZK_ERR_LEN, "verifying key: %zu bytes, at least 292 expected", kb.size());
-    const size_t nk = ((size_t)kb[288] << 24) | ((size_t)kb[289] << 16) | ((size_t)kb[290] << 8) | kb[291];
-    if (kb.size() != 292 + 32 * nk) return set_err(ZK_ERR_LEN, "verifying key: %zu bytes, the count says %zu K points (%zu bytes)", kb.size(), nk, 292 + 32 * nk);
-    G1 alpha, beta1, delta1, ar, krs;
-    G2 beta, gamma, delta, bs;
-    if (!g1_decompress_host(kb.data(), &alpha) || !g1_decompress_host(kb.data() + 32, &beta1) || !g1_decompress_host(kb.data() + 192, &delta1))
-        return set_err(ZK_ERR_ARG, "verifying key: invalid G1 point");
-    if (!g2_decompress_host(kb.data() + 64, &beta) || !g2_decompress_host(kb.data() + 128, &gamma) || !g2_decompress_host(kb.data() + 224, &delta))
-        return set_err(ZK_ERR_ARG, "verifying key: invalid G2 point");
-    std::vector<G1> K(nk);
-    for (size_t i = 0; i < nk; i++)
-        if (!g1_decompress_host(kb.data() + 292 + 32 * i, &K[i])) return set_err(ZK_ERR_ARG, "verifying key: invalid K point %zu", i);
+    Groth16Vk v;
+    ZK_TRY(groth16_vk_parse(vk, vk_len, vk_is_hex, &v));
+    const size_t nk = v.K.size();
+    const std::vector<G1>& K = v.K;
+    const G1 &alpha = v.alpha;
+    const G2 &beta = v.beta, &gamma = v.gamma, &delta = v.delta;
+    G1 ar, krs;
+    G2 bs;
     if (!g1_decompress_host(proof, &ar) || !g2_decompress_host(proof + 32, &bs) || !g1_decompress_host(proof + 96, &krs))
         return set_err(ZK_ERR_ARG, "proof: invalid point encoding");
     if (nk != n_public + 1) return set_err(ZK_ERR_LEN, "invalid witness size, got %zu, expected %zu (public - ONE_WIRE)", n_public, nk ? nk - 1 : 0);  // upstream's message

@@ -54,3 +54,43 @@ def pairing_check(g1_points, g2_points) -> bool:
     if len(p) != len(q):
         raise ValueError("as many G1 as G2 points")
     return _call(lib().zk_bn254_pairing_check, vp(p) if len(p) else None, vp(q) if len(q) else None, C.c_size_t(len(p)))
+
+
+def pair(g1_points, g2_points, on_device: bool = True) -> np.ndarray:
+    """prod_i e(P_i, Q_i), the reduced optimal ate pairing, as bn254.GT's memory image ((48,) uint64: E12 C0.B0 .. C1.B2, Montgomery).
+    on_device=False computes the same value on the host.  The value is exactly f^((q^12 - 1) / r) for the host Miller product f; it is not claimed to
+    equal gnark-crypto's bn254.Pair value (a fixed power of it may differ), only products tested against one are comparable across libraries."""
+    p = np.ascontiguousarray(g1_points, dtype=np.uint64).reshape(-1, 8)
+    q = np.ascontiguousarray(g2_points, dtype=np.uint64).reshape(-1, 16)
+    if len(p) != len(q):
+        raise ValueError("as many G1 as G2 points")
+    out = np.zeros(48, np.uint64)
+    fn = lib().zk_bn254_pair if on_device else lib().zk_bn254_pair_host
+    check(fn(vp(p) if len(p) else None, vp(q) if len(q) else None, C.c_size_t(len(p)), vp(out)))
+    return out
+
+
+def groth16_verify_batch(proofs, vk, public_inputs) -> np.ndarray:
+    """groth16.Verify for many proofs against ONE verifying key, on the device: one verdict per proof, equal to groth16_verify's, except that a
+    malformed proof encoding gives False instead of an error.  proofs: a sequence of 128-byte proofs (or their concatenation); public_inputs:
+    (n_proofs, n_public, 4) Montgomery limbs, without the constant wire."""
+    blob = bytes(proofs) if isinstance(proofs, (bytes, bytearray)) else b"".join(bytes(x) for x in proofs)
+    if len(blob) % 128:
+        raise ValueError("a Groth16 proof is 128 bytes (Proof.WriteTo)")
+    n = len(blob) // 128
+    k, is_hex = _blob(vk)
+    pub = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+    if pub.size == 0:
+        n_public = pub.shape[1] if pub.ndim == 3 and pub.shape[0] == n else 0
+        pub = np.zeros((max(n, 1), max(n_public, 1), 4), np.uint64)
+    else:
+        pub = pub.reshape(n, -1, 4)
+        n_public = pub.shape[1]
+    acc = np.zeros(max(n, 1), np.uint8)
+    n_acc = C.c_size_t(0)
+    rc = lib().zk_bn254_groth16_verify_batch(C.c_char_p(blob), C.c_size_t(n), C.c_char_p(k), C.c_size_t(len(k)), C.c_int(is_hex),
+                                             vp(pub) if n_public else None, C.c_size_t(n_public), vp(acc), C.byref(n_acc))
+    if rc in (_lib.ZK_ERR_LEN, _lib.ZK_ERR_ARG):
+        raise ValueError((lib().zk_last_error() or b"").decode())
+    check(rc)
+    return acc[:n].astype(bool)
