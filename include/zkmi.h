@@ -322,7 +322,7 @@ int zk_bn254_plonk_verify(const uint8_t proof[548] /* ZK_PLONK_PROOF_BYTES */, c
                           const zk_fr *public_inputs, size_t n_public, int *accepted);
 int zk_bn254_pairing_check(const zk_g1_affine *p, const zk_g2_affine *q, size_t n, int *is_one);
 
-/* ---- Pairings and batch Groth16 verification on the DEVICE.
+/* ---- Pairings and batch Groth16 / PLONK verification on the DEVICE.
  * zk_gt is bn254.GT's memory image: E12 {C0 E6{B0, B1, B2}, C1 E6{...}}, each E2 {A0, A1}, Montgomery (384 bytes) -- gnark's tower Fp6 = Fp2[v]/(v^3 - xi),
  * Fp12 = Fp6[w]/(w^2 - v), xi = 9 + u.
  *   zk_bn254_pair      : prod_i e(p_i, q_i), the reduced optimal ate pairing, exactly f^((q^12 - 1) / r) with f = prod_i of the Miller values of the host
@@ -340,12 +340,27 @@ int zk_bn254_pairing_check(const zk_g1_affine *p, const zk_g2_affine *q, size_t 
  *                        derived, not random, so results are reproducible; a batch with an invalid proof passes with probability about 2^-128 in the
  *                        random-oracle model.  If that check fails, every valid proof is checked on its own on the device.  Proofs go through in chunks of
  *                        at most 2^16; the device workspace is about 5 KB + 96 (n_public + 1) bytes per proof of a chunk.
- * Both device entries return ZK_ERR_NO_DEVICE without a GPU, after argument validation; there is no CPU fallback. */
+ *   zk_bn254_plonk_verify_batch : plonk.Verify for n_proofs proofs (n_proofs x 548 bytes, Proof.WriteTo) against ONE verifying key (368 bytes, bytes or hex)
+ *                        and the SRS's srs_g2 = ([1]2, [alpha]2); public_inputs: n_proofs x n_public Montgomery fr.Elements, row-major.  accepted[i] equals
+ *                        what zk_bn254_plonk_verify says of proof i, except that a malformed proof (an invalid point encoding, a batched-opening count other
+ *                        than 7) -- ZK_ERR_ARG there -- is a 0 here and does not affect the other proofs.  Claimed values are reduced mod r (fr.SetBytes), as
+ *                        on the host.  A malformed key, and n_public != NbPublicVariables, are ZK_ERR_ARG / ZK_ERR_LEN with the host verifier's messages.
+ *                        Each proof's transcript, quotient identity and folded KZG opening are computed on the device, one lane per proof; a proof that
+ *                        fails its quotient identity is rejected there.  The 2 n KZG openings of the remaining n proofs are then checked together:
+ *                        e(sum_i rho_i (D_i - e_i G + zeta_i W_i) + rho'_i (Z_i - zu_i G + zeta_i omega W'_i), [1]2) e(-sum_i rho_i W_i + rho'_i W'_i, [alpha]2)
+ *                        == 1 -- two Miller loops whatever n is -- with rho_i, rho'_i = the low 128 bits of SHA-256("zkmi-plonk-batch" || SHA-256(vk bytes) ||
+ *                        SHA-256(srs_g2) || SHA-256(proofs || public inputs) || u64 i little-endian || 0 / 1), forced non-zero.  If that check fails, every
+ *                        remaining proof gets its own two-pairing check on the device.  Chunks of at most 2^16 proofs; the device workspace is about
+ *                        8.4 KB + 32 n_public bytes per proof of a chunk.
+ * The device entries return ZK_ERR_NO_DEVICE without a GPU, after argument validation; there is no CPU fallback. */
 typedef struct { zk_fp c[12]; } zk_gt;
 int zk_bn254_pair(const zk_g1_affine *p, const zk_g2_affine *q, size_t n, zk_gt *out);
 int zk_bn254_pair_host(const zk_g1_affine *p, const zk_g2_affine *q, size_t n, zk_gt *out);
 int zk_bn254_groth16_verify_batch(const uint8_t *proofs, size_t n_proofs, const void *vk, size_t vk_len, int vk_is_hex, const zk_fr *public_inputs,
                                   size_t n_public, uint8_t *accepted, size_t *n_accepted);
+int zk_bn254_plonk_verify_batch(const uint8_t *proofs, size_t n_proofs, const void *vk, size_t vk_len, int vk_is_hex,
+                                const zk_g2_affine srs_g2[2], const zk_fr *public_inputs, size_t n_public,
+                                uint8_t *accepted, size_t *n_accepted);
 
 /* The two halves of zk_bn254_groth16_prove, exposed so that one proof can be range-sharded over several GPUs
  * (one process per GPU): every rank runs the five MSMs on ITS slice of the bases / wire values / h, the un-normalised

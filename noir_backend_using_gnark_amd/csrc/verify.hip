@@ -116,6 +116,23 @@ int groth16_vk_parse(const void* vk, size_t vk_len, int vk_is_hex, Groth16Vk* ou
     return ZK_OK;
 }
 
+// plonk.VerifyingKey.ReadFrom: Size u64 | SizeInv | Generator | NbPublicVariables u64 | CosetShift | S1..S3 Ql Qr Qm Qo Qk (plonk_verify and the batch verifier)
+int plonk_vk_parse(const void* vk, size_t vk_len, int vk_is_hex, PlonkVk* out) {
+    std::vector<uint8_t>& kb = out->bytes;
+    if (!blob_bytes(vk, vk_len, vk_is_hex, &kb)) return set_err(ZK_ERR_ARG, "verifying key: invalid hex text");
+    if (kb.size() != 368) return set_err(ZK_ERR_LEN, "verifying key: %zu bytes, 368 expected", kb.size());
+    const uint64_t n = be64(kb.data()), npub = be64(kb.data() + 72);
+    if (n == 0 || (n & (n - 1)) || n > ((uint64_t)1 << 28)) return set_err(ZK_ERR_ARG, "verifying key: size %llu is not a power of two <= 2^28", (unsigned long long)n);
+    out->n = n;
+    out->npub = npub;
+    out->size_inv = fr_from_be_reduce(kb.data() + 8);
+    out->gen = fr_from_be_reduce(kb.data() + 40);
+    out->u = fr_from_be_reduce(kb.data() + 80);
+    for (int k = 0; k < 8; k++)
+        if (!g1_decompress_host(kb.data() + 112 + 32 * k, &out->pts[k])) return set_err(ZK_ERR_ARG, "verifying key: invalid G1 point %d", k);
+    return ZK_OK;
+}
+
 }  // namespace zkmi
 
 using namespace zkmi;
@@ -158,15 +175,11 @@ int zk_bn254_plonk_verify(const uint8_t proof[548], const void* vk, size_t vk_le
                           int* accepted) {
     if (!proof || !vk || !srs_g2 || !accepted || (n_public && !public_inputs)) return set_err(ZK_ERR_ARG, "null pointer");
     *accepted = 0;
-    std::vector<uint8_t> kb;
-    if (!blob_bytes(vk, vk_len, vk_is_hex, &kb)) return set_err(ZK_ERR_ARG, "verifying key: invalid hex text");
-    if (kb.size() != 368) return set_err(ZK_ERR_LEN, "verifying key: %zu bytes, 368 expected", kb.size());
-    const uint64_t n = be64(kb.data()), npub = be64(kb.data() + 72);
-    if (n == 0 || (n & (n - 1)) || n > ((uint64_t)1 << 28)) return set_err(ZK_ERR_ARG, "verifying key: size %llu is not a power of two <= 2^28", (unsigned long long)n);
-    const HFr size_inv = fr_from_be_reduce(kb.data() + 8), gen = fr_from_be_reduce(kb.data() + 40), u = fr_from_be_reduce(kb.data() + 80);
-    G1 vkp[8];  // S1, S2, S3, Ql, Qr, Qm, Qo, Qk
-    for (int k = 0; k < 8; k++)
-        if (!g1_decompress_host(kb.data() + 112 + 32 * k, &vkp[k])) return set_err(ZK_ERR_ARG, "verifying key: invalid G1 point %d", k);
+    PlonkVk v;
+    ZK_TRY(plonk_vk_parse(vk, vk_len, vk_is_hex, &v));
+    const uint64_t n = v.n, npub = v.npub;
+    const HFr &size_inv = v.size_inv, &gen = v.gen, &u = v.u;
+    const G1* vkp = v.pts;  // S1, S2, S3, Ql, Qr, Qm, Qo, Qk
     G1 lro[3], z, h[3], batch_h, z_open_h;
     bool ok = true;
     for (int k = 0; k < 3; k++) ok = ok && g1_decompress_host(proof + 32 * k, &lro[k]) && g1_decompress_host(proof + 128 + 32 * k, &h[k]);

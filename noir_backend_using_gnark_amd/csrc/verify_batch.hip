@@ -1,4 +1,4 @@
-// Pairings and batch Groth16 verification on the device (include/zkmi.h "Pairings and batch Groth16 verification on the DEVICE").
+// Pairings and batch Groth16 / PLONK verification on the device (include/zkmi.h "Pairings and batch Groth16 / PLONK verification on the DEVICE").
 //   zk_bn254_pair          one Miller loop per lane (k_miller), a product tree (k_f12_fold), one final exponentiation (k_fe_*)
 //   zk_bn254_groth16_verify_batch, per chunk of at most 2^16 proofs:
 //     decode      Ar / Krs through k_g1_decompress, Bs through k_g2_decompress + the r-torsion test, with a flag per invalid point
@@ -9,6 +9,13 @@
 //     fallback    (only when the check fails) k_vb_single: -Ar_i, IC_i = K_0 + sum_j w_ij K_j, Krs_i per lane; 3 n + 1 Miller loops (the last one is
 //                 e(alpha, beta)'s); k_fe_easy multiplies each proof's three values and e(alpha, beta)'s, the k_fe_* chain exponentiates, k_fe_last
 //                 compares with one
+//   zk_bn254_plonk_verify_batch, per chunk of at most 2^16 proofs (one lane per proof):
+//     decode      k_pv_gather (header, points, values mod r), k_g1_decompress over the nine points with a flag per invalid point
+//     per proof   k_pv_transcript (gamma, beta, alpha, zeta from SHA-256 on the device), k_pv_scalars (PI, L1, the quotient identity), k_pv_smul + k_pv_digests
+//                 (folded quotient and linearised digests), k_pv_kzg (kzg's folding challenge, rho_i, rho'_i, the scalars of the combined openings)
+//     check       k_pv_smul + k_pv_combine: A_i = rho_i (D_i - e_i G + zeta_i W_i) + rho'_i (Z_i - zu_i G + zeta_i omega W'_i) without the fixed points,
+//                 B_i = rho_i W_i + rho'_i W'_i; k_g1_fold / k_fr_fold sum them; the host adds the G, S1, S2 terms; e(sum A, [1]2) e(-sum B, [alpha]2) == 1
+//     fallback    (only when the check fails) each proof's own A_i, -B_i (k_pv_single), 2 n Miller loops, a final exponentiation and a verdict per proof
 #include <string.h>
 
 #include <algorithm>
@@ -21,6 +28,7 @@
 #include "pairing.hpp"
 #include "pairing_dev.hpp"
 #include "proofio.hpp"
+#include "sha256_dev.hpp"
 #include "verify.hpp"
 
 using namespace zkmi;
@@ -165,6 +173,303 @@ __global__ __launch_bounds__(128) void k_vb_single(const Affine<Fp>* __restrict_
         ic.add(scalar_mul(kpts[1 + j], w.l));
     }
     P[n + i] = ic.to_affine();
+}
+
+// ---- batch PLONK verification: one lane per proof, Fr values per lane as columns sc[k n + i]
+enum PvCol {
+    PV_CLAIM = 0,  // 7 claimed values: quotient, linearised polynomial, l, r, o, s1, s2 at zeta (reduced mod r)
+    PV_ZU = 7,     // z(omega zeta)
+    PV_GAMMA, PV_BETA, PV_ALPHA, PV_ZETA,  // the transcript's challenges (this order: PV_GAMMA + c)
+    PV_ZP, PV_ZP2, PV_LR, PV_CS3, PV_CZ,   // the digests' scalars: zeta^(n+2), zeta^(2(n+2)), l r, S3's and Z's coefficients
+    PV_T,          // 10 scalars of the combined opening check (k_pv_kzg)
+    PV_NCOL = PV_T + 10
+};
+// points per lane (pts[k n + i]) in proof order: L R O Z H0 H1 H2 BatchH ZShiftH; the key's points (device copy): S1 S2 S3 Ql Qr Qm Qo Qk, then G
+enum { PV_L = 0, PV_Z = 3, PV_H0 = 4, PV_W = 7, PV_WS = 8, PV_NPTS = 9 };
+struct PvKey {
+    uint64_t n;
+    uint32_t log_n;
+    Fr size_inv, gen, u;
+};
+// one scalar multiplication per lane: out = k_i P_i (P fixed when step == 0); k_pv_smul runs a table of them, one per grid row
+struct PvTerm {
+    const Affine<Fp>* pts;
+    size_t step;
+    const Fr* sc;
+};
+
+// 256-bit big-endian word image (8 x u32 read straight from the bytes) -> limbs, reduced mod r as fr.SetBytes, Montgomery
+ZK_D Fr fr_from_be_words(const uint32_t* p) {
+    uint32_t t[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) t[k] = __builtin_bswap32(p[7 - k]);
+    Fr r = Fr::reduce_once(t);
+#pragma unroll
+    for (int k = 0; k < 4; k++) r = Fr::reduce_once(r.l);  // 2^256 < 6 r
+    return r.to_mont();
+}
+// a digest as fr.SetBytes reads it
+ZK_D Fr fr_from_digest(const uint32_t d[8]) {
+    uint32_t t[8];
+    sha_words_to_limbs(d, t);
+    Fr r = Fr::reduce_once(t);
+#pragma unroll
+    for (int k = 0; k < 4; k++) r = Fr::reduce_once(r.l);
+    return r.to_mont();
+}
+// one 32-byte half of G1Affine.RawBytes() (X || Y big-endian; infinity = 0x40 then zeros) as limbs
+ZK_D void raw_half(const Affine<Fp>& p, int half, uint32_t l[8]) {
+    Fp c = p.x;
+    if (half) c = p.y;
+    c = c.from_mont();
+#pragma unroll
+    for (int k = 0; k < 8; k++) l[k] = c.l[k];
+    if (!half && p.is_inf()) l[7] = 0x40000000u;
+}
+
+// header (bytes 256..259 = 00 00 00 07), the nine compressed points into their own arrays, the eight values reduced mod r
+__global__ __launch_bounds__(256) void k_pv_gather(const uint32_t* __restrict__ proofs, size_t n, uint32_t* __restrict__ praw, Fr* __restrict__ sc,
+                                                   uint8_t* __restrict__ hdr_bad) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* p = proofs + i * (548 / 4);
+    const int off[PV_NPTS] = {0, 8, 16, 24, 32, 40, 48, 56, 121};
+#pragma unroll
+    for (int k = 0; k < PV_NPTS; k++)
+#pragma unroll
+        for (int j = 0; j < 8; j++) praw[(k * n + i) * 8 + j] = p[off[k] + j];
+    hdr_bad[i] = p[64] != 0x07000000u;  // little-endian read of 00 00 00 07
+#pragma unroll 1
+    for (int k = 0; k < 8; k++) sc[(PV_CLAIM + k) * n + i] = fr_from_be_words(p + (k < 7 ? 65 + 8 * k : 129));
+}
+
+// gamma, beta, alpha, zeta as FsTranscript derives them.  gamma's prefix ("gamma" || S1..Qk) is the same for every lane: the host hashed its whole blocks
+// (mid = the chaining value after mid_len bytes) and pre holds the rest, then "beta", "alpha", "zeta"
+__global__ __launch_bounds__(64) void k_pv_transcript(const Affine<Fp>* __restrict__ pts, const uint8_t* __restrict__ bad, const uint8_t* __restrict__ hdr_bad,
+                                                      const Fr* __restrict__ pub, size_t n, size_t np, const uint32_t* __restrict__ mid, uint64_t mid_len,
+                                                      const uint8_t* __restrict__ pre, uint32_t tail_len, uint8_t* __restrict__ valid, Fr* __restrict__ sc) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bool ok = !hdr_bad[i];
+    for (int k = 0; k < PV_NPTS; k++) ok = ok && !bad[k * n + i];
+    valid[i] = ok;
+    if (!ok) return;
+    uint32_t prev[8];
+#pragma unroll 1
+    for (int c = 0; c < 4; c++) {
+        Sha256Dev h;
+        if (c == 0) h.resume(mid, mid_len);
+        else h.reset();
+        const uint32_t off = c == 0 ? 0 : c == 1 ? tail_len : c == 2 ? tail_len + 4 : tail_len + 9, len = c == 0 ? tail_len : c == 2 ? 5 : 4;
+        h.update(pre + off, len);
+        if (c) h.put256(prev);
+        // bindings: gamma: public inputs, L, R, O; beta: none; alpha: Z; zeta: H0, H1, H2 -- 32-byte items
+        const size_t items = c == 0 ? np + 6 : c == 1 ? 0 : c == 2 ? 2 : 6;
+#pragma unroll 1
+        for (size_t j = 0; j < items; j++) {
+            uint32_t l[8];
+            if (c == 0 && j < np) {
+                const Fr w = pub[i * np + j].from_mont();
+#pragma unroll
+                for (int k = 0; k < 8; k++) l[k] = w.l[k];
+            } else {
+                const size_t q = c == 0 ? j - np : j;
+                const int pt = (c == 0 ? PV_L : c == 2 ? PV_Z : PV_H0) + (int)(q >> 1);
+                raw_half(pts[pt * n + i], (int)(q & 1), l);
+            }
+            h.put256(l);
+        }
+        uint32_t d[8];
+        h.final(d);
+        sha_words_to_limbs(d, prev);  // the next challenge binds the raw digest
+        sc[(PV_GAMMA + c) * n + i] = fr_from_digest(d);
+    }
+}
+
+// zeta^n, PI(zeta), L1(zeta) and the quotient identity (a lane that fails it is invalid from here on); the digests' scalars.
+// PI(zeta) = sum_j w^j / n (zeta^n - 1) w_j / (zeta - w^j) accumulates as one fraction N / D: one inversion for all denominators
+__global__ __launch_bounds__(64) void k_pv_scalars(const Fr* __restrict__ pub, size_t n, size_t np, PvKey K, uint8_t* __restrict__ valid, Fr* __restrict__ sc) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !valid[i]) return;
+    const Fr one = Fr::one();
+    const Fr gamma = sc[PV_GAMMA * n + i], beta = sc[PV_BETA * n + i], alpha = sc[PV_ALPHA * n + i], zeta = sc[PV_ZETA * n + i];
+    Fr zn = zeta;
+    for (uint32_t k = 0; k < K.log_n; k++) zn = zn.sqr();
+    const Fr zz = zn - one, szz = K.size_inv * zz;
+    Fr num = Fr::zero(), den = one, wi = one;
+    for (size_t j = 0; j < np; j++) {
+        const Fr d = zeta - wi;
+        num = num * d + wi * szz * pub[i * np + j] * den;
+        den = den * d;
+        wi = wi * K.gen;
+    }
+    Fr pi = num * den.inv();
+    if (den.is_zero()) {  // zeta = w^j for some j: term by term, with inv(0) = 0 as the host
+        pi = Fr::zero();
+        wi = one;
+        for (size_t j = 0; j < np; j++) {
+            pi = pi + wi * szz * (zeta - wi).inv() * pub[i * np + j];
+            wi = wi * K.gen;
+        }
+    }
+    const Fr l1 = szz * (zeta - one).inv();
+    const Fr quot = sc[(PV_CLAIM + 0) * n + i], lin_z = sc[(PV_CLAIM + 1) * n + i], lz = sc[(PV_CLAIM + 2) * n + i], rz = sc[(PV_CLAIM + 3) * n + i],
+             oz = sc[(PV_CLAIM + 4) * n + i], s1z = sc[(PV_CLAIM + 5) * n + i], s2z = sc[(PV_CLAIM + 6) * n + i], zu = sc[PV_ZU * n + i];
+    const Fr f1 = lz + beta * s1z + gamma, f2 = rz + beta * s2z + gamma;
+    const Fr aa = alpha * alpha;
+    if (lin_z + pi + f1 * f2 * (oz + gamma) * alpha * zu - aa * l1 != quot * zz) {
+        valid[i] = 0;
+        return;
+    }
+    const Fr zp = zn * zeta.sqr(), bz = beta * zeta;
+    sc[PV_ZP * n + i] = zp;
+    sc[PV_ZP2 * n + i] = zp.sqr();
+    sc[PV_LR * n + i] = lz * rz;
+    sc[PV_CS3 * n + i] = f1 * f2 * zu * beta * alpha;
+    sc[PV_CZ * n + i] = (lz + bz + gamma).neg() * (rz + bz * K.u + gamma) * (oz + bz * K.u.sqr() + gamma) * alpha + aa * l1;
+}
+
+// out[t n + i] = k P for term t = blockIdx.y of the table (infinity for an invalid lane)
+__global__ __launch_bounds__(64) void k_pv_smul(const PvTerm* __restrict__ terms, size_t n, const uint8_t* __restrict__ valid, XYZZ<Fp>* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PvTerm T = terms[blockIdx.y];
+    XYZZ<Fp> r = XYZZ<Fp>::inf();
+    if (valid[i]) {
+        const Fr k = T.sc[i].from_mont();
+        r = scalar_mul(T.pts[T.step * i], k.l);
+    }
+    out[blockIdx.y * n + i] = r;
+}
+
+// the folded quotient digest H0 + zeta^(n+2) H1 + zeta^(2(n+2)) H2 and the linearised digest (terms 2..7 + Qk), affine
+__global__ __launch_bounds__(64) void k_pv_digests(const Affine<Fp>* __restrict__ pts, const XYZZ<Fp>* __restrict__ t, const Affine<Fp>* __restrict__ kpts, size_t n,
+                                                   const uint8_t* __restrict__ valid, Affine<Fp>* __restrict__ dig) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !valid[i]) return;
+    XYZZ<Fp> fh = t[i];
+    fh.add(t[n + i]);
+    fh.madd(pts[PV_H0 * n + i]);
+    XYZZ<Fp> lin = t[2 * n + i];
+    for (int k = 3; k < 8; k++) lin.add(t[k * n + i]);
+    lin.madd(kpts[7]);
+    dig[i] = fh.to_affine();
+    dig[n + i] = lin.to_affine();
+}
+
+// kzg.deriveGamma over zeta, the seven digests and the claimed values, then the lane's coefficients rho, rho' (SHA-256 of the host's prefix -- mid after 64
+// bytes, then rtail -- || u64 index || tag byte) and the scalars of  rho (D - e G + zeta W) + rho' (Z - zu G + zeta omega W')  and  rho W + rho' W':
+// per-lane terms into PV_T.., the fixed points' coefficients (G, S1, S2) into fix (columns) and fold (rows, k_fr_fold's input)
+__global__ __launch_bounds__(64) void k_pv_kzg(const Affine<Fp>* __restrict__ pts, const Affine<Fp>* __restrict__ dig, const Affine<Fp>* __restrict__ kpts, size_t n,
+                                               size_t c0, PvKey K, const uint32_t* __restrict__ rmid, const uint8_t* __restrict__ rtail,
+                                               const uint8_t* __restrict__ valid, Fr* __restrict__ sc, Fr* __restrict__ fix, Fr* __restrict__ fold) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (!valid[i]) {
+        for (int j = 0; j < 3; j++) fix[j * n + i] = fold[3 * i + j] = Fr::zero();
+        return;
+    }
+    const Fr zeta = sc[PV_ZETA * n + i];
+    Fr kg;
+    {
+        Sha256Dev h;
+        h.reset();
+        const uint64_t name = 0x67616d6d61ull;  // "gamma"
+#pragma unroll 1
+        for (int k = 4; k >= 0; k--) h.put_byte((uint32_t)(name >> (8 * k)));
+#pragma unroll 1
+        for (int j = 0; j < 22; j++) {  // zeta, fh lin L R O S1 S2 (X, Y each), the seven claimed values
+            uint32_t l[8];
+            if (j == 0 || j >= 15) {
+                Fr v = zeta;  // (not a ?: of references: that would put zeta in memory)
+                if (j) v = sc[(PV_CLAIM + j - 15) * n + i];
+                v = v.from_mont();
+#pragma unroll
+                for (int k = 0; k < 8; k++) l[k] = v.l[k];
+            } else {
+                const int d = (j - 1) >> 1;
+                Affine<Fp> p;
+                if (d < 2) p = dig[d * n + i];
+                else if (d < 5) p = pts[(PV_L + d - 2) * n + i];
+                else p = kpts[d - 5];
+                raw_half(p, (j - 1) & 1, l);
+            }
+            h.put256(l);
+        }
+        uint32_t dg[8];
+        h.final(dg);
+        kg = fr_from_digest(dg);
+    }
+    Fr rho = Fr::zero(), rho2 = Fr::zero();
+    const uint64_t idx = c0 + i;
+#pragma unroll 1
+    for (int tag = 0; tag < 2; tag++) {
+        Sha256Dev h;
+        h.resume(rmid, 64);
+#pragma unroll 1
+        for (int k = 0; k < 48 + 8 + 1; k++) h.put_byte(k < 48 ? rtail[k] : k < 56 ? (uint32_t)(idx >> (8 * (k - 48))) : (uint32_t)tag);
+        uint32_t dg[8];
+        h.final(dg);
+        Fr r = Fr::zero();  // the low 128 bits of the digest as a big-endian integer, forced non-zero
+        r.l[0] = dg[7];
+        r.l[1] = dg[6];
+        r.l[2] = dg[5];
+        r.l[3] = dg[4];
+        if ((r.l[0] | r.l[1] | r.l[2] | r.l[3]) == 0) r.l[0] = 1;
+        r = r.to_mont();
+        if (tag == 0) rho = r;
+        else rho2 = r;
+    }
+    Fr p[7], e = Fr::zero();  // p[k] = rho kg^k; e = sum claimed_k kg^k
+    Fr acc = Fr::one();
+#pragma unroll
+    for (int k = 0; k < 7; k++) {
+        e = e + sc[(PV_CLAIM + k) * n + i] * acc;
+        p[k] = rho * acc;
+        acc = acc * kg;
+    }
+    Fr* T = sc + PV_T * n + i;
+    T[0] = p[0];                 // fh
+    T[n] = p[1];                 // lin
+    T[2 * n] = p[2];             // L
+    T[3 * n] = p[3];             // R
+    T[4 * n] = p[4];             // O
+    T[5 * n] = rho * zeta;       // W
+    T[6 * n] = rho2;             // Z
+    T[7 * n] = rho2 * zeta * K.gen;  // W'
+    T[8 * n] = rho;              // W  (second pairing)
+    T[9 * n] = rho2;             // W' (second pairing)
+    const Fr f[3] = {(rho * e + rho2 * sc[PV_ZU * n + i]).neg(), p[5], p[6]};
+#pragma unroll
+    for (int j = 0; j < 3; j++) fix[j * n + i] = fold[3 * i + j] = f[j];
+}
+
+// A_i = sum of terms 0..7, B_i = terms 8 + 9; a copy of each for the folds (which overwrite their input)
+__global__ __launch_bounds__(256) void k_pv_combine(const XYZZ<Fp>* __restrict__ t, size_t n, XYZZ<Fp>* __restrict__ A, XYZZ<Fp>* __restrict__ B,
+                                                    XYZZ<Fp>* __restrict__ fa, XYZZ<Fp>* __restrict__ fb) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    XYZZ<Fp> a = t[i];
+    for (int k = 1; k < 8; k++) a.add(t[k * n + i]);
+    XYZZ<Fp> b = t[8 * n + i];
+    b.add(t[9 * n + i]);
+    A[i] = fa[i] = a;
+    B[i] = fb[i] = b;
+}
+
+// fallback, per lane: P[i] = A_i + c_G G + c_S1 S1 + c_S2 S2 (t: those three terms), P[n + i] = -B_i (infinity for an invalid lane)
+__global__ __launch_bounds__(256) void k_pv_single(const XYZZ<Fp>* __restrict__ A, const XYZZ<Fp>* __restrict__ B, const XYZZ<Fp>* __restrict__ t, size_t n,
+                                                   const uint8_t* __restrict__ valid, Affine<Fp>* __restrict__ P) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (!valid[i]) {
+        P[i] = P[n + i] = Affine<Fp>::inf();
+        return;
+    }
+    XYZZ<Fp> a = A[i];
+    for (int k = 0; k < 3; k++) a.add(t[k * n + i]);
+    P[i] = a.to_affine();
+    P[n + i] = B[i].to_affine().neg();
 }
 
 // halving launches until one element is left; a and b hold at least ceil(n / 2) elements each (a: n); returns where the result is
@@ -385,6 +690,208 @@ int zk_bn254_groth16_verify_batch(const uint8_t* proofs, size_t n_proofs, const 
         ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(blocks(3 * n + 1, PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_p, 3 * n + 1,
                   (const Affine<Fp2>*)d_bs, n, (const Affine<Fp2>*)d_fix, n, K, d_m);
         ZK_TRY(final_exp(s, st, K, d_m, n, 3, d_m + 3 * n, d_ws, nullptr, d_valid, d_verdict));
+        ZK_HIP(hipMemcpyAsync(accepted + c0, d_verdict, n, hipMemcpyDeviceToHost, st));
+        ZK_TRY(slot_sync(s, st));
+        for (size_t i = 0; i < n; i++) total += accepted[c0 + i] ? 1 : 0;
+    }
+    *n_accepted = total;
+    return ZK_OK;
+}
+
+int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const void* vk, size_t vk_len, int vk_is_hex, const zk_g2_affine srs_g2[2],
+                                const zk_fr* public_inputs, size_t n_public, uint8_t* accepted, size_t* n_accepted) {
+    if (!vk || !srs_g2 || !n_accepted || (n_proofs && (!proofs || !accepted)) || (n_proofs && n_public && !public_inputs))
+        return set_err(ZK_ERR_ARG, "null pointer");
+    *n_accepted = 0;
+    PlonkVk v;
+    ZK_TRY(plonk_vk_parse(vk, vk_len, vk_is_hex, &v));
+    if (v.npub != n_public) return set_err(ZK_ERR_LEN, "invalid witness size, got %zu, expected %llu", n_public, (unsigned long long)v.npub);  // upstream's message
+    if (n_proofs == 0) return ZK_OK;
+    ZK_TRY(ensure_init());
+    const PairConsts PK = pair_consts();
+    const size_t np = n_public;
+    PvKey K;
+    K.n = v.n;
+    K.log_n = 0;
+    while (((uint64_t)1 << K.log_n) < v.n) K.log_n++;
+    K.size_inv = bit_cast_img<Fr>(v.size_inv);
+    K.gen = bit_cast_img<Fr>(v.gen);
+    K.u = bit_cast_img<Fr>(v.u);
+    const Affine<HFp> G{HFp::one(), HFp::one() + HFp::one()};
+    Affine<HFp> kp[9];  // S1 S2 S3 Ql Qr Qm Qo Qk G
+    for (int k = 0; k < 8; k++) kp[k] = v.pts[k];
+    kp[8] = G;
+
+    // gamma's common prefix: "gamma" || RawBytes(S1 .. Qk); the lanes start from the chaining value after its whole blocks
+    Sha256 tg;
+    tg.update("gamma", 5);
+    for (int k = 0; k < 8; k++) {
+        uint8_t b[64];
+        g1_raw_bytes(v.pts[k], b);
+        tg.update(b, 64);
+    }
+    const uint32_t tail_len = (uint32_t)tg.fill;
+    // rho_i, rho'_i = the low 128 bits of SHA-256(tag || SHA-256(vk) || SHA-256(srs_g2) || SHA-256(proofs || public inputs) || u64 i || 0 / 1)
+    uint8_t pre[16 + 3 * 32];
+    memcpy(pre, "zkmi-plonk-batch", 16);
+    sha(v.bytes.data(), v.bytes.size(), pre + 16);
+    sha(srs_g2, 2 * sizeof(zk_g2_affine), pre + 48);
+    {
+        Sha256 h;
+        h.update(proofs, n_proofs * 548);
+        if (np) h.update(public_inputs, n_proofs * np * 32);
+        h.final(pre + 80);
+    }
+    Sha256 tr;
+    tr.update(pre, sizeof pre);  // one whole block, 48 bytes left in buf
+    std::vector<uint8_t> hbytes(tail_len + 13 + 48);
+    memcpy(hbytes.data(), tg.buf, tail_len);
+    memcpy(hbytes.data() + tail_len, "betaalphazeta", 13);
+    memcpy(hbytes.data() + tail_len + 13, tr.buf, 48);
+    uint32_t mids[16];
+    memcpy(mids, tg.h, 32);
+    memcpy(mids + 8, tr.h, 32);
+
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    Slot* s = g.s;
+    hipStream_t st = s->stream;
+    const size_t ch = std::min(n_proofs, CHUNK);
+    const size_t per = 548 + PV_NPTS * (32 + 64 + 1) + 3 + PV_NCOL * 32 + np * 32 + 2 * 64 + 10 * 128 + 2 * 128 + 3 * 128 + 8 * 32 + 2 * 64 + 2 * 384 + FE_SLOTS * 384;
+    ZK_TRY(s->reserve(ch * per + 64 * 1024 + 4 * 384 + FE_SLOTS * 384));
+    uint32_t* d_proofs = (uint32_t*)s->alloc(ch * 548);
+    uint32_t* d_praw = (uint32_t*)s->alloc(ch * PV_NPTS * 32);
+    Affine<Fp>* d_pts = (Affine<Fp>*)s->alloc(ch * PV_NPTS * 64);
+    uint8_t* d_bad = (uint8_t*)s->alloc(ch * PV_NPTS);
+    uint8_t* d_hdr = (uint8_t*)s->alloc(ch);
+    uint8_t* d_valid = (uint8_t*)s->alloc(ch);
+    uint8_t* d_verdict = (uint8_t*)s->alloc(ch);
+    Fr* d_sc = (Fr*)s->alloc(ch * PV_NCOL * 32);
+    Fr* d_pub = (Fr*)s->alloc(std::max(ch * np, (size_t)1) * 32);
+    Affine<Fp>* d_dig = (Affine<Fp>*)s->alloc(ch * 2 * 64);
+    XYZZ<Fp>* d_t = (XYZZ<Fp>*)s->alloc(ch * 10 * 128);
+    XYZZ<Fp>* d_A = (XYZZ<Fp>*)s->alloc(ch * 128);
+    XYZZ<Fp>* d_B = (XYZZ<Fp>*)s->alloc(ch * 128);
+    XYZZ<Fp>* d_fa = (XYZZ<Fp>*)s->alloc(ch * 128);
+    XYZZ<Fp>* d_fa2 = (XYZZ<Fp>*)s->alloc((ch + 1) / 2 * 128);
+    XYZZ<Fp>* d_fb = (XYZZ<Fp>*)s->alloc(ch * 128);
+    XYZZ<Fp>* d_fb2 = (XYZZ<Fp>*)s->alloc((ch + 1) / 2 * 128);
+    Fr* d_fix = (Fr*)s->alloc(ch * 3 * 32);
+    Fr* d_fold = (Fr*)s->alloc(ch * 3 * 32);
+    Fr* d_fold2 = (Fr*)s->alloc((ch + 1) / 2 * 3 * 32);
+    Affine<Fp>* d_p = (Affine<Fp>*)s->alloc(ch * 2 * 64);
+    F12* d_m = (F12*)s->alloc(ch * 2 * 384);
+    F12* d_ws = (F12*)s->alloc(ch * FE_SLOTS * 384);
+    F12* d_one_ws = (F12*)s->alloc(FE_SLOTS * 384);
+    Affine<Fp>* d_kpts = (Affine<Fp>*)s->alloc(9 * 64);
+    Affine<Fp2>* d_g2 = (Affine<Fp2>*)s->alloc(2 * 128);
+    uint32_t* d_mids = (uint32_t*)s->alloc(64);
+    uint8_t* d_hbytes = (uint8_t*)s->alloc(hbytes.size());
+    PvTerm* d_terms = (PvTerm*)s->alloc(21 * sizeof(PvTerm));
+    int* d_status = (int*)s->alloc(64);
+    uint8_t* d_chk = (uint8_t*)s->alloc(64);
+    if (!d_proofs || !d_praw || !d_pts || !d_bad || !d_hdr || !d_valid || !d_verdict || !d_sc || !d_pub || !d_dig || !d_t || !d_A || !d_B || !d_fa || !d_fa2 ||
+        !d_fb || !d_fb2 || !d_fix || !d_fold || !d_fold2 || !d_p || !d_m || !d_ws || !d_one_ws || !d_kpts || !d_g2 || !d_mids || !d_hbytes || !d_terms || !d_status ||
+        !d_chk)
+        return set_err(ZK_ERR_ARG, "plonk_verify_batch: workspace");
+    ZK_HIP(hipMemcpyAsync(d_kpts, kp, sizeof kp, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_g2, srs_g2, 2 * 128, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_mids, mids, sizeof mids, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_hbytes, hbytes.data(), hbytes.size(), hipMemcpyHostToDevice, st));
+
+    std::vector<PvTerm> terms(21);
+    size_t tn = 0;  // the table is rebuilt per chunk: its column pointers depend on the chunk's length
+    std::vector<uint8_t> valid(ch), one(1);
+    size_t total = 0;
+    for (size_t c0 = 0; c0 < n_proofs; c0 += ch) {
+        const size_t n = std::min(ch, n_proofs - c0);
+        if (n != tn) {
+            auto col = [&](int c) { return (const Fr*)(d_sc + (size_t)c * n); };
+            auto lane = [&](int k) { return (const Affine<Fp>*)(d_pts + (size_t)k * n); };
+            // digests: H1 zp, H2 zp^2 | Ql l, Qr r, Qm lr, Qo o, S3 c_s3, Z c_z
+            terms[0] = {lane(PV_H0 + 1), 1, col(PV_ZP)};
+            terms[1] = {lane(PV_H0 + 2), 1, col(PV_ZP2)};
+            terms[2] = {d_kpts + 3, 0, col(PV_CLAIM + 2)};
+            terms[3] = {d_kpts + 4, 0, col(PV_CLAIM + 3)};
+            terms[4] = {d_kpts + 5, 0, col(PV_LR)};
+            terms[5] = {d_kpts + 6, 0, col(PV_CLAIM + 4)};
+            terms[6] = {d_kpts + 2, 0, col(PV_CS3)};
+            terms[7] = {lane(PV_Z), 1, col(PV_CZ)};
+            // the combined opening check: fh lin L R O W Z W' | W W'
+            const Affine<Fp>* cp[10] = {d_dig, d_dig + n, lane(PV_L), lane(PV_L + 1), lane(PV_L + 2), lane(PV_W), lane(PV_Z), lane(PV_WS), lane(PV_W), lane(PV_WS)};
+            for (int k = 0; k < 10; k++) terms[8 + k] = {cp[k], 1, col(PV_T + k)};
+            // fallback: G, S1, S2
+            terms[18] = {d_kpts + 8, 0, d_fix};
+            terms[19] = {d_kpts + 0, 0, d_fix + n};
+            terms[20] = {d_kpts + 1, 0, d_fix + 2 * n};
+            ZK_HIP(hipMemcpyAsync(d_terms, terms.data(), terms.size() * sizeof(PvTerm), hipMemcpyHostToDevice, st));
+            tn = n;
+        }
+        ZK_HIP(hipMemcpyAsync(d_proofs, proofs + c0 * 548, n * 548, hipMemcpyHostToDevice, st));
+        if (np) ZK_HIP(hipMemcpyAsync(d_pub, public_inputs + c0 * np, n * np * 32, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemsetAsync(d_bad, 0, n * PV_NPTS, st));
+        ZK_HIP(hipMemsetAsync(d_status, 0, 4, st));
+        const dim3 g64(blocks(n, 64)), g256(blocks(n, 256));
+        ZK_LAUNCH(s, st, "pv_gather", k_pv_gather, g256, dim3(256), 0, (const uint32_t*)d_proofs, n, d_praw, d_sc, d_hdr);
+        ZK_TRY(g1_decompress_dev(s, st, d_praw, PV_NPTS * n, d_pts, d_status, d_bad));
+        ZK_LAUNCH(s, st, "pv_transcript", k_pv_transcript, g64, dim3(64), 0, (const Affine<Fp>*)d_pts, (const uint8_t*)d_bad, (const uint8_t*)d_hdr,
+                  (const Fr*)d_pub, n, np, (const uint32_t*)d_mids, (uint64_t)(tg.len - tail_len), (const uint8_t*)d_hbytes, tail_len, d_valid, d_sc);
+        ZK_LAUNCH(s, st, "pv_scalars", k_pv_scalars, g64, dim3(64), 0, (const Fr*)d_pub, n, np, K, d_valid, d_sc);
+        ZK_LAUNCH(s, st, "pv_smul", k_pv_smul, dim3(blocks(n, 64), 8), dim3(64), 0, (const PvTerm*)d_terms, n, (const uint8_t*)d_valid, d_t);
+        ZK_LAUNCH(s, st, "pv_digests", k_pv_digests, g64, dim3(64), 0, (const Affine<Fp>*)d_pts, (const XYZZ<Fp>*)d_t, (const Affine<Fp>*)d_kpts, n,
+                  (const uint8_t*)d_valid, d_dig);
+        ZK_LAUNCH(s, st, "pv_kzg", k_pv_kzg, g64, dim3(64), 0, (const Affine<Fp>*)d_pts, (const Affine<Fp>*)d_dig, (const Affine<Fp>*)d_kpts, n, c0, K,
+                  (const uint32_t*)(d_mids + 8), (const uint8_t*)(d_hbytes + tail_len + 13), (const uint8_t*)d_valid, d_sc, d_fix, d_fold);
+        ZK_LAUNCH(s, st, "pv_smul", k_pv_smul, dim3(blocks(n, 64), 10), dim3(64), 0, (const PvTerm*)(d_terms + 8), n, (const uint8_t*)d_valid, d_t);
+        ZK_LAUNCH(s, st, "pv_combine", k_pv_combine, g256, dim3(256), 0, (const XYZZ<Fp>*)d_t, n, d_A, d_B, d_fa, d_fb);
+        const XYZZ<Fp>* a_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, d_fa, d_fa2, n, 1);
+        const XYZZ<Fp>* b_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, d_fb, d_fb2, n, 1);
+        const Fr* c_sum = fold_all(s, st, "fr_fold", k_fr_fold, 256, d_fold, d_fold2, n, 3);
+        XYZZ<HFp> sa, sb;
+        HFr c[3];
+        ZK_HIP(hipMemcpyAsync(&sa, a_sum, 128, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipMemcpyAsync(&sb, b_sum, 128, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipMemcpyAsync(c, c_sum, 3 * 32, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipMemcpyAsync(valid.data(), d_valid, n, hipMemcpyDeviceToHost, st));
+        ZK_TRY(slot_sync(s, st));
+        size_t n_valid = 0;
+        for (size_t i = 0; i < n; i++) n_valid += valid[i];
+        if (n_valid == 0) {
+            memset(accepted + c0, 0, n);
+            continue;
+        }
+        // e(sum A_i + c_G G + c_S1 S1 + c_S2 S2, [1]2) e(-sum B_i, [alpha]2) == 1 (the fixed points scaled here: three host multiplications per chunk)
+        Affine<HFp> two[2];
+        {
+            const Affine<HFp> fp[3] = {G, v.pts[0], v.pts[1]};
+            for (int j = 0; j < 3; j++) {
+                uint32_t k[8];
+                to_canonical_u32(c[j], k);
+                sa.add(scalar_mul(fp[j], k));
+            }
+            two[0] = sa.to_affine();
+            two[1] = sb.to_affine().neg();
+        }
+        ZK_HIP(hipMemcpyAsync(d_p, two, 2 * 64, hipMemcpyHostToDevice, st));
+        ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(1), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_p, (size_t)2, (const Affine<Fp2>*)nullptr, (size_t)0,
+                  (const Affine<Fp2>*)d_g2, (size_t)1, PK, d_m);
+        const F12* prod = fold_all(s, st, "f12_fold", k_f12_fold, PAIR_BLOCK, d_m, d_ws, 2, 1);
+        ZK_HIP(hipMemsetAsync(d_chk, 1, 1, st));  // d_chk[0]: "valid", d_chk[1]: the verdict
+        ZK_TRY(final_exp(s, st, PK, prod, 1, 1, nullptr, d_one_ws, nullptr, d_chk, d_chk + 1));
+        ZK_HIP(hipMemcpyAsync(one.data(), d_chk + 1, 1, hipMemcpyDeviceToHost, st));
+        ZK_TRY(slot_sync(s, st));
+        if (one[0]) {
+            memcpy(accepted + c0, valid.data(), n);
+            total += n_valid;
+            continue;
+        }
+        // fallback: each valid proof's own two-pairing check, with its own rho_i, rho'_i
+        ZK_LAUNCH(s, st, "pv_smul", k_pv_smul, dim3(blocks(n, 64), 3), dim3(64), 0, (const PvTerm*)(d_terms + 18), n, (const uint8_t*)d_valid, d_t);
+        ZK_LAUNCH(s, st, "pv_single", k_pv_single, g256, dim3(256), 0, (const XYZZ<Fp>*)d_A, (const XYZZ<Fp>*)d_B, (const XYZZ<Fp>*)d_t, n,
+                  (const uint8_t*)d_valid, d_p);
+        ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(blocks(2 * n, PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_p, 2 * n,
+                  (const Affine<Fp2>*)nullptr, (size_t)0, (const Affine<Fp2>*)d_g2, n, PK, d_m);
+        ZK_TRY(final_exp(s, st, PK, d_m, n, 2, nullptr, d_ws, nullptr, d_valid, d_verdict));
         ZK_HIP(hipMemcpyAsync(accepted + c0, d_verdict, n, hipMemcpyDeviceToHost, st));
         ZK_TRY(slot_sync(s, st));
         for (size_t i = 0; i < n; i++) total += accepted[c0 + i] ? 1 : 0;

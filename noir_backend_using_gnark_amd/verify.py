@@ -94,3 +94,31 @@ def groth16_verify_batch(proofs, vk, public_inputs) -> np.ndarray:
         raise ValueError((lib().zk_last_error() or b"").decode())
     check(rc)
     return acc[:n].astype(bool)
+
+
+def plonk_verify_batch(proofs, vk, srs_g2, public_inputs) -> np.ndarray:
+    """plonk.Verify for many proofs against ONE verifying key, on the device: one verdict per proof, equal to plonk_verify's, except that a malformed
+    proof (an invalid point encoding, a batched-opening count other than 7) gives False instead of an error.  proofs: a sequence of 548-byte proofs (or
+    their concatenation); srs_g2: the SRS's two G2 points ((2, 16) uint64); public_inputs: (n_proofs, n_public, 4) Montgomery limbs."""
+    pb = _lib.PLONK_PROOF_BYTES
+    blob = bytes(proofs) if isinstance(proofs, (bytes, bytearray)) else b"".join(bytes(x) for x in proofs)
+    if len(blob) % pb:
+        raise ValueError("a PLONK proof is %d bytes (Proof.WriteTo)" % pb)
+    n = len(blob) // pb
+    k, is_hex = _blob(vk)
+    g2 = np.ascontiguousarray(srs_g2, dtype=np.uint64).reshape(2, 16)
+    pub = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+    if pub.size == 0:
+        n_public = pub.shape[1] if pub.ndim == 3 and pub.shape[0] == n else 0
+        pub = np.zeros((max(n, 1), max(n_public, 1), 4), np.uint64)
+    else:
+        pub = pub.reshape(n, -1, 4)
+        n_public = pub.shape[1]
+    acc = np.zeros(max(n, 1), np.uint8)
+    n_acc = C.c_size_t(0)
+    rc = lib().zk_bn254_plonk_verify_batch(C.c_char_p(blob), C.c_size_t(n), C.c_char_p(k), C.c_size_t(len(k)), C.c_int(is_hex), vp(g2),
+                                           vp(pub) if n_public else None, C.c_size_t(n_public), vp(acc), C.byref(n_acc))
+    if rc in (_lib.ZK_ERR_LEN, _lib.ZK_ERR_ARG):
+        raise ValueError((lib().zk_last_error() or b"").decode())
+    check(rc)
+    return acc[:n].astype(bool)
