@@ -221,3 +221,21 @@ def test_chunk_boundary(keys):
     got = zv.plonk_verify_batch(ps, key.vk, key.g2, ws)
     assert (got == host[idx]).all()
     assert (zv.plonk_verify_batch(ps, key.vk, key.g2, ws) == got).all()
+
+
+def test_non_canonical_public_inputs_match_the_host(keys):
+    """public inputs given as Montgomery images increased by r (limbs >= r, the same value): the device verdicts equal the host verifier's, proof by proof"""
+    key = keys[3]
+    proofs, pubs = key.proofs(16)
+    wide = pubs.copy()
+    for i in range(16):
+        for j in range(3):
+            v = int.from_bytes(np.asarray(pubs[i][j], dtype=np.uint64).tobytes(), "little") + R
+            assert v < 1 << 256
+            wide[i][j] = np.frombuffer(v.to_bytes(32, "little"), dtype=np.uint64)
+    wide[4] = pubs[4]                                                              # a canonical row in the same batch
+    wide[11][2] = mont_limbs([5])[0]                                               # a wrong value
+    want = _host(proofs, key.vk, key.g2, wide)
+    got = zv.plonk_verify_batch(proofs, key.vk, key.g2, wide)
+    assert (got == want).all(), [i for i in range(16) if got[i] != want[i]]
+    assert (got == zv.plonk_verify_batch(proofs, key.vk, key.g2, pubs) & (np.arange(16) != 11)).all()

@@ -168,3 +168,24 @@ def test_fresh_proofs_one_public_input_and_the_oracle():
         proof = (pl.g1_decompress(p[:32]), pl.g2_decompress(p[32:96]), pl.g1_decompress(p[96:]))
         w = [1] + [int.from_bytes(np.asarray(x, dtype=np.uint64).tobytes(), "little") * pow(1 << 256, -1, ref.R) % ref.R for x in pubs[i]]
         assert ref.groth16_verify(ovk, proof, w) == bool(got[i])
+
+
+def _plus_r(pubs):
+    """the same public inputs as NON-canonical Montgomery images: each limb vector increased by r (value unchanged mod r, limbs >= r)"""
+    out = pubs.copy()
+    for idx in np.ndindex(pubs.shape[:-1]):
+        v = int.from_bytes(np.asarray(pubs[idx], dtype=np.uint64).tobytes(), "little") + ref.R
+        assert v < 1 << 256
+        out[idx] = np.frombuffer(v.to_bytes(32, "little"), dtype=np.uint64)
+    return out
+
+
+def test_non_canonical_public_inputs_match_the_host_verifier():
+    vk, proofs, pubs = _fresh(12, 4, 0xACE)
+    wide = _plus_r(pubs)
+    assert (wide != pubs).any()
+    wide[7] = pubs[7]                                                            # a canonical one in the same batch
+    wide[9][1] = mont_limbs([3])[0]                                              # a wrong value
+    got = zv.groth16_verify_batch(proofs, vk, wide)
+    assert (got == _host_verdicts(proofs, vk, wide)).all()
+    assert (got == zv.groth16_verify_batch(proofs, vk, pubs) & (np.arange(12) != 9)).all()
