@@ -3,7 +3,9 @@
 
 N = 1 (default): BASELINE.json configs[1], "Synthetic R1CS 2^20 constraints, BN254 Groth16 prove on 1xMI355X (G1 MSM + Fr NTT)".
 One step = one proof from the solver output onwards (computeH = 7 NTTs, 4 G1 MSMs, 1 G2 MSM, host tail), inputs already resident
-in HBM.  The same JSON line also carries, measured in the same run:
+in HBM.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline.  With --full the same JSON line also carries,
+measured in the same run after the timed steps (DESIGN.md §6 lists every block):
+  * `roofline`              the dominant kernel, from a second pass of the same proofs with the library's event pairs on,
   * `prove_ms_host_inputs`  the proof through the entry point a cgo caller has (host slices: a, b, c, w cross PCIe inside the call),
   * `at_2p24`               the metric's other size (2^24 constraints on this one GPU: key with 84 GB of window tables), whose proof
                             bytes are checked against the recombination of two half-size slices run through the table-less path
@@ -13,8 +15,8 @@ configs[2] (2^24 constraints).  Every rank owns one block of a, b, c, w, h and o
 is block-sharded (the top log2 N butterfly stages of each transform run on all-to-all-transposed data: 10 RCCL all_to_all_single
 per proof), the five MSMs run on the rank's slice, and an all-gather of the 768-byte partial-sum record lets every rank finish.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric / value / unit follow BASELINE.json; `roofline` describes the
-dominant kernel (hipEvent pairs recorded inside libzkmi on the stream the kernels run on, live over the timed region);
+Prints ONE JSON line on rank 0: metric / value / unit follow BASELINE.json.  With --full, `roofline` describes the
+dominant kernel (hipEvent pairs recorded inside libzkmi on the stream the kernels run on, over a second pass of the timed proofs);
 `cpu_baseline` is the CPU oracle (a restatement of gnark's algorithm, NOT the gnark binary: no Go toolchain here) timed on this
 box's host cores on the SAME 2^20 proof -- whose bytes are compared with the GPU's (parity at full size).
 """
@@ -72,6 +74,9 @@ def main():
     ap.add_argument("--dry-launch", action="store_true", help="with --gpus N > 1 and no launcher around: print the torch.distributed.run command this script would start and exit")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the proof of the last one (what a caller of zk.prove receives) "
                     "as DIR/proof.npy (float64, one value per byte); the inputs are seeded, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything else into the same line: the roofline pass, "
+                    "host inputs, CPU baselines, the 2^24, PLONK and 2^26 blocks, the export paths (the --no-* options above pick among them); "
+                    "without it a run does only what the headline needs")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -162,24 +167,10 @@ def main():
     elapsed = time.perf_counter() - t0
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, proof)
-    # the roofline pass: the same number of the same proofs once more with a hipEvent pair around every launch, on the stream it is launched on
-    _lib.profile(True)
-    _lib.profile_reset()
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        proof_p = step()
-    barrier()
-    elapsed_profiled = time.perf_counter() - t1
-    _lib.profile(False)
-    prof = _lib.profile_read()
-    assert proof_p == proof, "the profiled pass proved other bytes"
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if par.dist().get_backend() == "nccl" else "cpu")
         par.dist().all_reduce(t, op=par.dist().ReduceOp.MAX)
         elapsed = float(t.item())
-        allp = par.all_gather_limbs(np.frombuffer(proof, dtype=np.uint64))
-        assert (allp == allp[0]).all(), "ranks disagree on the proof bytes"
 
     n_ranks_seen, rank_devices = 1, [local]
     if par.dist().is_available() and par.dist().is_initialized():
@@ -195,39 +186,6 @@ def main():
     g1_units = N_g + N_g + (N_g - N_PUBLIC) + (N_g - 1)
     ms_per_step = elapsed / args.steps * 1e3
     value = g1_units * args.steps / elapsed
-
-    # ---- roofline of the dominant kernel (by total time over the timed region)
-    # restricted to the hand-written hot kernels of the path; with the five MSMs of a proof running on concurrent
-    # streams an event pair also sees the time a kernel spends sharing the machine, exactly as rocprofv3 does
-    hot = {k: v for k, v in prof.items() if k in HAND_WRITTEN_HOT[:4]}
-    name, (launches, tot_ms) = max(hot.items(), key=lambda kv: kv[1][1])
-    per_launch_ms = tot_ms / launches
-    if name == "msm_accumulate_g1":
-        # the G1 MSMs of a proof come in launches / steps accumulate launches (A, B1, K share one: same sorted digits)
-        units_per_launch, bytes_per_unit = g1_units / world / (launches / float(args.steps)), 96.0
-    elif name == "msm_accumulate_g2":
-        units_per_launch, bytes_per_unit = N_loc, 160.0
-    else:  # an NTT pass: 64 B per element per pass
-        units_per_launch, bytes_per_unit = (N_loc if sharded else N_g), 64.0
-    achieved = units_per_launch * bytes_per_unit / (per_launch_ms * 1e-3) / 1e9
-    # HBM traffic per launch from the PMC counters (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, gfx950 correction:
-    # tools/pmc_traffic.py) -- taken at the SAME per-GPU size and table setting, else null
-    traffic = None
-    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(tpath) and not args.no_tables:
-        try:
-            traffic = json.load(open(tpath)).get(name, {}).get("by_log_n", {}).get(str(log_n), {}).get("hbm_bytes_per_launch")
-        except Exception:
-            traffic = None
-    # the honest ceiling of this kernel is the VALU, not HBM (bench_blocks/common.py valu_fraction)
-    valu = valu_fraction(L, _lib, name, units_per_launch, per_launch_ms, N_g if win else N_loc, bool(pk.info()["tables"]))
-    roofline = {"kernel": name, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                "avg_launch_ms": round(per_launch_ms, 4), "launches": launches, "measured_in": "a second pass of %d proofs with event pairs on (%.3f ms per proof; the timed region runs without them)"
-                % (args.steps, elapsed_profiled / args.steps * 1e3), "valu": valu, "dominant_by_time": dominant_by_time(prof, args.steps),
-                "note": "VALU-bound kernel (254-bit modular multiplies on 32-bit integer ALUs); see DESIGN.md for the ALU-issue fraction",
-                "kernel_ms_per_step": {k: round(v[1] / args.steps, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])}}
-    traffic_ratio(roofline, units_per_launch, bytes_per_unit)
 
     # the metric's name is BASELINE.json's, verbatim; the size this run used is in config.workload / config.constraints
     baseline_metric = "Groth16 prove ms + BN254 G1 MSM scalar-muls/sec at 2^20 / 2^24 constraints"
@@ -255,12 +213,72 @@ def main():
                    ("one proof window-sharded x%d: block-sharded computeH (all-to-all transposes), all-gather of h, MSMs over all wires on this rank's table rows "
                     "(all-gather of partial sums)" % world) if win else
                    "one proof range-sharded x%d: block-sharded computeH (all-to-all transposes) + MSMs on rank-local key slices (all-gather of partial sums)" % world},
-        "roofline": roofline, "proof_sha": hashlib.sha256(proof).hexdigest()[:16], "setup_s": round(t_setup, 2),
+        "roofline": None, "proof_sha": hashlib.sha256(proof).hexdigest()[:16], "setup_s": round(t_setup, 2),
     }
     if par.dist().is_available() and par.dist().is_initialized():
         out["config"]["collectives"] = par.dist().get_backend()  # "nccl" = RCCL carried the exchanges of this run
         out["n_ranks_seen"] = n_ranks_seen  # ranks that answered an all-reduce of ones over that backend, and the devices they ran on
         out["config"]["rank_devices"] = rank_devices
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            par.dist().barrier()
+            par.dist().destroy_process_group()
+
+    if not args.full:  # a plain run: the headline and nothing else
+        return finish()
+
+    # ---- everything below runs with --full only, after the timed region
+    # the roofline pass: the same number of the same proofs once more with a hipEvent pair around every launch, on the stream it is launched on
+    _lib.profile(True)
+    _lib.profile_reset()
+    barrier()
+    t1 = time.perf_counter()
+    for _ in range(args.steps):
+        proof_p = step()
+    barrier()
+    elapsed_profiled = time.perf_counter() - t1
+    _lib.profile(False)
+    prof = _lib.profile_read()
+    assert proof_p == proof, "the profiled pass proved other bytes"
+    if world > 1:
+        allp = par.all_gather_limbs(np.frombuffer(proof, dtype=np.uint64))
+        assert (allp == allp[0]).all(), "ranks disagree on the proof bytes"
+
+    # ---- roofline of the dominant kernel (by total time over the profiled pass)
+    # restricted to the hand-written hot kernels of the path; with the five MSMs of a proof running on concurrent
+    # streams an event pair also sees the time a kernel spends sharing the machine, exactly as a kernel trace does
+    hot = {k: v for k, v in prof.items() if k in HAND_WRITTEN_HOT[:4]}
+    name, (launches, tot_ms) = max(hot.items(), key=lambda kv: kv[1][1])
+    per_launch_ms = tot_ms / launches
+    if name == "msm_accumulate_g1":
+        # the G1 MSMs of a proof come in launches / steps accumulate launches (A, B1, K share one: same sorted digits)
+        units_per_launch, bytes_per_unit = g1_units / world / (launches / float(args.steps)), 96.0
+    elif name == "msm_accumulate_g2":
+        units_per_launch, bytes_per_unit = N_loc, 160.0
+    else:  # an NTT pass: 64 B per element per pass
+        units_per_launch, bytes_per_unit = (N_loc if sharded else N_g), 64.0
+    achieved = units_per_launch * bytes_per_unit / (per_launch_ms * 1e-3) / 1e9
+    # HBM traffic per launch from the PMC counters (FETCH_SIZE / WRITE_SIZE, separate passes, gfx950 correction: tools/pmc_traffic.py)
+    # -- taken at the SAME per-GPU size and table setting, else null
+    traffic = None
+    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(tpath) and not args.no_tables:
+        try:
+            traffic = json.load(open(tpath)).get(name, {}).get("by_log_n", {}).get(str(log_n), {}).get("hbm_bytes_per_launch")
+        except Exception:
+            traffic = None
+    # the honest ceiling of this kernel is the VALU, not HBM (bench_blocks/common.py valu_fraction)
+    valu = valu_fraction(L, _lib, name, units_per_launch, per_launch_ms, N_g if win else N_loc, bool(pk.info()["tables"]))
+    roofline = {"kernel": name, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                "avg_launch_ms": round(per_launch_ms, 4), "launches": launches, "measured_in": "a second pass of %d proofs with event pairs on (%.3f ms per proof; the timed region runs without them)"
+                % (args.steps, elapsed_profiled / args.steps * 1e3), "valu": valu, "dominant_by_time": dominant_by_time(prof, args.steps),
+                "note": "VALU-bound kernel (254-bit modular multiplies on 32-bit integer ALUs); see DESIGN.md for the ALU-issue fraction",
+                "kernel_ms_per_step": {k: round(v[1] / args.steps, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])}}
+    out["roofline"] = traffic_ratio(roofline, units_per_launch, bytes_per_unit)
 
     single = rank == 0 and not sharded
     # ---- the same proof through the entry point a cgo caller has: host slices in, 128 bytes out (PCIe-inclusive; never `value`)
@@ -410,11 +428,7 @@ def main():
         out["micro_2p%d_sharded" % args.micro_log_n] = blk
         if not (blk["msm_same_on_every_rank"] and blk["msm_equals_odd_split_recombination"] and blk["ntt_inverse_of_forward_is_identity"]):
             out["parity_error"] = "sharded micro-benchmark cross-check failed"
-    if rank == 0:
-        print(json.dumps(out))
-    if world > 1:
-        par.dist().barrier()
-        par.dist().destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -601,7 +601,7 @@ def test_two_process_sharded_proof_equals_single_process():
     with socket.socket() as so:
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
-    common = ["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--micro-log-n", "14"]
+    common = ["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--micro-log-n", "14", "--full"]
     single = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--log-n", "13"] + common, capture_output=True, text=True, timeout=600)
     assert single.returncode == 0, single.stdout[-2000:] + single.stderr[-2000:]
     sha1 = json.loads(single.stdout.strip().splitlines()[-1])["proof_sha"]
@@ -643,7 +643,7 @@ def test_rccl_executes_the_collectives_of_the_sharded_proof_world_of_one():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--log-n", "14", "--micro-log-n", "16"]
+    common = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--log-n", "14", "--micro-log-n", "16", "--full"]
     single = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common, capture_output=True, text=True, timeout=600)
     assert single.returncode == 0, single.stdout[-2000:] + single.stderr[-2000:]
     sha1 = json.loads(single.stdout.strip().splitlines()[-1])["proof_sha"]

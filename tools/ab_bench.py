@@ -29,7 +29,7 @@ def main():
             argv = argv[1:]
     out_path, cfgs = args[0], args[1:]
     only = only or ["2p20", "2p24", "plonk", "micro"]
-    flags = ["--steps", str(steps), "--warmup", "5", "--no-cpu-baseline", "--no-host-inputs", "--no-export"]
+    flags = ["--steps", str(steps), "--warmup", "5", "--full", "--no-cpu-baseline", "--no-host-inputs", "--no-export"]
     for k, f in (("2p24", "--no-2p24"), ("plonk", "--no-plonk"), ("micro", "--no-micro")):
         if k not in only:
             flags.append(f)
