@@ -413,6 +413,38 @@ void orc_g2_mul(const uint64_t a[16], const uint64_t k[4], int k_mont, uint64_t 
     g2_aff o; g2_to_aff(&o, &t); memcpy(out, &o, 128);
 }
 
+/* [k_i] G1 / [k_i] G2 for many scalars (the Setup reference of tests/groth16_setup_ref.py): 4-bit windows over a 64 x 15 table of the generator,
+ * T[w * 15 + d - 1] = d * 16^w * G (built per call: 960 points), one mixed addition per non-zero digit, then one inversion per point.  Scalars < r
+ * (canonical or Montgomery); a zero scalar gives the point at infinity, (0,0). */
+#define ORC_MUL_GEN_MANY(g, GEN, WIDTH)                                                                                                  \
+    void orc_##g##_mul_gen_many(const uint64_t *scalars, size_t n, int scalars_mont, int nthreads, uint64_t *out) {                      \
+        orc_init();                                                                                                                      \
+        const int nt = nthreads > 0 ? nthreads : effective_threads();                                                                    \
+        g##_aff *tab = (g##_aff *)malloc(sizeof(g##_aff) * 64 * 15);                                                                     \
+        g##_xyzz base, acc;                                                                                                              \
+        g##_from_aff(&base, &GEN);                                                                                                       \
+        for (int w = 0; w < 64; w++) {                                                                                                   \
+            g##_set_inf(&acc);                                                                                                           \
+            for (int d = 1; d < 16; d++) { g##_add(&acc, &base); g##_to_aff(&tab[w * 15 + d - 1], &acc); }                              \
+            for (int i = 0; i < 4; i++) g##_dbl(&base);                                                                                  \
+        }                                                                                                                                \
+        _Pragma("omp parallel for schedule(dynamic, 64) num_threads(nt)")                                                                \
+        for (size_t i = 0; i < n; i++) {                                                                                                 \
+            fe k; memcpy(&k, scalars + 4 * i, 32);                                                                                       \
+            if (scalars_mont) fld_from_mont(&FR, &k, &k);                                                                                \
+            g##_xyzz r; g##_set_inf(&r);                                                                                                 \
+            for (int w = 0; w < 64; w++) {                                                                                               \
+                const unsigned d = (unsigned)(k.l[w >> 4] >> (4 * (w & 15))) & 15u;                                                      \
+                if (d) g##_madd(&r, &tab[w * 15 + d - 1], 0);                                                                            \
+            }                                                                                                                            \
+            g##_aff o; g##_to_aff(&o, &r); memcpy(out + WIDTH * i, &o, sizeof o);                                                        \
+        }                                                                                                                                \
+        free(tab);                                                                                                                       \
+    }
+ORC_MUL_GEN_MANY(g1, G1_GEN, 8)
+ORC_MUL_GEN_MANY(g2, G2_GEN, 16)
+#undef ORC_MUL_GEN_MANY
+
 /* G1Affine.Bytes(): 32 B big-endian X, flags in the two top bits of byte 0:
  * mCompressedSmallest 0b10<<6, mCompressedLargest 0b11<<6, mCompressedInfinity 0b01<<6  [UPSTREAM-RECALL] */
 static void fe_to_be(uint8_t out[32], const fe *canon) {

@@ -54,6 +54,10 @@ void orc_g1_add(const uint64_t a[8], const uint64_t b[8], uint64_t out[8]);
 void orc_g2_add(const uint64_t a[16], const uint64_t b[16], uint64_t out[16]);
 void orc_g1_mul(const uint64_t a[8], const uint64_t k[4], int k_mont, uint64_t out[8]);
 void orc_g2_mul(const uint64_t a[16], const uint64_t k[4], int k_mont, uint64_t out[16]);
+/* out[i] = [k_i] G1 (n*8 limbs) / [k_i] G2 (n*16 limbs) for n scalars k_i < r (canonical, or Montgomery if scalars_mont); k_i = 0 gives (0,0).
+ * nthreads <= 0: the oracle's own thread count. */
+void orc_g1_mul_gen_many(const uint64_t *scalars, size_t n, int scalars_mont, int nthreads, uint64_t *out);
+void orc_g2_mul_gen_many(const uint64_t *scalars, size_t n, int scalars_mont, int nthreads, uint64_t *out);
 /* G1Affine.Bytes() / G2Affine.Bytes() compressed encodings */
 void orc_g1_compress(const uint64_t a[8], uint8_t out[32]);
 void orc_g2_compress(const uint64_t a[16], uint8_t out[64]);

@@ -183,6 +183,23 @@ def g2_mul(a, k, k_mont=True):
     out = np.zeros(16, dtype=np.uint64); lib().orc_g2_mul(_p(_u64(a)), _p(_u64(k)), C.c_int(int(k_mont)), _p(out)); return out
 
 
+def _mul_gen_many(fn, width, scalars, scalars_mont, nthreads):
+    scalars = _u64(scalars).reshape(-1, 4)
+    out = np.zeros((scalars.shape[0], width), dtype=np.uint64)
+    fn(_p(scalars), C.c_size_t(scalars.shape[0]), C.c_int(int(scalars_mont)), C.c_int(nthreads), _p(out))
+    return out
+
+
+def g1_mul_gen_many(scalars, scalars_mont=True, nthreads=0) -> np.ndarray:
+    """(n, 4) scalars < r -> (n, 8) affine [k_i] G1; zero -> (0,0).  nthreads = 0: the oracle's own count."""
+    return _mul_gen_many(lib().orc_g1_mul_gen_many, 8, scalars, scalars_mont, nthreads)
+
+
+def g2_mul_gen_many(scalars, scalars_mont=True, nthreads=0) -> np.ndarray:
+    """(n, 4) scalars < r -> (n, 16) affine [k_i] G2; zero -> (0,0)."""
+    return _mul_gen_many(lib().orc_g2_mul_gen_many, 16, scalars, scalars_mont, nthreads)
+
+
 def g1_compress(a) -> bytes:
     out = (C.c_uint8 * 32)(); lib().orc_g1_compress(_p(_u64(a)), out); return bytes(out)
 
