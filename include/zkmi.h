@@ -576,6 +576,45 @@ int zk_bn254_kzg_srs_write(uint64_t handle, const zk_g2_affine g2[2], int as_hex
  * device work: a process that only verifies never starts the HIP runtime.  Header and length are checked as in _read; the G1 points are not looked at. */
 int zk_bn254_kzg_srs_g2(const void *data, size_t len, int is_hex, zk_g2_affine g2_out[2]);
 
+/* ---- KZG openings: the rest of gnark-crypto v0.9.1's kzg package (ecc/bn254/fr/kzg/kzg.go: Open, BatchOpenSinglePoint, FoldProof, Verify,
+ * BatchVerifySinglePoint, BatchVerifyMultiPoints) [UPSTREAM-RECALL].  plonk.Prove's last round is BatchOpenSinglePoint of seven polynomials at zeta and Open of
+ * Z at omega zeta (gnark v0.8.0 backend/plonk/bn254/prove.go, reached from gnark_backend_ffi/backend/plonk/plonk.go:67); plonk.Verify ends in
+ * BatchVerifySinglePoint and Verify.  zk_kzg_opening is kzg.OpeningProof{H, ClaimedValue}; a kzg.BatchOpeningProof{H, ClaimedValues} travels as h + claimed[count].
+ * The hash of deriveGamma (the folding challenge: a one-challenge fiatshamir transcript "gamma" over the point, the digests' RawBytes and the claimed values) is
+ * SHA-256 ONLY -- what gnark's PLONK passes; upstream takes any hash.Hash.
+ * Proving side, on the DEVICE.  srs: a registered G1 base array (zk_bn254_bases_register*, zk_bn254_kzg_srs_read), on ONE device entry: a handle spread over
+ * several entries (device_mask) is refused with ZK_ERR_ARG.  polys[k]: lens[k] Montgomery coefficients, host pointers, or device pointers if on_device.
+ *   zk_bn254_kzg_open : `count` >= 1 independent openings, polynomial k at points[k]: out[k].claimed_value = p_k(z_k), out[k].h = Commit((p_k - p_k(z_k)) / (X - z_k)).
+ *                       count == 1 is kzg.Open.  All rows share one set of scan launches (polynomial, length and point are indexed per row) and up to three
+ *                       quotients one multi-scalar multiplication when the SRS has a window table; eight rows are in flight at a time.
+ *   zk_bn254_kzg_batch_open_single_point : kzg.BatchOpenSinglePoint -- out_claimed[k] = p_k(point); gamma = deriveGamma(point, digests, out_claimed);
+ *                       *out_h = Commit((sum_k gamma^k p_k - sum_k gamma^k p_k(point)) / (X - point)).  Any count; lengths may differ.
+ *   Errors: count == 0 or a null array ZK_ERR_ARG; an unknown handle ZK_ERR_HANDLE; a length of 0 or above the SRS's size ZK_ERR_LEN ("kzg: invalid polynomial
+ *   size (larger than SRS or == 0)", ErrInvalidPolynomialSize).  A constant polynomial (length 1) has an empty quotient: h = infinity, no error -- what upstream
+ *   does with it is unpinned.  Without a GPU: ZK_ERR_NO_DEVICE after the checks that need no handle; there is no CPU fallback.
+ * Verifying side.  Points are affine Montgomery images and are not validated (as zk_bn254_pairing_check); srs_g2 = ([1]2, [alpha]2).
+ *   zk_bn254_kzg_verify (HOST, never starts the HIP runtime) : kzg.Verify -- e(C - v G + z H, [1]2) e(-H, [alpha]2) == 1; *accepted = 1 / 0.
+ *   zk_bn254_kzg_fold_proof (HOST) : kzg.FoldProof -- out_opening = {h, sum_k gamma^k claimed[k]}, out_digest = sum_k gamma^k digests[k].
+ *   zk_bn254_kzg_batch_verify_single_point (HOST) : kzg.BatchVerifySinglePoint = fold, then verify.
+ *   zk_bn254_kzg_verify_batch (DEVICE) : kzg.BatchVerifyMultiPoints with a verdict per opening: accepted[i] equals what zk_bn254_kzg_verify says of (digests[i],
+ *                       openings[i], points[i]).  The openings are first checked together, e(sum_i lambda_i (C_i - v_i G + z_i H_i), [1]2)
+ *                       e(-sum_i lambda_i H_i, [alpha]2) == 1 -- two Miller loops whatever n is -- with lambda_i = the low 128 bits of SHA-256("zkmi-kzg-batch" ||
+ *                       SHA-256(srs_g2) || SHA-256(digests || openings || points) || u64 i little-endian), forced non-zero: derived, not random (upstream draws
+ *                       them), so results are reproducible; a batch with a wrong opening passes with probability about 2^-128 in the random-oracle model.  If
+ *                       that check fails, every opening gets its own two-pairing check on the device.  Chunks of at most 2^16 openings; about 4.3 KB of
+ *                       device workspace per opening of a chunk; one stream slot per call.  ZK_ERR_NO_DEVICE without a GPU, after the null-pointer checks. */
+typedef struct { zk_g1_affine h; zk_fr claimed_value; } zk_kzg_opening;
+int zk_bn254_kzg_open(uint64_t srs, const void *const *polys, const size_t *lens, const zk_fr *points, size_t count, int on_device, zk_kzg_opening *out);
+int zk_bn254_kzg_batch_open_single_point(uint64_t srs, const void *const *polys, const size_t *lens, const zk_g1_affine *digests, size_t count,
+                                         const zk_fr *point, int on_device, zk_g1_affine *out_h, zk_fr *out_claimed);
+int zk_bn254_kzg_verify(const zk_g1_affine *digest, const zk_kzg_opening *opening, const zk_fr *point, const zk_g2_affine srs_g2[2], int *accepted);
+int zk_bn254_kzg_fold_proof(const zk_g1_affine *digests, size_t count, const zk_g1_affine *h, const zk_fr *claimed, const zk_fr *point,
+                            zk_kzg_opening *out_opening, zk_g1_affine *out_digest);
+int zk_bn254_kzg_batch_verify_single_point(const zk_g1_affine *digests, size_t count, const zk_g1_affine *h, const zk_fr *claimed, const zk_fr *point,
+                                           const zk_g2_affine srs_g2[2], int *accepted);
+int zk_bn254_kzg_verify_batch(const zk_g1_affine *digests, const zk_kzg_opening *openings, const zk_fr *points, size_t n_openings,
+                              const zk_g2_affine srs_g2[2], uint8_t *accepted, size_t *n_accepted);
+
 /* ---- device memory plumbing for hosts without a HIP binding (ctypes tests, the cgo shim) ------------------------ */
 int zk_dev_alloc(void **d_ptr, size_t bytes);
 int zk_dev_free(void *d_ptr);

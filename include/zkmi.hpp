@@ -167,7 +167,8 @@ inline Error Prove(const ProvingKey& pk, const fr::Vector& a, const fr::Vector& 
 
 namespace kzg {
 
-// kzg.SRS with the G1 side resident in HBM (RAII over the registered base array).  kzg.NewSRS / (*SRS).ReadFrom / WriteTo / kzg.Commit.
+// kzg.SRS with the G1 side resident in HBM (RAII over the registered base array).  kzg.NewSRS / (*SRS).ReadFrom / WriteTo / kzg.Commit; the openings
+// (Open, BatchOpenSinglePoint, FoldProof, Verify, BatchVerifySinglePoint, BatchVerifyMultiPoints) follow the class.
 class SRS {
 public:
     SRS() = default;
@@ -223,6 +224,69 @@ private:
     uint64_t handle_ = 0;
     uint64_t size_ = 0;
 };
+
+// kzg.OpeningProof{H, ClaimedValue} and kzg.BatchOpeningProof{H, ClaimedValues}
+typedef zk_kzg_opening OpeningProof;
+struct BatchOpeningProof {
+    zk_g1_affine H = {};
+    fr::Vector ClaimedValues;
+};
+typedef zk_g1_affine Digest;
+
+// kzg.Open(p, point, srs): ClaimedValue = p(point), H = Commit((p - p(point)) / (X - point)), on the device
+inline Error Open(const fr::Vector& p, const fr::Element& point, const SRS& srs, OpeningProof* proof) {
+    if (p.empty() || p.size() > srs.Size()) return Error{ZK_ERR_LEN, "kzg: invalid polynomial size (larger than SRS or == 0)"};
+    const void* polys[1] = {p.data()};
+    const size_t lens[1] = {p.size()};
+    return make_error(zk_bn254_kzg_open(srs.handle(), polys, lens, &point, 1, 0, proof));
+}
+// kzg.BatchOpenSinglePoint(polynomials, digests, point, hf, srs) with hf = SHA-256
+inline Error BatchOpenSinglePoint(const std::vector<fr::Vector>& polynomials, const std::vector<Digest>& digests, const fr::Element& point, const SRS& srs,
+                                  BatchOpeningProof* proof) {
+    if (polynomials.size() != digests.size()) return Error{ZK_ERR_ARG, "kzg: number of digests differs from the number of polynomials"};
+    std::vector<const void*> polys;
+    std::vector<size_t> lens;
+    for (const fr::Vector& p : polynomials) {
+        if (p.empty() || p.size() > srs.Size()) return Error{ZK_ERR_LEN, "kzg: invalid polynomial size (larger than SRS or == 0)"};
+        polys.push_back(p.data());
+        lens.push_back(p.size());
+    }
+    proof->ClaimedValues.resize(polynomials.size());
+    return make_error(zk_bn254_kzg_batch_open_single_point(srs.handle(), polys.data(), lens.data(), digests.data(), polys.size(), &point, 0, &proof->H,
+                                                           proof->ClaimedValues.data()));
+}
+// kzg.FoldProof(digests, batchOpeningProof, point, hf): the folded opening and the folded digest (host)
+inline Error FoldProof(const std::vector<Digest>& digests, const BatchOpeningProof& batch, const fr::Element& point, OpeningProof* proof, Digest* digest) {
+    if (digests.size() != batch.ClaimedValues.size()) return Error{ZK_ERR_ARG, "kzg: number of digests differs from the number of claimed values"};
+    return make_error(zk_bn254_kzg_fold_proof(digests.data(), digests.size(), &batch.H, batch.ClaimedValues.data(), &point, proof, digest));
+}
+// kzg.Verify(commitment, proof, point, srs): nil when the opening holds, "can't verify opening proof" (upstream's ErrVerifyOpeningProof) otherwise (host)
+inline Error Verify(const Digest& commitment, const OpeningProof& proof, const fr::Element& point, const SRS& srs) {
+    int ok = 0;
+    Error e = make_error(zk_bn254_kzg_verify(&commitment, &proof, &point, srs.G2, &ok));
+    if (e.ok() && !ok) return Error{ZK_ERR_ARG, "can't verify opening proof"};
+    return e;
+}
+// kzg.BatchVerifySinglePoint(digests, batchOpeningProof, point, hf, srs) (host)
+inline Error BatchVerifySinglePoint(const std::vector<Digest>& digests, const BatchOpeningProof& batch, const fr::Element& point, const SRS& srs) {
+    if (digests.size() != batch.ClaimedValues.size()) return Error{ZK_ERR_ARG, "kzg: number of digests differs from the number of claimed values"};
+    int ok = 0;
+    Error e = make_error(zk_bn254_kzg_batch_verify_single_point(digests.data(), digests.size(), &batch.H, batch.ClaimedValues.data(), &point, srs.G2, &ok));
+    if (e.ok() && !ok) return Error{ZK_ERR_ARG, "can't verify opening proof"};
+    return e;
+}
+// kzg.BatchVerifyMultiPoints(digests, proofs, points, srs) on the device.  Upstream answers for the whole batch; `accepted` (optional) receives a verdict per opening.
+inline Error BatchVerifyMultiPoints(const std::vector<Digest>& digests, const std::vector<OpeningProof>& proofs, const fr::Vector& points, const SRS& srs,
+                                    std::vector<uint8_t>* accepted = nullptr) {
+    if (digests.size() != proofs.size() || digests.size() != points.size()) return Error{ZK_ERR_ARG, "kzg: number of digests, proofs and points differ"};
+    if (digests.empty()) return Error{ZK_ERR_ARG, "kzg: no opening to verify"};
+    std::vector<uint8_t> acc(digests.size());
+    size_t n_ok = 0;
+    Error e = make_error(zk_bn254_kzg_verify_batch(digests.data(), proofs.data(), points.data(), digests.size(), srs.G2, acc.data(), &n_ok));
+    if (accepted) *accepted = acc;
+    if (e.ok() && n_ok != digests.size()) return Error{ZK_ERR_ARG, "can't verify opening proof"};
+    return e;
+}
 
 }  // namespace kzg
 

@@ -32,23 +32,11 @@
 #include "multidev.hpp"
 #include "ntt.hpp"
 #include "proofio.hpp"
+#include "scan.hpp"
 #include "text_host.hpp"
 
 namespace zkmi {
 
-static Fr to_dev(const HFr& h) {
-    Fr r;
-    memcpy(&r, &h, 32);
-    return r;
-}
-__device__ __forceinline__ Fr ld(const Fr* p) {
-    const uint4* q = reinterpret_cast<const uint4*>(p);
-    uint4 a = q[0], b = q[1];
-    Fr r;
-    r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
-    r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
-    return r;
-}
 __device__ __forceinline__ unsigned brev(unsigned i, unsigned logn) { return logn ? (__brev(i) >> (32 - logn)) : 0; }
 
 // ------------------------------------------------------------------------------------------------ small kernels
@@ -239,7 +227,6 @@ __global__ __launch_bounds__(256) void k_hscan_local(const Fr* __restrict__ f, s
 }
 // Several polynomials at the SAME point in one launch (plonk.Prove evaluates l, r, o, s1, s2 and then foldedH, linPol at zeta: seven evaluations that are two
 // launches each -- a lane-Horner pass and a single-workgroup block scan that is pure latency): blockIdx.y selects the polynomial.
-constexpr int HSCAN_BATCH_MAX = 8;
 struct HscanBatch {
     const Fr* f[HSCAN_BATCH_MAX];
     size_t len[HSCAN_BATCH_MAX];
@@ -268,6 +255,7 @@ __global__ __launch_bounds__(256) void k_hscan_local_batch(HscanBatch Bt, uint32
     }
     if (threadIdx.x == 0) btot[(size_t)blockIdx.y * nb + blockIdx.x] = val;
 }
+// (kzg.hip's k_hscan_*_rows are these three passes with polynomial, length and point per row: an edit of one belongs in the other)
 // pass 2: one block; btot[b] <- C_b = sum_{b' > b} btot[b'] * M^(b'-b-1) (M = A^256); *total = S_0 = f(a).
 __global__ __launch_bounds__(1024) void k_hscan_blocks(Fr* __restrict__ btot, uint32_t nb, Fr M, Fr* __restrict__ total) {
     __shared__ Fr sh[1024];
@@ -685,13 +673,8 @@ static int to_big_coset(Slot* s, hipStream_t st, Fr* dst, const Fr* p, size_t le
     return ntt_dev(s, st, dst, P->logN4, 0, ZK_DIF, 1);
 }
 
-// scratch carved from the slot arena for the scans over `len` elements
-struct ScanBufs {
-    uint32_t K = 0, nb = 0;
-    Fr *t = nullptr, *b = nullptr, *total = nullptr;
-};
-static size_t scan_need(size_t len) { return (len / 8 + 4096) * sizeof(Fr) + 8192 + (size_t)8 * (len / 2048 + 2) * sizeof(Fr); }
-static int scan_bufs(Slot* s, size_t len, ScanBufs* B) {
+// scratch carved from the slot arena for the scans over `len` elements (scan.hpp)
+int scan_bufs(Slot* s, size_t len, ScanBufs* B) {
     uint32_t K = (uint32_t)((len + 256 * 1024 - 1) / (256 * 1024));
     if (K < 8) K = 8;
     size_t T = (len + K - 1) / K;
@@ -704,7 +687,7 @@ static int scan_bufs(Slot* s, size_t len, ScanBufs* B) {
     return ZK_OK;
 }
 // f_k(a) -> d_out[k] for cnt <= HSCAN_BATCH_MAX polynomials, two launches in all
-static int poly_eval_batch_dev(Slot* s, hipStream_t st, const Fr* const* f, const size_t* len, int cnt, const HFr& a, const ScanBufs& B, Fr* d_out) {
+int poly_eval_batch_dev(Slot* s, hipStream_t st, const Fr* const* f, const size_t* len, int cnt, const HFr& a, const ScanBufs& B, Fr* d_out) {
     if (cnt < 1 || cnt > HSCAN_BATCH_MAX) return set_err(ZK_ERR_ARG, "evaluation batch of %d", cnt);
     HFr A = HFr::one(), M;
     {
@@ -720,7 +703,7 @@ static int poly_eval_batch_dev(Slot* s, hipStream_t st, const Fr* const* f, cons
     return ZK_OK;
 }
 // q = (f - f(a)) / (X - a) (len - 1 coefficients; q may alias f; q[len-1] is set to 0), f(a) -> *d_eval
-static int poly_divide_dev(Slot* s, hipStream_t st, const Fr* f, size_t len, const HFr& a, const ScanBufs& B, Fr* q, Fr* d_eval) {
+int poly_divide_dev(Slot* s, hipStream_t st, const Fr* f, size_t len, const HFr& a, const ScanBufs& B, Fr* q, Fr* d_eval) {
     HFr A = HFr::one(), M;
     {
         HFr base = a;

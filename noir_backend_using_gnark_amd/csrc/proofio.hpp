@@ -169,4 +169,14 @@ struct FsTranscript {
     }
 };
 
+// kzg.deriveGamma (gnark-crypto v0.9.1, hash = SHA-256): the folding challenge of BatchOpenSinglePoint / FoldProof -- a one-challenge transcript "gamma" over the
+// point, the digests' RawBytes and the claimed values.  Prover (kzg.hip) and verifier (verify.hip) both call this.
+static inline HFr kzg_derive_gamma(const HFr& point, const Affine<HFp>* digests, const HFr* claimed, size_t count) {
+    FsTranscript kt{"gamma"};
+    kt.bind_fr(0, point);
+    for (size_t k = 0; k < count; k++) kt.bind_g1(0, digests[k]);
+    for (size_t k = 0; k < count; k++) kt.bind_fr(0, claimed[k]);
+    return kt.challenge(0);
+}
+
 }  // namespace zkmi

@@ -96,6 +96,26 @@ bool kzg_check(const G1& digest, const G1& h, const HFr& value, const HFr& point
     lhs.add(g1_mul(h, point));
     return pairing::product_is_one({{lhs.to_affine(), g2[0]}, {h.neg(), g2[1]}});
 }
+// kzg.FoldProof: gamma = deriveGamma(point, digests, claimed values) over SHA-256 (a one-challenge transcript); sum_k gamma^k C_k and sum_k gamma^k v_k
+void kzg_fold(const G1* digests, const HFr* claimed, size_t count, const HFr& point, G1* folded_digest, HFr* folded_value) {
+    const HFr kg = kzg_derive_gamma(point, digests, claimed, count);
+    XYZZ<HFp> fd = XYZZ<HFp>::inf();
+    HFr fe = HFr::zero(), acc = HFr::one();
+    for (size_t k = 0; k < count; k++) {
+        fd.add(g1_mul(digests[k], acc));
+        fe = fe + claimed[k] * acc;
+        acc = acc * kg;
+    }
+    *folded_digest = fd.to_affine();
+    *folded_value = fe;
+}
+template <class T, class S>
+T img(const S& s) {
+    static_assert(sizeof(T) == sizeof(S), "same memory image");
+    T t;
+    memcpy(&t, &s, sizeof t);
+    return t;
+}
 
 }  // namespace
 
@@ -237,23 +257,49 @@ int zk_bn254_plonk_verify(const uint8_t proof[548], const void* vk, size_t vk_le
     lin.add(g1_mul(vkp[2], c_s3));                // S3
     lin.add(g1_mul(z, c_z));
     const G1 digests[7] = {fh.to_affine(), lin.to_affine(), lro[0], lro[1], lro[2], vkp[0], vkp[1]};
-    // kzg.deriveGamma: one-challenge transcript over the point, the digests and the claimed values
-    FsTranscript kt{"gamma"};
-    kt.bind_fr(0, zeta);
-    for (const G1& d : digests) kt.bind_g1(0, d);
-    for (const HFr& v : claimed) kt.bind_fr(0, v);
-    const HFr kg = kt.challenge(0);
-    XYZZ<HFp> fd = XYZZ<HFp>::inf();
-    HFr fe = HFr::zero(), acc = one;
-    for (int k = 0; k < 7; k++) {
-        fd.add(g1_mul(digests[k], acc));
-        fe = fe + claimed[k] * acc;
-        acc = acc * kg;
-    }
-    if (!kzg_check(fd.to_affine(), batch_h, fe, zeta, g2)) return ZK_OK;
+    // kzg.BatchVerifySinglePoint of the batched opening (fold, then verify), kzg.Verify of Z's
+    G1 fd;
+    HFr fe;
+    kzg_fold(digests, claimed, 7, zeta, &fd, &fe);
+    if (!kzg_check(fd, batch_h, fe, zeta, g2)) return ZK_OK;
     if (!kzg_check(z, z_open_h, zu, zeta * gen, g2)) return ZK_OK;
     *accepted = 1;
     return ZK_OK;
+}
+
+// ---- KZG opening checks (gnark-crypto v0.9.1 ecc/bn254/fr/kzg: Verify, FoldProof, BatchVerifySinglePoint; deriveGamma over SHA-256).  Host only, like the
+// verifiers above; points are affine Montgomery images and are not validated.
+int zk_bn254_kzg_verify(const zk_g1_affine* digest, const zk_kzg_opening* opening, const zk_fr* point, const zk_g2_affine srs_g2[2], int* accepted) {
+    if (!digest || !opening || !point || !srs_g2 || !accepted) return set_err(ZK_ERR_ARG, "null pointer");
+    G2 g2[2];
+    memcpy(g2, srs_g2, sizeof g2);
+    *accepted = kzg_check(img<G1>(*digest), img<G1>(opening->h), img<HFr>(opening->claimed_value), img<HFr>(*point), g2) ? 1 : 0;
+    return ZK_OK;
+}
+int zk_bn254_kzg_fold_proof(const zk_g1_affine* digests, size_t count, const zk_g1_affine* h, const zk_fr* claimed, const zk_fr* point, zk_kzg_opening* out_opening,
+                            zk_g1_affine* out_digest) {
+    if (!digests || !h || !claimed || !point || !out_opening || !out_digest) return set_err(ZK_ERR_ARG, "null pointer");
+    if (count == 0) return set_err(ZK_ERR_ARG, "kzg: no digest to fold");
+    std::vector<G1> d(count);
+    std::vector<HFr> v(count);
+    memcpy(d.data(), digests, count * 64);
+    memcpy(v.data(), claimed, count * 32);
+    G1 fd;
+    HFr fe;
+    kzg_fold(d.data(), v.data(), count, img<HFr>(*point), &fd, &fe);
+    out_opening->h = *h;
+    out_opening->claimed_value = img<zk_fr>(fe);
+    *out_digest = img<zk_g1_affine>(fd);
+    return ZK_OK;
+}
+int zk_bn254_kzg_batch_verify_single_point(const zk_g1_affine* digests, size_t count, const zk_g1_affine* h, const zk_fr* claimed, const zk_fr* point,
+                                           const zk_g2_affine srs_g2[2], int* accepted) {
+    if (!srs_g2 || !accepted) return set_err(ZK_ERR_ARG, "null pointer");
+    *accepted = 0;
+    zk_kzg_opening o;
+    zk_g1_affine d;
+    ZK_TRY(zk_bn254_kzg_fold_proof(digests, count, h, claimed, point, &o, &d));
+    return zk_bn254_kzg_verify(&d, &o, point, srs_g2, accepted);
 }
 
 // e(P1, Q1) e(P2, Q2) ... == 1 for n pairs of affine Montgomery points (a building block for callers and tests: bilinearity is how the host pairing is

@@ -16,6 +16,8 @@
 //     check       k_pv_smul + k_pv_combine: A_i = rho_i (D_i - e_i G + zeta_i W_i) + rho'_i (Z_i - zu_i G + zeta_i omega W'_i) without the fixed points,
 //                 B_i = rho_i W_i + rho'_i W'_i; k_g1_fold / k_fr_fold sum them; the host adds the G, S1, S2 terms; e(sum A, [1]2) e(-sum B, [alpha]2) == 1
 //     fallback    (only when the check fails) each proof's own A_i, -B_i (k_pv_single), 2 n Miller loops, a final exponentiation and a verdict per proof
+//   zk_bn254_kzg_verify_batch, per chunk of at most 2^16 openings (one lane per opening): k_kzg_combine, the same folds, two Miller loops and one
+//                 final exponentiation; the fallback runs each lane's own pair through k_miller and the per-lane final exponentiation
 #include <string.h>
 
 #include <algorithm>
@@ -472,6 +474,30 @@ __global__ __launch_bounds__(256) void k_pv_single(const XYZZ<Fp>* __restrict__ 
     P[n + i] = B[i].to_affine().neg();
 }
 
+// batch KZG opening check, per lane: T = C - v G + z H;  fa = lambda T and fb = lambda H for the folds;
+// the lane's own pair for the fallback: P[i] = T, P[n + i] = -H (affine)
+struct KzgLane {
+    zk_g1_affine h;
+    zk_fr v;
+};
+__global__ __launch_bounds__(64) void k_kzg_combine(const Affine<Fp>* __restrict__ dig, const KzgLane* __restrict__ op, const Fr* __restrict__ z,
+                                                    const uint32_t* __restrict__ rr, size_t n, Affine<Fp> G,
+                                                    XYZZ<Fp>* __restrict__ fa, XYZZ<Fp>* __restrict__ fb, Affine<Fp>* __restrict__ P) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Affine<Fp> h = reinterpret_cast<const Affine<Fp>*>(&op[i].h)[0];
+    const Fr v = reinterpret_cast<const Fr*>(&op[i].v)[0].from_mont(), zi = z[i].from_mont();
+    XYZZ<Fp> t = XYZZ<Fp>::from_affine(dig[i]);
+    t.add(scalar_mul(G, v.l).neg());
+    t.add(scalar_mul(h, zi.l));
+    const Affine<Fp> ta = t.to_affine();
+    P[i] = ta;
+    P[n + i] = h.neg();
+    const uint32_t k[8] = {rr[4 * i], rr[4 * i + 1], rr[4 * i + 2], rr[4 * i + 3], 0, 0, 0, 0};
+    fa[i] = scalar_mul(ta, k);
+    fb[i] = scalar_mul(h, k);
+}
+
 // halving launches until one element is left; a and b hold at least ceil(n / 2) elements each (a: n); returns where the result is
 template <class T, class Kern>
 T* fold_all(Slot* s, hipStream_t st, const char* name, Kern kernel, unsigned block, T* a, T* b, size_t n, size_t cols) {
@@ -889,6 +915,109 @@ int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const vo
         ZK_LAUNCH(s, st, "pv_smul", k_pv_smul, dim3(blocks(n, 64), 3), dim3(64), 0, (const PvTerm*)(d_terms + 18), n, (const uint8_t*)d_valid, d_t);
         ZK_LAUNCH(s, st, "pv_single", k_pv_single, g256, dim3(256), 0, (const XYZZ<Fp>*)d_A, (const XYZZ<Fp>*)d_B, (const XYZZ<Fp>*)d_t, n,
                   (const uint8_t*)d_valid, d_p);
+        ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(blocks(2 * n, PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_p, 2 * n,
+                  (const Affine<Fp2>*)nullptr, (size_t)0, (const Affine<Fp2>*)d_g2, n, PK, d_m);
+        ZK_TRY(final_exp(s, st, PK, d_m, n, 2, nullptr, d_ws, nullptr, d_valid, d_verdict));
+        ZK_HIP(hipMemcpyAsync(accepted + c0, d_verdict, n, hipMemcpyDeviceToHost, st));
+        ZK_TRY(slot_sync(s, st));
+        for (size_t i = 0; i < n; i++) total += accepted[c0 + i] ? 1 : 0;
+    }
+    *n_accepted = total;
+    return ZK_OK;
+}
+
+// kzg.BatchVerifyMultiPoints with a verdict per opening (include/zkmi.h)
+int zk_bn254_kzg_verify_batch(const zk_g1_affine* digests, const zk_kzg_opening* openings, const zk_fr* points, size_t n_openings, const zk_g2_affine srs_g2[2],
+                              uint8_t* accepted, size_t* n_accepted) {
+    static_assert(sizeof(zk_kzg_opening) == 96 && sizeof(KzgLane) == 96, "opening image");
+    if (!srs_g2 || !n_accepted || (n_openings && (!digests || !openings || !points || !accepted))) return set_err(ZK_ERR_ARG, "null pointer");
+    *n_accepted = 0;
+    if (n_openings == 0) return ZK_OK;
+    ZK_TRY(ensure_init());
+    const PairConsts PK = pair_consts();
+    const Affine<Fp> G = bit_cast_img<Affine<Fp>>(Affine<HFp>{HFp::one(), HFp::one() + HFp::one()});
+    // lambda_i = the low 128 bits of SHA-256("zkmi-kzg-batch" || SHA-256(srs_g2) || SHA-256(digests || openings || points) || u64 i), forced non-zero
+    uint8_t pre[14 + 32 + 32 + 8];
+    memcpy(pre, "zkmi-kzg-batch", 14);
+    sha(srs_g2, 2 * sizeof(zk_g2_affine), pre + 14);
+    {
+        Sha256 h;
+        h.update(digests, n_openings * 64);
+        h.update(openings, n_openings * 96);
+        h.update(points, n_openings * 32);
+        h.final(pre + 46);
+    }
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    Slot* s = g.s;
+    hipStream_t st = s->stream;
+    const size_t ch = std::min(n_openings, CHUNK);
+    const size_t per = 64 + 96 + 32 + 16 + 2 + 4 * 128 + 2 * 64 + 2 * 384 + FE_SLOTS * 384;
+    ZK_TRY(s->reserve(ch * per + 64 * 1024 + 4 * 384 + FE_SLOTS * 384));
+    Affine<Fp>* d_dig = (Affine<Fp>*)s->alloc(ch * 64);
+    KzgLane* d_op = (KzgLane*)s->alloc(ch * 96);
+    Fr* d_z = (Fr*)s->alloc(ch * 32);
+    uint32_t* d_rr = (uint32_t*)s->alloc(ch * 16);
+    uint8_t* d_valid = (uint8_t*)s->alloc(ch);
+    uint8_t* d_verdict = (uint8_t*)s->alloc(ch);
+    XYZZ<Fp>* d_fa = (XYZZ<Fp>*)s->alloc(ch * 128);
+    XYZZ<Fp>* d_fa2 = (XYZZ<Fp>*)s->alloc((ch + 1) / 2 * 128);
+    XYZZ<Fp>* d_fb = (XYZZ<Fp>*)s->alloc(ch * 128);
+    XYZZ<Fp>* d_fb2 = (XYZZ<Fp>*)s->alloc((ch + 1) / 2 * 128);
+    Affine<Fp>* d_p = (Affine<Fp>*)s->alloc(ch * 2 * 64);
+    Affine<Fp>* d_two = (Affine<Fp>*)s->alloc(2 * 64);
+    F12* d_m = (F12*)s->alloc(ch * 2 * 384);
+    F12* d_ws = (F12*)s->alloc(ch * FE_SLOTS * 384);
+    F12* d_one_ws = (F12*)s->alloc(FE_SLOTS * 384);
+    Affine<Fp2>* d_g2 = (Affine<Fp2>*)s->alloc(2 * 128);
+    uint8_t* d_chk = (uint8_t*)s->alloc(64);
+    if (!d_dig || !d_op || !d_z || !d_rr || !d_valid || !d_verdict || !d_fa || !d_fa2 || !d_fb || !d_fb2 || !d_p || !d_two || !d_m || !d_ws ||
+        !d_one_ws || !d_g2 || !d_chk)
+        return set_err(ZK_ERR_ARG, "kzg_verify_batch: workspace");
+    ZK_HIP(hipMemcpyAsync(d_g2, srs_g2, 2 * 128, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemsetAsync(d_valid, 1, ch, st));  // the points are not validated: every lane takes part
+    std::vector<uint32_t> rr(ch * 4);
+    std::vector<uint8_t> one(1);
+    size_t total = 0;
+    for (size_t c0 = 0; c0 < n_openings; c0 += ch) {
+        const size_t n = std::min(ch, n_openings - c0);
+        for (size_t i = 0; i < n; i++) {
+            const uint64_t idx = c0 + i;
+            for (int b = 0; b < 8; b++) pre[78 + b] = (uint8_t)(idx >> (8 * b));
+            uint8_t d[32];
+            sha(pre, sizeof pre, d);
+            uint32_t* r = &rr[4 * i];  // the low 128 bits of the digest read as a big-endian integer
+            for (int w = 0; w < 4; w++) r[w] = ((uint32_t)d[28 - 4 * w] << 24) | ((uint32_t)d[29 - 4 * w] << 16) | ((uint32_t)d[30 - 4 * w] << 8) | d[31 - 4 * w];
+            if ((r[0] | r[1] | r[2] | r[3]) == 0) r[0] = 1;
+        }
+        ZK_HIP(hipMemcpyAsync(d_dig, digests + c0, n * 64, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemcpyAsync(d_op, openings + c0, n * 96, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemcpyAsync(d_z, points + c0, n * 32, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemcpyAsync(d_rr, rr.data(), n * 16, hipMemcpyHostToDevice, st));
+        ZK_LAUNCH(s, st, "kzg_combine", k_kzg_combine, dim3(blocks(n, 64)), dim3(64), 0, (const Affine<Fp>*)d_dig, (const KzgLane*)d_op, (const Fr*)d_z,
+                  (const uint32_t*)d_rr, n, G, d_fa, d_fb, d_p);
+        const XYZZ<Fp>* a_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, d_fa, d_fa2, n, 1);
+        const XYZZ<Fp>* b_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, d_fb, d_fb2, n, 1);
+        XYZZ<HFp> sa, sb;
+        ZK_HIP(hipMemcpyAsync(&sa, a_sum, 128, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipMemcpyAsync(&sb, b_sum, 128, hipMemcpyDeviceToHost, st));
+        ZK_TRY(slot_sync(s, st));
+        // e(sum_i lambda_i (C_i - v_i G + z_i H_i), [1]2) e(-sum_i lambda_i H_i, [alpha]2) == 1: two Miller loops whatever n is
+        const Affine<HFp> two[2] = {sa.to_affine(), sb.to_affine().neg()};
+        ZK_HIP(hipMemcpyAsync(d_two, two, 2 * 64, hipMemcpyHostToDevice, st));
+        ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(1), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_two, (size_t)2, (const Affine<Fp2>*)nullptr, (size_t)0,
+                  (const Affine<Fp2>*)d_g2, (size_t)1, PK, d_m);
+        const F12* prod = fold_all(s, st, "f12_fold", k_f12_fold, PAIR_BLOCK, d_m, d_ws, 2, 1);
+        ZK_HIP(hipMemsetAsync(d_chk, 1, 1, st));  // d_chk[0]: "valid", d_chk[1]: the verdict
+        ZK_TRY(final_exp(s, st, PK, prod, 1, 1, nullptr, d_one_ws, nullptr, d_chk, d_chk + 1));
+        ZK_HIP(hipMemcpyAsync(one.data(), d_chk + 1, 1, hipMemcpyDeviceToHost, st));
+        ZK_TRY(slot_sync(s, st));
+        if (one[0]) {
+            memset(accepted + c0, 1, n);
+            total += n;
+            continue;
+        }
+        // fallback: each opening's own two-pairing check e(T_i, [1]2) e(-H_i, [alpha]2) == 1
         ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(blocks(2 * n, PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_p, 2 * n,
                   (const Affine<Fp2>*)nullptr, (size_t)0, (const Affine<Fp2>*)d_g2, n, PK, d_m);
         ZK_TRY(final_exp(s, st, PK, d_m, n, 2, nullptr, d_ws, nullptr, d_valid, d_verdict));

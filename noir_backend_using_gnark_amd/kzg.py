@@ -2,6 +2,10 @@
     kzg.NewSRS(size, alpha)         reached at /root/reference/gnark_backend_ffi/backend/common.go:137      -> new_srs(size, alpha)
     (*SRS).ReadFrom / WriteTo       what LoadSRS / SaveSRS move through srs.hex (backend/common.go:86-125) -> read_srs / SRS.write
     kzg.Commit(p, srs)              reached through plonk.Setup / plonk.Prove (backend/plonk/plonk.go:21,67) -> SRS.commit
+    kzg.Open(p, point, srs)         plonk.Prove's opening of Z at omega zeta                                  -> SRS.open (SRS.open_many: several at once)
+    kzg.BatchOpenSinglePoint        plonk.Prove's batched opening of seven polynomials at zeta               -> SRS.batch_open_single_point
+    kzg.Verify / FoldProof / BatchVerifySinglePoint   the end of plonk.Verify (host, no device)              -> verify / fold_proof / batch_verify_single_point
+    kzg.BatchVerifyMultiPoints      many openings in one check, a verdict each (device)                      -> batch_verify_multi_points
 The G1 side lives in HBM as a registered base array with its window tables; decoding a serialised SRS decompresses the points on the
 device (one square root each) instead of on the host cores, and happens once instead of on every prove / verify call."""
 from __future__ import annotations
@@ -30,6 +34,49 @@ class SRS:
             return self.g1.multi_exp_dev(poly, n, cfg)
         return self.g1.multi_exp(poly, cfg)
 
+    @staticmethod
+    def _rows(polys, lens):
+        """host arrays or DeviceBuffers (then lens[k] = their coefficient counts) -> (pointer array, length array, on_device, keep-alive)"""
+        dev = [isinstance(p, _lib.DeviceBuffer) for p in polys]
+        if dev and any(dev) != all(dev):
+            raise TypeError("polynomials must be all host arrays or all DeviceBuffers")
+        if dev and dev[0]:
+            if lens is None or len(lens) != len(polys):
+                raise ValueError("DeviceBuffer polynomials need their lengths")
+            keep, ptrs, ns = list(polys), [p.ptr for p in polys], [int(n) for n in lens]
+        else:
+            keep = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in polys]
+            ptrs, ns = [a.ctypes.data for a in keep], [a.shape[0] for a in keep]
+        k = len(polys)
+        return (C.c_void_p * max(k, 1))(*ptrs), (C.c_size_t * max(k, 1))(*ns), int(bool(dev and dev[0])), keep
+
+    def open_many(self, polys, points, lens=None):
+        """`len(polys)` independent kzg.Open calls in one launch set: polynomial k at points[k] ((k, 4) Montgomery).  Returns (H (k, 8), claimed values (k, 4))."""
+        ptrs, ns, on_dev, keep = self._rows(polys, lens)
+        z = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 4)
+        if z.shape[0] != len(polys):
+            raise ValueError("one point per polynomial")
+        out = np.zeros((max(len(polys), 1), 12), np.uint64)
+        _check_open(lib().zk_bn254_kzg_open(self.g1.handle, ptrs, ns, vp(z), C.c_size_t(len(polys)), C.c_int(on_dev), vp(out)))
+        out = out[:len(polys)]
+        return out[:, :8].copy(), out[:, 8:].copy()
+
+    def open(self, poly, point, n: int | None = None):
+        """kzg.Open(p, point, srs) -> (H (8,), claimed value (4,)); poly: Montgomery coefficients or a DeviceBuffer with n."""
+        h, v = self.open_many([poly], np.ascontiguousarray(point, dtype=np.uint64).reshape(1, 4), None if n is None else [n])
+        return h[0], v[0]
+
+    def batch_open_single_point(self, polys, digests, point, lens=None):
+        """kzg.BatchOpenSinglePoint(polys, digests, point, sha256, srs) -> (H (8,), claimed values (k, 4))."""
+        ptrs, ns, on_dev, keep = self._rows(polys, lens)
+        d = np.ascontiguousarray(digests, dtype=np.uint64).reshape(-1, 8)
+        if d.shape[0] != len(polys):
+            raise ValueError("kzg: number of digests differs from the number of polynomials")  # ErrInvalidNbDigests
+        h, claimed = np.zeros(8, np.uint64), np.zeros((max(len(polys), 1), 4), np.uint64)
+        _check_open(lib().zk_bn254_kzg_batch_open_single_point(self.g1.handle, ptrs, ns, vp(d), C.c_size_t(len(polys)),
+                                                               vp(np.ascontiguousarray(point, dtype=np.uint64)), C.c_int(on_dev), vp(h), vp(claimed)))
+        return h, claimed[:len(polys)]
+
     def write(self, as_hex: bool = False) -> bytes:
         """(*SRS).WriteTo (as_hex: the text SaveSRS writes to srs.hex)"""
         nbytes = 132 + 32 * self.g1.n
@@ -41,6 +88,63 @@ class SRS:
 
     def free(self):
         self.g1.free()
+
+
+def _check_open(rc: int) -> None:
+    """ZK_ERR_LEN is upstream's ErrInvalidPolynomialSize: a ValueError, like SRS.commit's length errors"""
+    if rc == _lib.ZK_ERR_LEN:
+        raise ValueError((lib().zk_last_error() or b"").decode())
+    check(rc)
+
+
+def _opening(h, claimed) -> np.ndarray:
+    o = np.zeros(12, np.uint64)
+    o[:8], o[8:] = np.asarray(h, np.uint64).reshape(8), np.asarray(claimed, np.uint64).reshape(4)
+    return o
+
+
+def verify(digest, h, claimed, point, g2) -> bool:
+    """kzg.Verify(digest, proof{H, ClaimedValue}, point, srs) on the host: e(C - v G + z H, [1]2) e(-H, [alpha]2) == 1; g2 = SRS.g2."""
+    ok = C.c_int(0)
+    check(lib().zk_bn254_kzg_verify(vp(np.ascontiguousarray(digest, dtype=np.uint64)), vp(_opening(h, claimed)), vp(np.ascontiguousarray(point, dtype=np.uint64)),
+                                    vp(np.ascontiguousarray(g2, dtype=np.uint64)), C.byref(ok)))
+    return bool(ok.value)
+
+
+def fold_proof(digests, h, claimed, point):
+    """kzg.FoldProof(digests, batchOpeningProof{H, ClaimedValues}, point, sha256) -> ((H, folded claimed value), folded digest)."""
+    d = np.ascontiguousarray(digests, dtype=np.uint64).reshape(-1, 8)
+    v = np.ascontiguousarray(claimed, dtype=np.uint64).reshape(-1, 4)
+    if d.shape[0] != v.shape[0]:
+        raise ValueError("kzg: number of digests differs from the number of claimed values")
+    o, fd = np.zeros(12, np.uint64), np.zeros(8, np.uint64)
+    check(lib().zk_bn254_kzg_fold_proof(vp(d), C.c_size_t(d.shape[0]), vp(np.ascontiguousarray(h, dtype=np.uint64)), vp(v),
+                                        vp(np.ascontiguousarray(point, dtype=np.uint64)), vp(o), vp(fd)))
+    return (o[:8].copy(), o[8:].copy()), fd
+
+
+def batch_verify_single_point(digests, h, claimed, point, g2) -> bool:
+    """kzg.BatchVerifySinglePoint on the host: fold, then verify."""
+    d = np.ascontiguousarray(digests, dtype=np.uint64).reshape(-1, 8)
+    v = np.ascontiguousarray(claimed, dtype=np.uint64).reshape(-1, 4)
+    if d.shape[0] != v.shape[0]:
+        raise ValueError("kzg: number of digests differs from the number of claimed values")
+    ok = C.c_int(0)
+    check(lib().zk_bn254_kzg_batch_verify_single_point(vp(d), C.c_size_t(d.shape[0]), vp(np.ascontiguousarray(h, dtype=np.uint64)), vp(v),
+                                                       vp(np.ascontiguousarray(point, dtype=np.uint64)), vp(np.ascontiguousarray(g2, dtype=np.uint64)), C.byref(ok)))
+    return bool(ok.value)
+
+
+def batch_verify_multi_points(digests, hs, claimed, points, g2) -> np.ndarray:
+    """kzg.BatchVerifyMultiPoints on the device with a verdict per opening: digests (n, 8), hs (n, 8), claimed (n, 4), points (n, 4) -> (n,) uint8."""
+    d = np.ascontiguousarray(digests, dtype=np.uint64).reshape(-1, 8)
+    n = d.shape[0]
+    o = np.zeros((n, 12), np.uint64)
+    o[:, :8], o[:, 8:] = np.asarray(hs, np.uint64).reshape(n, 8), np.asarray(claimed, np.uint64).reshape(n, 4)
+    z = np.ascontiguousarray(points, dtype=np.uint64).reshape(n, 4)
+    acc, cnt = np.zeros(max(n, 1), np.uint8), C.c_size_t(0)
+    check(lib().zk_bn254_kzg_verify_batch(vp(d), vp(o), vp(z), C.c_size_t(n), vp(np.ascontiguousarray(g2, dtype=np.uint64)), vp(acc), C.byref(cnt)))
+    return acc[:n]
 
 
 def new_srs(size: int, alpha_mont, table_window_bits: int = 0) -> SRS:
