@@ -198,4 +198,33 @@ void prof_host(const char* name, double ms);  // host-side section of the path (
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// A request's workspace, written down once: plan_workspace runs the same layout function against a counting plan (slot == nullptr: sums what Slot::alloc
+// will take, 256-byte alignment included), reserves exactly that, and runs it again against the slot.  One failure flag, checked once.
+struct ArenaPlan {
+    Slot* slot = nullptr;
+    size_t bytes = 0;
+    bool failed = false;
+    // `count` elements for each of the pointers
+    template <class T, class... R>
+    void take(size_t count, T*& p, R*&... rest) {
+        p = slot ? (T*)slot->alloc(count * sizeof(T)) : nullptr;
+        if (slot) failed |= !p;
+        later(count * sizeof(T));
+        if constexpr (sizeof...(rest) > 0) take(count, rest...);
+    }
+    // what a callee takes from the arena after the layout, in one allocation (g2_decompress_dev's scratch): counted only
+    void later(size_t n_bytes) {
+        if (!slot) bytes = align_up(bytes, 256) + n_bytes;
+    }
+};
+template <class Layout>
+int plan_workspace(Slot* s, const char* who, Layout&& layout) {
+    ArenaPlan count, place;
+    layout(count);
+    ZK_TRY(s->reserve(count.bytes));
+    place.slot = s;
+    layout(place);
+    return place.failed ? set_err(ZK_ERR_ARG, "%s: workspace", who) : ZK_OK;
+}
+
 }  // namespace zkmi

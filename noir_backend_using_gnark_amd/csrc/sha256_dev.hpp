@@ -99,4 +99,12 @@ ZK_HD void sha_words_to_limbs(const uint32_t d[8], uint32_t l[8]) {
     for (int i = 0; i < 8; i++) l[i] = d[7 - i];
 }
 
+// The coefficient rule of the batch verifiers (include/zkmi.h: r_i, rho_i, lambda_i): the low 128 bits of a digest read as a big-endian integer, forced
+// non-zero.  l: that integer as limbs (sha_words_to_limbs on the device, the digest bytes read backwards on the host); out: the coefficient's four limbs
+ZK_HD void batch_coeff(const uint32_t l[8], uint32_t out[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) out[i] = l[i];
+    if ((out[0] | out[1] | out[2] | out[3]) == 0) out[0] = 1;
+}
+
 }  // namespace zkmi

@@ -1,23 +1,16 @@
-// Pairings and batch Groth16 / PLONK verification on the device (include/zkmi.h "Pairings and batch Groth16 / PLONK verification on the DEVICE").
-//   zk_bn254_pair          one Miller loop per lane (k_miller), a product tree (k_f12_fold), one final exponentiation (k_fe_*)
-//   zk_bn254_groth16_verify_batch, per chunk of at most 2^16 proofs:
-//     decode      Ar / Krs through k_g1_decompress, Bs through k_g2_decompress + the r-torsion test, with a flag per invalid point
-//     combine     k_vb_prep: r_i Ar_i (affine), r_i Krs_i, r_i (1, w_i1, ..); k_g1_fold / k_fr_fold sum the last two over the chunk; the host scales the
-//                 three fixed-key terms: -(sum r_i) alpha, -sum_j c_j K_j, -sum r_i Krs_i
-//     check       n' + 3 Miller loops, product tree, one final exponentiation: prod e(r_i Ar_i, Bs_i) e(-c_0 alpha, beta) e(-sum c_j K_j, gamma)
-//                 e(-sum r_i Krs_i, delta) == 1 accepts every valid proof of the chunk
-//     fallback    (only when the check fails) k_vb_single: -Ar_i, IC_i = K_0 + sum_j w_ij K_j, Krs_i per lane; 3 n + 1 Miller loops (the last one is
-//                 e(alpha, beta)'s); k_fe_easy multiplies each proof's three values and e(alpha, beta)'s, the k_fe_* chain exponentiates, k_fe_last
-//                 compares with one
-//   zk_bn254_plonk_verify_batch, per chunk of at most 2^16 proofs (one lane per proof):
-//     decode      k_pv_gather (header, points, values mod r), k_g1_decompress over the nine points with a flag per invalid point
-//     per proof   k_pv_transcript (gamma, beta, alpha, zeta from SHA-256 on the device), k_pv_scalars (PI, L1, the quotient identity), k_pv_smul + k_pv_digests
-//                 (folded quotient and linearised digests), k_pv_kzg (kzg's folding challenge, rho_i, rho'_i, the scalars of the combined openings)
-//     check       k_pv_smul + k_pv_combine: A_i = rho_i (D_i - e_i G + zeta_i W_i) + rho'_i (Z_i - zu_i G + zeta_i omega W'_i) without the fixed points,
-//                 B_i = rho_i W_i + rho'_i W'_i; k_g1_fold / k_fr_fold sum them; the host adds the G, S1, S2 terms; e(sum A, [1]2) e(-sum B, [alpha]2) == 1
-//     fallback    (only when the check fails) each proof's own A_i, -B_i (k_pv_single), 2 n Miller loops, a final exponentiation and a verdict per proof
-//   zk_bn254_kzg_verify_batch, per chunk of at most 2^16 openings (one lane per opening): k_kzg_combine, the same folds, two Miller loops and one
-//                 final exponentiation; the fallback runs each lane's own pair through k_miller and the per-lane final exponentiation
+// Pairings and batch Groth16 / PLONK / KZG verification on the device (include/zkmi.h "Pairings and batch Groth16 / PLONK verification on the DEVICE").
+//   zk_bn254_pair   one Miller loop per lane (k_miller), a product tree (k_f12_fold), one final exponentiation (k_fe_*)
+// The three batch verifiers work in chunks of at most 2^16 lanes and share one pairing check per chunk (PairCheck):
+//   coefficients   128 bits per lane from SHA-256 (batch_coeff: on the host in batch_coeffs, PLONK's on the device in k_pv_kzg)
+//   combine        the lanes' points times their coefficients, summed by halving folds (k_g1_fold / k_fr_fold); the host adds the fixed-key terms
+//   check          Miller loops over the folded points, the product tree, one final exponentiation: a product of one accepts every valid lane
+//   fallback       (only when the check fails) each valid lane's own Miller loops, a final exponentiation and a verdict per lane
+// What each adds (the kernels say the rest):
+//   groth16 (one lane per proof)   k_g1_decompress / k_g2_decompress with a flag per invalid point; k_vb_prep: r_i Ar_i, r_i Krs_i, r_i (1, w_i1, ..); check: n' + 3
+//       lanes, prod e(r_i Ar_i, Bs_i) e(-c_0 alpha, beta) e(-sum c_j K_j, gamma) e(-sum r_i Krs_i, delta) == 1; fallback: k_vb_single, 3 n + 1 lanes (the last: e(alpha, beta))
+//   plonk (one lane per proof)   k_pv_gather, k_g1_decompress, k_pv_transcript, k_pv_scalars, k_pv_smul + k_pv_digests, k_pv_kzg, k_pv_smul +
+//       k_pv_combine (A_i, B_i); check: 2 lanes, e(sum A + the G, S1, S2 terms, [1]2) e(-sum B, [alpha]2) == 1; fallback: k_pv_smul + k_pv_single, 2 n lanes
+//   kzg (one lane per opening)   k_kzg_combine (lambda_i T_i, lambda_i H_i and the lane's own pair); check: 2 lanes; fallback: 2 n lanes
 #include <string.h>
 
 #include <algorithm>
@@ -412,12 +405,10 @@ __global__ __launch_bounds__(64) void k_pv_kzg(const Affine<Fp>* __restrict__ pt
         for (int k = 0; k < 48 + 8 + 1; k++) h.put_byte(k < 48 ? rtail[k] : k < 56 ? (uint32_t)(idx >> (8 * (k - 48))) : (uint32_t)tag);
         uint32_t dg[8];
         h.final(dg);
-        Fr r = Fr::zero();  // the low 128 bits of the digest as a big-endian integer, forced non-zero
-        r.l[0] = dg[7];
-        r.l[1] = dg[6];
-        r.l[2] = dg[5];
-        r.l[3] = dg[4];
-        if ((r.l[0] | r.l[1] | r.l[2] | r.l[3]) == 0) r.l[0] = 1;
+        uint32_t l[8];
+        sha_words_to_limbs(dg, l);
+        Fr r = Fr::zero();
+        batch_coeff(l, r.l);
         r = r.to_mont();
         if (tag == 0) rho = r;
         else rho2 = r;
@@ -498,20 +489,25 @@ __global__ __launch_bounds__(64) void k_kzg_combine(const Affine<Fp>* __restrict
     fb[i] = scalar_mul(h, k);
 }
 
-// halving launches until one element is left; a and b hold at least ceil(n / 2) elements each (a: n); returns where the result is
+// the two buffers of a fold: a holds the n x cols elements to fold (overwritten), b at least ceil(n / 2) x cols
+template <class T>
+struct FoldPair {
+    T *a = nullptr, *b = nullptr;
+    void layout(ArenaPlan& p, size_t n, size_t cols = 1) { p.take(n * cols, a); p.take((n + 1) / 2 * cols, b); }
+};
+// halving launches until one element is left; returns where the result is
 template <class T, class Kern>
-T* fold_all(Slot* s, hipStream_t st, const char* name, Kern kernel, unsigned block, T* a, T* b, size_t n, size_t cols) {
+T* fold_all(Slot* s, hipStream_t st, const char* name, Kern kernel, unsigned block, FoldPair<T> f, size_t n, size_t cols) {
     while (n > 1) {
         const size_t m = (n + 1) / 2;
-        ZK_LAUNCH(s, st, name, kernel, dim3(blocks(m * cols, block)), dim3(block), 0, (const T*)a, n, cols, b);
-        std::swap(a, b);
+        ZK_LAUNCH(s, st, name, kernel, dim3(blocks(m * cols, block)), dim3(block), 0, (const T*)f.a, n, cols, f.b);
+        std::swap(f.a, f.b);
         n = m;
     }
-    return a;
+    return f.a;
 }
 
 constexpr size_t CHUNK = (size_t)1 << 16;
-constexpr size_t SLACK = 64 * 256;  // per-allocation alignment, generously
 
 // final exponentiation of n lanes (see k_fe_easy); d_ws: FE_SLOTS n F12
 int final_exp(Slot* s, hipStream_t st, const PairConsts& K, const F12* d_in, size_t n, int rows, const F12* d_mul_by, F12* d_ws, F12* d_out,
@@ -524,11 +520,91 @@ int final_exp(Slot* s, hipStream_t st, const PairConsts& K, const F12* d_in, siz
     return ZK_OK;
 }
 
-void sha(const void* p, size_t n, uint8_t out[32]) {
+// SHA-256 of a || b || c
+void sha(uint8_t out[32], const void* a, size_t na, const void* b = nullptr, size_t nb = 0, const void* c = nullptr, size_t nc = 0) {
     Sha256 h;
-    h.update(p, n);
+    h.update(a, na);
+    h.update(b, nb);
+    h.update(c, nc);
     h.final(out);
 }
+
+// out[4 i ..] = the coefficient of lane c0 + i (batch_coeff) for i < n: pre with the lane's index, u64 little-endian, written at idx_offset, hashed
+void batch_coeffs(uint8_t* pre, size_t pre_len, size_t idx_offset, size_t c0, size_t n, uint32_t* out) {
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t idx = c0 + i;
+        for (int b = 0; b < 8; b++) pre[idx_offset + b] = (uint8_t)(idx >> (8 * b));
+        uint8_t d[32];
+        sha(d, pre, pre_len);
+        uint32_t l[8];
+        for (int w = 0; w < 8; w++) l[w] = ((uint32_t)d[28 - 4 * w] << 24) | ((uint32_t)d[29 - 4 * w] << 16) | ((uint32_t)d[30 - 4 * w] << 8) | d[31 - 4 * w];
+        batch_coeff(l, out + 4 * i);
+    }
+}
+
+// The pairing check of a chunk, shared by the three batch verifiers: its buffers and its steps.  An entry fills d_valid and the points, then
+//   sync_valid   waits for what the entry has queued and for the lanes' valid flags; a chunk without a valid lane is rejected whole
+//   combined     the Miller loops of the folded points, the product tree, one final exponentiation; a product of one accepts every valid lane
+//   per_lane     (only when that fails) rows Miller loops, a final exponentiation and a verdict per lane
+// decided: the last step settled the chunk's verdicts (the entry goes on to the next chunk); total: the lanes accepted so far
+struct PairCheck {
+    Slot* s;
+    hipStream_t st;
+    PairConsts K;
+    size_t ch;                                   // lanes per chunk, at most
+    F12 *d_m, *d_ws, *d_one_ws;                  // Miller values; FE_SLOTS per lane (and the product tree's second buffer); the combined check's FE_SLOTS
+    uint8_t *d_valid, *d_verdict, *d_chk;        // per lane; the combined check's own "valid" (d_chk[0]) and verdict (d_chk[1])
+    std::vector<uint8_t> valid;                  // d_valid on the host
+    uint8_t one = 0;
+    bool decided = false;
+    size_t total = 0;
+
+    PairCheck(Slot* s_, const PairConsts& K_, size_t ch_) : s(s_), st(s_->stream), K(K_), ch(ch_), valid(ch_) {}
+    // m_lanes: the most Miller loops of one launch
+    void layout(ArenaPlan& p, size_t m_lanes) {
+        p.take(m_lanes, d_m);
+        p.take(std::max(FE_SLOTS * ch, (m_lanes + 1) / 2), d_ws);
+        p.take(FE_SLOTS, d_one_ws);
+        p.take(ch, d_valid, d_verdict);
+        p.take(64, d_chk);
+    }
+    void miller(const Affine<Fp>* P, size_t lanes, const Affine<Fp2>* qvar, size_t n_var, const Affine<Fp2>* qfix, size_t rep) {
+        ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(blocks(lanes, PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, P, lanes, qvar, n_var, qfix, rep, K, d_m);
+    }
+    void tally(const uint8_t* accepted, size_t n) { for (size_t i = 0; i < n; i++) total += accepted[i] ? 1 : 0; }
+    int sync_valid(size_t n, uint8_t* accepted) {
+        ZK_HIP(hipMemcpyAsync(valid.data(), d_valid, n, hipMemcpyDeviceToHost, st));
+        ZK_TRY(slot_sync(s, st));
+        decided = std::none_of(valid.begin(), valid.begin() + n, [](uint8_t v) { return v != 0; });
+        if (decided) memset(accepted, 0, n);
+        return ZK_OK;
+    }
+    // prod_{i < n_lanes} e(P_i, Q_i) == 1, Q_i = qvar[i] for i < n_var, qfix[i - n_var] after; if so, accepted = valid for the chunk's n lanes
+    int combined(const Affine<Fp>* P, size_t n_lanes, const Affine<Fp2>* qvar, size_t n_var, const Affine<Fp2>* qfix, size_t n, uint8_t* accepted) {
+        miller(P, n_lanes, qvar, n_var, qfix, 1);
+        const F12* prod = fold_all(s, st, "f12_fold", k_f12_fold, PAIR_BLOCK, FoldPair<F12>{d_m, d_ws}, n_lanes, 1);
+        ZK_HIP(hipMemsetAsync(d_chk, 1, 1, st));
+        ZK_TRY(final_exp(s, st, K, prod, 1, 1, nullptr, d_one_ws, nullptr, d_chk, d_chk + 1));
+        ZK_HIP(hipMemcpyAsync(&one, d_chk + 1, 1, hipMemcpyDeviceToHost, st));
+        ZK_TRY(slot_sync(s, st));
+        decided = one != 0;
+        if (decided) {
+            memcpy(accepted, valid.data(), n);
+            tally(accepted, n);
+        }
+        return ZK_OK;
+    }
+    // accepted[i] = valid[i] && prod_{r < rows} e(P[r n + i], Q_r) == 1 -- times e(P[rows n], qfix's last) when shared_lane -- with Q_r = qvar[i] while
+    // r n + i < n_var, qfix[r - n_var / n] after
+    int per_lane(const Affine<Fp>* P, size_t n, int rows, const Affine<Fp2>* qvar, size_t n_var, const Affine<Fp2>* qfix, bool shared_lane, uint8_t* accepted) {
+        miller(P, rows * n + (shared_lane ? 1 : 0), qvar, n_var, qfix, n);
+        ZK_TRY(final_exp(s, st, K, d_m, n, rows, shared_lane ? d_m + rows * n : nullptr, d_ws, nullptr, d_valid, d_verdict));
+        ZK_HIP(hipMemcpyAsync(accepted, d_verdict, n, hipMemcpyDeviceToHost, st));
+        ZK_TRY(slot_sync(s, st));
+        tally(accepted, n);
+        return ZK_OK;
+    }
+};
 
 }  // namespace
 
@@ -551,29 +627,31 @@ int zk_bn254_pair(const zk_g1_affine* p, const zk_g2_affine* q, size_t n, zk_gt*
     Slot* s = g.s;
     hipStream_t st = s->stream;
     const size_t ch = std::min(std::max(n, (size_t)1), CHUNK);
-    ZK_TRY(s->reserve(ch * (64 + 128 + 384 + 384) + (FE_SLOTS + 1) * 384 + SLACK));
-    Affine<Fp>* d_p = (Affine<Fp>*)s->alloc(ch * 64);
-    Affine<Fp2>* d_q = (Affine<Fp2>*)s->alloc(ch * 128);
-    F12* d_m = (F12*)s->alloc(ch * 384);
-    F12* d_b = (F12*)s->alloc(ch * 384);
-    F12* d_ws = (F12*)s->alloc((FE_SLOTS + 1) * 384);
-    if (!d_p || !d_q || !d_m || !d_b || !d_ws) return set_err(ZK_ERR_ARG, "pair: workspace");
+    Affine<Fp>* d_p;
+    Affine<Fp2>* d_q;
+    FoldPair<F12> fm;  // the Miller values and their product tree
+    F12* d_ws;
+    ZK_TRY(plan_workspace(s, "pair", [&](ArenaPlan& p) {
+        p.take(ch, d_p, d_q);
+        fm.layout(p, ch);
+        p.take(FE_SLOTS + 1, d_ws);
+    }));
     F12 acc = F12::one();  // the chunks' Miller products, multiplied on the host (one product per 2^16 pairs)
     for (size_t c0 = 0; c0 < n; c0 += ch) {
         const size_t m = std::min(ch, n - c0);
         ZK_HIP(hipMemcpyAsync(d_p, p + c0, m * 64, hipMemcpyHostToDevice, st));
         ZK_HIP(hipMemcpyAsync(d_q, q + c0, m * 128, hipMemcpyHostToDevice, st));
         ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(blocks(m, PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_p, m, (const Affine<Fp2>*)d_q, m,
-                  (const Affine<Fp2>*)nullptr, (size_t)1, K, d_m);
-        const F12* r = fold_all(s, st, "f12_fold", k_f12_fold, PAIR_BLOCK, d_m, d_b, m, 1);
+                  (const Affine<Fp2>*)nullptr, (size_t)1, K, fm.a);
+        const F12* r = fold_all(s, st, "f12_fold", k_f12_fold, PAIR_BLOCK, fm, m, 1);
         F12 part;
         ZK_HIP(hipMemcpyAsync(&part, r, 384, hipMemcpyDeviceToHost, st));
         ZK_TRY(slot_sync(s, st));
         acc = acc * part;
     }
     ZK_HIP(hipMemcpyAsync(d_ws + FE_SLOTS, &acc, 384, hipMemcpyHostToDevice, st));
-    ZK_TRY(final_exp(s, st, K, d_ws + FE_SLOTS, 1, 1, nullptr, d_ws, d_m, nullptr, nullptr));
-    ZK_HIP(hipMemcpyAsync(out, d_m, 384, hipMemcpyDeviceToHost, st));
+    ZK_TRY(final_exp(s, st, K, d_ws + FE_SLOTS, 1, 1, nullptr, d_ws, fm.a, nullptr, nullptr));
+    ZK_HIP(hipMemcpyAsync(out, fm.a, 384, hipMemcpyDeviceToHost, st));
     return slot_sync(s, st);
 }
 
@@ -593,51 +671,43 @@ int zk_bn254_groth16_verify_batch(const uint8_t* proofs, size_t n_proofs, const 
     // r_i = low 128 bits of SHA-256(tag || SHA-256(vk) || SHA-256(proofs || public inputs) || u64 i), forced non-zero
     uint8_t pre[18 + 32 + 32 + 8];
     memcpy(pre, "zkmi-groth16-batch", 18);
-    sha(v.bytes.data(), v.bytes.size(), pre + 18);
-    {
-        Sha256 h;
-        h.update(proofs, n_proofs * 128);
-        if (np) h.update(public_inputs, n_proofs * np * 32);
-        h.final(pre + 50);
-    }
+    sha(pre + 18, v.bytes.data(), v.bytes.size());
+    sha(pre + 50, proofs, n_proofs * 128, public_inputs, n_proofs * np * 32);
 
     SlotGuard g;
     ZK_TRY(acquire_slot(&g.s));
     Slot* s = g.s;
     hipStream_t st = s->stream;
     const size_t ch = std::min(n_proofs, CHUNK);
-    const size_t per = 128 + 64 + 64 + 128 + 3 + 1 + 1 + 16 + 128 + 64 + np * 32 + cols * 32 * 2 + 3 * 64 + 3 * 384 + FE_SLOTS * 384 + G2_DECOMPRESS_SCRATCH;
-    ZK_TRY(s->reserve(ch * per + nk * 64 + 16 * 384 + 64 * 1024));
-    uint8_t* d_raw = (uint8_t*)s->alloc(ch * 128);        // Ar | Bs | Krs, each contiguous
-    Affine<Fp>* d_ar = (Affine<Fp>*)s->alloc(ch * 64);
-    Affine<Fp>* d_krs = (Affine<Fp>*)s->alloc(ch * 64);
-    Affine<Fp2>* d_bs = (Affine<Fp2>*)s->alloc(ch * 128);
-    uint8_t* d_bad = (uint8_t*)s->alloc(ch * 3);
-    uint8_t* d_valid = (uint8_t*)s->alloc(ch);
-    uint32_t* d_rr = (uint32_t*)s->alloc(ch * 16);
-    XYZZ<Fp>* d_rk = (XYZZ<Fp>*)s->alloc(ch * 128);
-    XYZZ<Fp>* d_rk2 = (XYZZ<Fp>*)s->alloc((ch + 1) / 2 * 128);
-    Fr* d_pub = (Fr*)s->alloc(std::max(ch * np, (size_t)1) * 32);
-    Fr* d_terms = (Fr*)s->alloc(ch * cols * 32);
-    Fr* d_terms2 = (Fr*)s->alloc((ch + 1) / 2 * cols * 32);
-    Affine<Fp>* d_p = (Affine<Fp>*)s->alloc((3 * ch + 3) * 64);
-    F12* d_m = (F12*)s->alloc((3 * ch + 3) * 384);
-    F12* d_ws = (F12*)s->alloc(std::max(FE_SLOTS * ch, 3 * ch + 3) * 384);
-    Affine<Fp>* d_kpts = (Affine<Fp>*)s->alloc(nk * 64);
-    Affine<Fp2>* d_fix = (Affine<Fp2>*)s->alloc(3 * 128);
-    F12* d_one_ws = (F12*)s->alloc(FE_SLOTS * 384);
-    uint8_t* d_verdict = (uint8_t*)s->alloc(ch);
-    int* d_status = (int*)s->alloc(64);
-    uint8_t* d_chk = (uint8_t*)s->alloc(64);
-    if (!d_raw || !d_ar || !d_krs || !d_bs || !d_bad || !d_valid || !d_rr || !d_rk || !d_rk2 || !d_pub || !d_terms || !d_terms2 || !d_p || !d_m || !d_ws || !d_kpts ||
-        !d_fix || !d_one_ws || !d_verdict || !d_status || !d_chk)
-        return set_err(ZK_ERR_ARG, "groth16_verify_batch: workspace");
+    PairCheck pc(s, K, ch);
+    uint8_t *d_raw, *d_bad;  // d_raw: Ar | Bs | Krs, each contiguous
+    Affine<Fp> *d_ar, *d_krs, *d_p, *d_kpts;
+    Affine<Fp2> *d_bs, *d_fix;
+    uint32_t* d_rr;
+    Fr* d_pub;
+    FoldPair<XYZZ<Fp>> rk_fold;
+    FoldPair<Fr> terms;
+    int* d_status;
+    ZK_TRY(plan_workspace(s, "groth16_verify_batch", [&](ArenaPlan& p) {
+        p.take(ch * 128, d_raw);
+        p.take(ch, d_ar, d_krs, d_bs);
+        p.take(ch * 3, d_bad);
+        p.take(ch * 4, d_rr);
+        p.take(std::max(ch * np, (size_t)1), d_pub);
+        rk_fold.layout(p, ch);
+        terms.layout(p, ch, cols);
+        p.take(3 * ch + 3, d_p);
+        pc.layout(p, 3 * ch + 3);
+        p.take(nk, d_kpts);
+        p.take(3, d_fix);
+        p.take(16, d_status);
+        p.later(ch * G2_DECOMPRESS_SCRATCH);  // g2_decompress_dev's, per chunk
+    }));
     ZK_HIP(hipMemcpyAsync(d_kpts, v.K.data(), nk * 64, hipMemcpyHostToDevice, st));
     const size_t arena_mark = s->arena_off;  // g2_decompress_dev takes its scratch from the arena per call: give it back per chunk
 
-    std::vector<uint8_t> raw(ch * 128), valid(ch), one(1);
+    std::vector<uint8_t> raw(ch * 128);
     std::vector<uint32_t> rr(ch * 4);
-    size_t total = 0;
     for (size_t c0 = 0; c0 < n_proofs; c0 += ch) {
         const size_t n = std::min(ch, n_proofs - c0);
         s->arena_off = arena_mark;
@@ -646,14 +716,8 @@ int zk_bn254_groth16_verify_batch(const uint8_t* proofs, size_t n_proofs, const 
             memcpy(&raw[i * 32], pr, 32);
             memcpy(&raw[n * 32 + i * 64], pr + 32, 64);
             memcpy(&raw[n * 96 + i * 32], pr + 96, 32);
-            const uint64_t idx = c0 + i;
-            for (int b = 0; b < 8; b++) pre[82 + b] = (uint8_t)(idx >> (8 * b));
-            uint8_t d[32];
-            sha(pre, sizeof pre, d);
-            uint32_t* r = &rr[4 * i];  // the low 128 bits of the digest read as a big-endian integer
-            for (int w = 0; w < 4; w++) r[w] = ((uint32_t)d[28 - 4 * w] << 24) | ((uint32_t)d[29 - 4 * w] << 16) | ((uint32_t)d[30 - 4 * w] << 8) | d[31 - 4 * w];
-            if ((r[0] | r[1] | r[2] | r[3]) == 0) r[0] = 1;
         }
+        batch_coeffs(pre, sizeof pre, 82, c0, n, rr.data());
         ZK_HIP(hipMemcpyAsync(d_raw, raw.data(), n * 128, hipMemcpyHostToDevice, st));
         ZK_HIP(hipMemcpyAsync(d_rr, rr.data(), n * 16, hipMemcpyHostToDevice, st));
         if (np) ZK_HIP(hipMemcpyAsync(d_pub, public_inputs + c0 * np, n * np * 32, hipMemcpyHostToDevice, st));
@@ -663,21 +727,15 @@ int zk_bn254_groth16_verify_batch(const uint8_t* proofs, size_t n_proofs, const 
         ZK_TRY(g2_decompress_dev(s, st, d_raw + n * 32, n, d_bs, d_status, d_bad + n));
         ZK_TRY(g1_decompress_dev(s, st, d_raw + n * 96, n, d_krs, d_status, d_bad + 2 * n));
         ZK_LAUNCH(s, st, "vb_prep", k_vb_prep, dim3(blocks(n, 128)), dim3(128), 0, (const Affine<Fp>*)d_ar, (const Affine<Fp>*)d_krs, (const uint8_t*)d_bad,
-                  (const uint32_t*)d_rr, (const Fr*)d_pub, n, np, d_valid, d_p, d_rk, d_terms);
-        const XYZZ<Fp>* rk_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, d_rk, d_rk2, n, 1);
-        const Fr* c_sum = fold_all(s, st, "fr_fold", k_fr_fold, 256, d_terms, d_terms2, n, cols);
+                  (const uint32_t*)d_rr, (const Fr*)d_pub, n, np, pc.d_valid, d_p, rk_fold.a, terms.a);
+        const XYZZ<Fp>* rk_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, rk_fold, n, 1);
+        const Fr* c_sum = fold_all(s, st, "fr_fold", k_fr_fold, 256, terms, n, cols);
         XYZZ<HFp> rk;
         std::vector<HFr> c(cols);
         ZK_HIP(hipMemcpyAsync(&rk, rk_sum, 128, hipMemcpyDeviceToHost, st));
         ZK_HIP(hipMemcpyAsync(c.data(), c_sum, cols * 32, hipMemcpyDeviceToHost, st));
-        ZK_HIP(hipMemcpyAsync(valid.data(), d_valid, n, hipMemcpyDeviceToHost, st));
-        ZK_TRY(slot_sync(s, st));
-        size_t n_valid = 0;
-        for (size_t i = 0; i < n; i++) n_valid += valid[i];
-        if (n_valid == 0) {
-            memset(accepted + c0, 0, n);
-            continue;
-        }
+        ZK_TRY(pc.sync_valid(n, accepted + c0));
+        if (pc.decided) continue;
         // the three fixed-key terms (O(n_public) host work): -c_0 alpha, -sum_j c_j K_j, -sum_i r_i Krs_i
         Affine<HFp> fixed[3];
         {
@@ -695,32 +753,17 @@ int zk_bn254_groth16_verify_batch(const uint8_t* proofs, size_t n_proofs, const 
         const Affine<HFp2> qfix_b[3] = {v.beta, v.gamma, v.delta};
         ZK_HIP(hipMemcpyAsync(d_p + n, fixed, 3 * 64, hipMemcpyHostToDevice, st));
         ZK_HIP(hipMemcpyAsync(d_fix, qfix_b, 3 * 128, hipMemcpyHostToDevice, st));
-        ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(blocks(n + 3, PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_p, n + 3, (const Affine<Fp2>*)d_bs, n,
-                  (const Affine<Fp2>*)d_fix, (size_t)1, K, d_m);
-        const F12* prod = fold_all(s, st, "f12_fold", k_f12_fold, PAIR_BLOCK, d_m, d_ws, n + 3, 1);
-        ZK_HIP(hipMemsetAsync(d_chk, 1, 1, st));  // d_chk[0]: "valid", d_chk[1]: the verdict
-        ZK_TRY(final_exp(s, st, K, prod, 1, 1, nullptr, d_one_ws, nullptr, d_chk, d_chk + 1));
-        ZK_HIP(hipMemcpyAsync(one.data(), d_chk + 1, 1, hipMemcpyDeviceToHost, st));
-        ZK_TRY(slot_sync(s, st));
-        if (one[0]) {
-            memcpy(accepted + c0, valid.data(), n);
-            total += n_valid;
-            continue;
-        }
-        // fallback: every valid proof on its own
+        ZK_TRY(pc.combined(d_p, n + 3, d_bs, n, d_fix, n, accepted + c0));
+        if (pc.decided) continue;
+        // fallback: every valid proof on its own; the shared lane is e(alpha, beta)'s
         const Affine<HFp2> qfix_f[3] = {v.gamma, v.delta, v.beta};
         ZK_HIP(hipMemcpyAsync(d_fix, qfix_f, 3 * 128, hipMemcpyHostToDevice, st));
         ZK_HIP(hipMemcpyAsync(d_p + 3 * n, &v.alpha, 64, hipMemcpyHostToDevice, st));
-        ZK_LAUNCH(s, st, "vb_single", k_vb_single, dim3(blocks(n, 128)), dim3(128), 0, (const Affine<Fp>*)d_ar, (const Affine<Fp>*)d_krs, (const uint8_t*)d_valid,
-                  (const Fr*)d_pub, (const Affine<Fp>*)d_kpts, n, np, d_p);
-        ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(blocks(3 * n + 1, PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_p, 3 * n + 1,
-                  (const Affine<Fp2>*)d_bs, n, (const Affine<Fp2>*)d_fix, n, K, d_m);
-        ZK_TRY(final_exp(s, st, K, d_m, n, 3, d_m + 3 * n, d_ws, nullptr, d_valid, d_verdict));
-        ZK_HIP(hipMemcpyAsync(accepted + c0, d_verdict, n, hipMemcpyDeviceToHost, st));
-        ZK_TRY(slot_sync(s, st));
-        for (size_t i = 0; i < n; i++) total += accepted[c0 + i] ? 1 : 0;
+        ZK_LAUNCH(s, st, "vb_single", k_vb_single, dim3(blocks(n, 128)), dim3(128), 0, (const Affine<Fp>*)d_ar, (const Affine<Fp>*)d_krs,
+                  (const uint8_t*)pc.d_valid, (const Fr*)d_pub, (const Affine<Fp>*)d_kpts, n, np, d_p);
+        ZK_TRY(pc.per_lane(d_p, n, 3, d_bs, n, d_fix, true, accepted + c0));
     }
-    *n_accepted = total;
+    *n_accepted = pc.total;
     return ZK_OK;
 }
 
@@ -760,14 +803,9 @@ int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const vo
     // rho_i, rho'_i = the low 128 bits of SHA-256(tag || SHA-256(vk) || SHA-256(srs_g2) || SHA-256(proofs || public inputs) || u64 i || 0 / 1)
     uint8_t pre[16 + 3 * 32];
     memcpy(pre, "zkmi-plonk-batch", 16);
-    sha(v.bytes.data(), v.bytes.size(), pre + 16);
-    sha(srs_g2, 2 * sizeof(zk_g2_affine), pre + 48);
-    {
-        Sha256 h;
-        h.update(proofs, n_proofs * 548);
-        if (np) h.update(public_inputs, n_proofs * np * 32);
-        h.final(pre + 80);
-    }
+    sha(pre + 16, v.bytes.data(), v.bytes.size());
+    sha(pre + 48, srs_g2, 2 * sizeof(zk_g2_affine));
+    sha(pre + 80, proofs, n_proofs * 548, public_inputs, n_proofs * np * 32);
     Sha256 tr;
     tr.update(pre, sizeof pre);  // one whole block, 48 bytes left in buf
     std::vector<uint8_t> hbytes(tail_len + 13 + 48);
@@ -783,43 +821,38 @@ int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const vo
     Slot* s = g.s;
     hipStream_t st = s->stream;
     const size_t ch = std::min(n_proofs, CHUNK);
-    const size_t per = 548 + PV_NPTS * (32 + 64 + 1) + 3 + PV_NCOL * 32 + np * 32 + 2 * 64 + 10 * 128 + 2 * 128 + 3 * 128 + 8 * 32 + 2 * 64 + 2 * 384 + FE_SLOTS * 384;
-    ZK_TRY(s->reserve(ch * per + 64 * 1024 + 4 * 384 + FE_SLOTS * 384));
-    uint32_t* d_proofs = (uint32_t*)s->alloc(ch * 548);
-    uint32_t* d_praw = (uint32_t*)s->alloc(ch * PV_NPTS * 32);
-    Affine<Fp>* d_pts = (Affine<Fp>*)s->alloc(ch * PV_NPTS * 64);
-    uint8_t* d_bad = (uint8_t*)s->alloc(ch * PV_NPTS);
-    uint8_t* d_hdr = (uint8_t*)s->alloc(ch);
-    uint8_t* d_valid = (uint8_t*)s->alloc(ch);
-    uint8_t* d_verdict = (uint8_t*)s->alloc(ch);
-    Fr* d_sc = (Fr*)s->alloc(ch * PV_NCOL * 32);
-    Fr* d_pub = (Fr*)s->alloc(std::max(ch * np, (size_t)1) * 32);
-    Affine<Fp>* d_dig = (Affine<Fp>*)s->alloc(ch * 2 * 64);
-    XYZZ<Fp>* d_t = (XYZZ<Fp>*)s->alloc(ch * 10 * 128);
-    XYZZ<Fp>* d_A = (XYZZ<Fp>*)s->alloc(ch * 128);
-    XYZZ<Fp>* d_B = (XYZZ<Fp>*)s->alloc(ch * 128);
-    XYZZ<Fp>* d_fa = (XYZZ<Fp>*)s->alloc(ch * 128);
-    XYZZ<Fp>* d_fa2 = (XYZZ<Fp>*)s->alloc((ch + 1) / 2 * 128);
-    XYZZ<Fp>* d_fb = (XYZZ<Fp>*)s->alloc(ch * 128);
-    XYZZ<Fp>* d_fb2 = (XYZZ<Fp>*)s->alloc((ch + 1) / 2 * 128);
-    Fr* d_fix = (Fr*)s->alloc(ch * 3 * 32);
-    Fr* d_fold = (Fr*)s->alloc(ch * 3 * 32);
-    Fr* d_fold2 = (Fr*)s->alloc((ch + 1) / 2 * 3 * 32);
-    Affine<Fp>* d_p = (Affine<Fp>*)s->alloc(ch * 2 * 64);
-    F12* d_m = (F12*)s->alloc(ch * 2 * 384);
-    F12* d_ws = (F12*)s->alloc(ch * FE_SLOTS * 384);
-    F12* d_one_ws = (F12*)s->alloc(FE_SLOTS * 384);
-    Affine<Fp>* d_kpts = (Affine<Fp>*)s->alloc(9 * 64);
-    Affine<Fp2>* d_g2 = (Affine<Fp2>*)s->alloc(2 * 128);
-    uint32_t* d_mids = (uint32_t*)s->alloc(64);
-    uint8_t* d_hbytes = (uint8_t*)s->alloc(hbytes.size());
-    PvTerm* d_terms = (PvTerm*)s->alloc(21 * sizeof(PvTerm));
-    int* d_status = (int*)s->alloc(64);
-    uint8_t* d_chk = (uint8_t*)s->alloc(64);
-    if (!d_proofs || !d_praw || !d_pts || !d_bad || !d_hdr || !d_valid || !d_verdict || !d_sc || !d_pub || !d_dig || !d_t || !d_A || !d_B || !d_fa || !d_fa2 ||
-        !d_fb || !d_fb2 || !d_fix || !d_fold || !d_fold2 || !d_p || !d_m || !d_ws || !d_one_ws || !d_kpts || !d_g2 || !d_mids || !d_hbytes || !d_terms || !d_status ||
-        !d_chk)
-        return set_err(ZK_ERR_ARG, "plonk_verify_batch: workspace");
+    PairCheck pc(s, PK, ch);
+    uint32_t *d_proofs, *d_praw, *d_mids;
+    Affine<Fp> *d_pts, *d_dig, *d_p, *d_kpts;
+    uint8_t *d_bad, *d_hdr, *d_hbytes;
+    Fr *d_sc, *d_pub, *d_fix;
+    XYZZ<Fp> *d_t, *d_A, *d_B;
+    FoldPair<XYZZ<Fp>> fa, fb;
+    FoldPair<Fr> fold;
+    Affine<Fp2>* d_g2;
+    PvTerm* d_terms;
+    int* d_status;
+    ZK_TRY(plan_workspace(s, "plonk_verify_batch", [&](ArenaPlan& p) {
+        p.take(ch * (548 / 4), d_proofs);
+        p.take(ch * PV_NPTS * 8, d_praw);
+        p.take(ch * PV_NPTS, d_pts, d_bad);
+        p.take(ch * PV_NCOL, d_sc);
+        p.take(std::max(ch * np, (size_t)1), d_pub);
+        p.take(ch * 10, d_t);
+        p.take(ch * 3, d_fix);
+        p.take(ch * 2, d_dig, d_p);
+        p.take(ch, d_hdr, d_A, d_B);
+        fa.layout(p, ch);
+        fb.layout(p, ch);
+        fold.layout(p, ch, 3);
+        pc.layout(p, ch * 2);
+        p.take(9, d_kpts);
+        p.take(2, d_g2);
+        p.take(16, d_mids, d_status);
+        p.take(hbytes.size(), d_hbytes);
+        p.take(21, d_terms);
+    }));
+    uint8_t* const d_valid = pc.d_valid;
     ZK_HIP(hipMemcpyAsync(d_kpts, kp, sizeof kp, hipMemcpyHostToDevice, st));
     ZK_HIP(hipMemcpyAsync(d_g2, srs_g2, 2 * 128, hipMemcpyHostToDevice, st));
     ZK_HIP(hipMemcpyAsync(d_mids, mids, sizeof mids, hipMemcpyHostToDevice, st));
@@ -827,8 +860,6 @@ int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const vo
 
     std::vector<PvTerm> terms(21);
     size_t tn = 0;  // the table is rebuilt per chunk: its column pointers depend on the chunk's length
-    std::vector<uint8_t> valid(ch), one(1);
-    size_t total = 0;
     for (size_t c0 = 0; c0 < n_proofs; c0 += ch) {
         const size_t n = std::min(ch, n_proofs - c0);
         if (n != tn) {
@@ -867,25 +898,19 @@ int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const vo
         ZK_LAUNCH(s, st, "pv_digests", k_pv_digests, g64, dim3(64), 0, (const Affine<Fp>*)d_pts, (const XYZZ<Fp>*)d_t, (const Affine<Fp>*)d_kpts, n,
                   (const uint8_t*)d_valid, d_dig);
         ZK_LAUNCH(s, st, "pv_kzg", k_pv_kzg, g64, dim3(64), 0, (const Affine<Fp>*)d_pts, (const Affine<Fp>*)d_dig, (const Affine<Fp>*)d_kpts, n, c0, K,
-                  (const uint32_t*)(d_mids + 8), (const uint8_t*)(d_hbytes + tail_len + 13), (const uint8_t*)d_valid, d_sc, d_fix, d_fold);
+                  (const uint32_t*)(d_mids + 8), (const uint8_t*)(d_hbytes + tail_len + 13), (const uint8_t*)d_valid, d_sc, d_fix, fold.a);
         ZK_LAUNCH(s, st, "pv_smul", k_pv_smul, dim3(blocks(n, 64), 10), dim3(64), 0, (const PvTerm*)(d_terms + 8), n, (const uint8_t*)d_valid, d_t);
-        ZK_LAUNCH(s, st, "pv_combine", k_pv_combine, g256, dim3(256), 0, (const XYZZ<Fp>*)d_t, n, d_A, d_B, d_fa, d_fb);
-        const XYZZ<Fp>* a_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, d_fa, d_fa2, n, 1);
-        const XYZZ<Fp>* b_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, d_fb, d_fb2, n, 1);
-        const Fr* c_sum = fold_all(s, st, "fr_fold", k_fr_fold, 256, d_fold, d_fold2, n, 3);
+        ZK_LAUNCH(s, st, "pv_combine", k_pv_combine, g256, dim3(256), 0, (const XYZZ<Fp>*)d_t, n, d_A, d_B, fa.a, fb.a);
+        const XYZZ<Fp>* a_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, fa, n, 1);
+        const XYZZ<Fp>* b_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, fb, n, 1);
+        const Fr* c_sum = fold_all(s, st, "fr_fold", k_fr_fold, 256, fold, n, 3);
         XYZZ<HFp> sa, sb;
         HFr c[3];
         ZK_HIP(hipMemcpyAsync(&sa, a_sum, 128, hipMemcpyDeviceToHost, st));
         ZK_HIP(hipMemcpyAsync(&sb, b_sum, 128, hipMemcpyDeviceToHost, st));
         ZK_HIP(hipMemcpyAsync(c, c_sum, 3 * 32, hipMemcpyDeviceToHost, st));
-        ZK_HIP(hipMemcpyAsync(valid.data(), d_valid, n, hipMemcpyDeviceToHost, st));
-        ZK_TRY(slot_sync(s, st));
-        size_t n_valid = 0;
-        for (size_t i = 0; i < n; i++) n_valid += valid[i];
-        if (n_valid == 0) {
-            memset(accepted + c0, 0, n);
-            continue;
-        }
+        ZK_TRY(pc.sync_valid(n, accepted + c0));
+        if (pc.decided) continue;
         // e(sum A_i + c_G G + c_S1 S1 + c_S2 S2, [1]2) e(-sum B_i, [alpha]2) == 1 (the fixed points scaled here: three host multiplications per chunk)
         Affine<HFp> two[2];
         {
@@ -899,30 +924,15 @@ int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const vo
             two[1] = sb.to_affine().neg();
         }
         ZK_HIP(hipMemcpyAsync(d_p, two, 2 * 64, hipMemcpyHostToDevice, st));
-        ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(1), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_p, (size_t)2, (const Affine<Fp2>*)nullptr, (size_t)0,
-                  (const Affine<Fp2>*)d_g2, (size_t)1, PK, d_m);
-        const F12* prod = fold_all(s, st, "f12_fold", k_f12_fold, PAIR_BLOCK, d_m, d_ws, 2, 1);
-        ZK_HIP(hipMemsetAsync(d_chk, 1, 1, st));  // d_chk[0]: "valid", d_chk[1]: the verdict
-        ZK_TRY(final_exp(s, st, PK, prod, 1, 1, nullptr, d_one_ws, nullptr, d_chk, d_chk + 1));
-        ZK_HIP(hipMemcpyAsync(one.data(), d_chk + 1, 1, hipMemcpyDeviceToHost, st));
-        ZK_TRY(slot_sync(s, st));
-        if (one[0]) {
-            memcpy(accepted + c0, valid.data(), n);
-            total += n_valid;
-            continue;
-        }
+        ZK_TRY(pc.combined(d_p, 2, nullptr, 0, d_g2, n, accepted + c0));
+        if (pc.decided) continue;
         // fallback: each valid proof's own two-pairing check, with its own rho_i, rho'_i
         ZK_LAUNCH(s, st, "pv_smul", k_pv_smul, dim3(blocks(n, 64), 3), dim3(64), 0, (const PvTerm*)(d_terms + 18), n, (const uint8_t*)d_valid, d_t);
         ZK_LAUNCH(s, st, "pv_single", k_pv_single, g256, dim3(256), 0, (const XYZZ<Fp>*)d_A, (const XYZZ<Fp>*)d_B, (const XYZZ<Fp>*)d_t, n,
                   (const uint8_t*)d_valid, d_p);
-        ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(blocks(2 * n, PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_p, 2 * n,
-                  (const Affine<Fp2>*)nullptr, (size_t)0, (const Affine<Fp2>*)d_g2, n, PK, d_m);
-        ZK_TRY(final_exp(s, st, PK, d_m, n, 2, nullptr, d_ws, nullptr, d_valid, d_verdict));
-        ZK_HIP(hipMemcpyAsync(accepted + c0, d_verdict, n, hipMemcpyDeviceToHost, st));
-        ZK_TRY(slot_sync(s, st));
-        for (size_t i = 0; i < n; i++) total += accepted[c0 + i] ? 1 : 0;
+        ZK_TRY(pc.per_lane(d_p, n, 2, nullptr, 0, d_g2, false, accepted + c0));
     }
-    *n_accepted = total;
+    *n_accepted = pc.total;
     return ZK_OK;
 }
 
@@ -939,65 +949,44 @@ int zk_bn254_kzg_verify_batch(const zk_g1_affine* digests, const zk_kzg_opening*
     // lambda_i = the low 128 bits of SHA-256("zkmi-kzg-batch" || SHA-256(srs_g2) || SHA-256(digests || openings || points) || u64 i), forced non-zero
     uint8_t pre[14 + 32 + 32 + 8];
     memcpy(pre, "zkmi-kzg-batch", 14);
-    sha(srs_g2, 2 * sizeof(zk_g2_affine), pre + 14);
-    {
-        Sha256 h;
-        h.update(digests, n_openings * 64);
-        h.update(openings, n_openings * 96);
-        h.update(points, n_openings * 32);
-        h.final(pre + 46);
-    }
+    sha(pre + 14, srs_g2, 2 * sizeof(zk_g2_affine));
+    sha(pre + 46, digests, n_openings * 64, openings, n_openings * 96, points, n_openings * 32);
     SlotGuard g;
     ZK_TRY(acquire_slot(&g.s));
     Slot* s = g.s;
     hipStream_t st = s->stream;
     const size_t ch = std::min(n_openings, CHUNK);
-    const size_t per = 64 + 96 + 32 + 16 + 2 + 4 * 128 + 2 * 64 + 2 * 384 + FE_SLOTS * 384;
-    ZK_TRY(s->reserve(ch * per + 64 * 1024 + 4 * 384 + FE_SLOTS * 384));
-    Affine<Fp>* d_dig = (Affine<Fp>*)s->alloc(ch * 64);
-    KzgLane* d_op = (KzgLane*)s->alloc(ch * 96);
-    Fr* d_z = (Fr*)s->alloc(ch * 32);
-    uint32_t* d_rr = (uint32_t*)s->alloc(ch * 16);
-    uint8_t* d_valid = (uint8_t*)s->alloc(ch);
-    uint8_t* d_verdict = (uint8_t*)s->alloc(ch);
-    XYZZ<Fp>* d_fa = (XYZZ<Fp>*)s->alloc(ch * 128);
-    XYZZ<Fp>* d_fa2 = (XYZZ<Fp>*)s->alloc((ch + 1) / 2 * 128);
-    XYZZ<Fp>* d_fb = (XYZZ<Fp>*)s->alloc(ch * 128);
-    XYZZ<Fp>* d_fb2 = (XYZZ<Fp>*)s->alloc((ch + 1) / 2 * 128);
-    Affine<Fp>* d_p = (Affine<Fp>*)s->alloc(ch * 2 * 64);
-    Affine<Fp>* d_two = (Affine<Fp>*)s->alloc(2 * 64);
-    F12* d_m = (F12*)s->alloc(ch * 2 * 384);
-    F12* d_ws = (F12*)s->alloc(ch * FE_SLOTS * 384);
-    F12* d_one_ws = (F12*)s->alloc(FE_SLOTS * 384);
-    Affine<Fp2>* d_g2 = (Affine<Fp2>*)s->alloc(2 * 128);
-    uint8_t* d_chk = (uint8_t*)s->alloc(64);
-    if (!d_dig || !d_op || !d_z || !d_rr || !d_valid || !d_verdict || !d_fa || !d_fa2 || !d_fb || !d_fb2 || !d_p || !d_two || !d_m || !d_ws ||
-        !d_one_ws || !d_g2 || !d_chk)
-        return set_err(ZK_ERR_ARG, "kzg_verify_batch: workspace");
+    PairCheck pc(s, PK, ch);
+    Affine<Fp> *d_dig, *d_p, *d_two;
+    KzgLane* d_op;
+    Fr* d_z;
+    uint32_t* d_rr;
+    FoldPair<XYZZ<Fp>> fa, fb;
+    Affine<Fp2>* d_g2;
+    ZK_TRY(plan_workspace(s, "kzg_verify_batch", [&](ArenaPlan& p) {
+        p.take(ch, d_dig, d_op, d_z);
+        p.take(ch * 4, d_rr);
+        fa.layout(p, ch);
+        fb.layout(p, ch);
+        p.take(ch * 2, d_p);
+        p.take(2, d_two, d_g2);
+        pc.layout(p, ch * 2);
+    }));
     ZK_HIP(hipMemcpyAsync(d_g2, srs_g2, 2 * 128, hipMemcpyHostToDevice, st));
-    ZK_HIP(hipMemsetAsync(d_valid, 1, ch, st));  // the points are not validated: every lane takes part
+    ZK_HIP(hipMemsetAsync(pc.d_valid, 1, ch, st));  // the points are not validated: every lane takes part
+    std::fill(pc.valid.begin(), pc.valid.end(), 1);
     std::vector<uint32_t> rr(ch * 4);
-    std::vector<uint8_t> one(1);
-    size_t total = 0;
     for (size_t c0 = 0; c0 < n_openings; c0 += ch) {
         const size_t n = std::min(ch, n_openings - c0);
-        for (size_t i = 0; i < n; i++) {
-            const uint64_t idx = c0 + i;
-            for (int b = 0; b < 8; b++) pre[78 + b] = (uint8_t)(idx >> (8 * b));
-            uint8_t d[32];
-            sha(pre, sizeof pre, d);
-            uint32_t* r = &rr[4 * i];  // the low 128 bits of the digest read as a big-endian integer
-            for (int w = 0; w < 4; w++) r[w] = ((uint32_t)d[28 - 4 * w] << 24) | ((uint32_t)d[29 - 4 * w] << 16) | ((uint32_t)d[30 - 4 * w] << 8) | d[31 - 4 * w];
-            if ((r[0] | r[1] | r[2] | r[3]) == 0) r[0] = 1;
-        }
+        batch_coeffs(pre, sizeof pre, 78, c0, n, rr.data());
         ZK_HIP(hipMemcpyAsync(d_dig, digests + c0, n * 64, hipMemcpyHostToDevice, st));
         ZK_HIP(hipMemcpyAsync(d_op, openings + c0, n * 96, hipMemcpyHostToDevice, st));
         ZK_HIP(hipMemcpyAsync(d_z, points + c0, n * 32, hipMemcpyHostToDevice, st));
         ZK_HIP(hipMemcpyAsync(d_rr, rr.data(), n * 16, hipMemcpyHostToDevice, st));
         ZK_LAUNCH(s, st, "kzg_combine", k_kzg_combine, dim3(blocks(n, 64)), dim3(64), 0, (const Affine<Fp>*)d_dig, (const KzgLane*)d_op, (const Fr*)d_z,
-                  (const uint32_t*)d_rr, n, G, d_fa, d_fb, d_p);
-        const XYZZ<Fp>* a_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, d_fa, d_fa2, n, 1);
-        const XYZZ<Fp>* b_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, d_fb, d_fb2, n, 1);
+                  (const uint32_t*)d_rr, n, G, fa.a, fb.a, d_p);
+        const XYZZ<Fp>* a_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, fa, n, 1);
+        const XYZZ<Fp>* b_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, fb, n, 1);
         XYZZ<HFp> sa, sb;
         ZK_HIP(hipMemcpyAsync(&sa, a_sum, 128, hipMemcpyDeviceToHost, st));
         ZK_HIP(hipMemcpyAsync(&sb, b_sum, 128, hipMemcpyDeviceToHost, st));
@@ -1005,27 +994,12 @@ int zk_bn254_kzg_verify_batch(const zk_g1_affine* digests, const zk_kzg_opening*
         // e(sum_i lambda_i (C_i - v_i G + z_i H_i), [1]2) e(-sum_i lambda_i H_i, [alpha]2) == 1: two Miller loops whatever n is
         const Affine<HFp> two[2] = {sa.to_affine(), sb.to_affine().neg()};
         ZK_HIP(hipMemcpyAsync(d_two, two, 2 * 64, hipMemcpyHostToDevice, st));
-        ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(1), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_two, (size_t)2, (const Affine<Fp2>*)nullptr, (size_t)0,
-                  (const Affine<Fp2>*)d_g2, (size_t)1, PK, d_m);
-        const F12* prod = fold_all(s, st, "f12_fold", k_f12_fold, PAIR_BLOCK, d_m, d_ws, 2, 1);
-        ZK_HIP(hipMemsetAsync(d_chk, 1, 1, st));  // d_chk[0]: "valid", d_chk[1]: the verdict
-        ZK_TRY(final_exp(s, st, PK, prod, 1, 1, nullptr, d_one_ws, nullptr, d_chk, d_chk + 1));
-        ZK_HIP(hipMemcpyAsync(one.data(), d_chk + 1, 1, hipMemcpyDeviceToHost, st));
-        ZK_TRY(slot_sync(s, st));
-        if (one[0]) {
-            memset(accepted + c0, 1, n);
-            total += n;
-            continue;
-        }
-        // fallback: each opening's own two-pairing check e(T_i, [1]2) e(-H_i, [alpha]2) == 1
-        ZK_LAUNCH(s, st, "miller_loop", k_miller, dim3(blocks(2 * n, PAIR_BLOCK)), dim3(PAIR_BLOCK), 0, (const Affine<Fp>*)d_p, 2 * n,
-                  (const Affine<Fp2>*)nullptr, (size_t)0, (const Affine<Fp2>*)d_g2, n, PK, d_m);
-        ZK_TRY(final_exp(s, st, PK, d_m, n, 2, nullptr, d_ws, nullptr, d_valid, d_verdict));
-        ZK_HIP(hipMemcpyAsync(accepted + c0, d_verdict, n, hipMemcpyDeviceToHost, st));
-        ZK_TRY(slot_sync(s, st));
-        for (size_t i = 0; i < n; i++) total += accepted[c0 + i] ? 1 : 0;
+        ZK_TRY(pc.combined(d_two, 2, nullptr, 0, d_g2, n, accepted + c0));
+        if (pc.decided) continue;
+        // fallback: each opening's own two-pairing check e(T_i, [1]2) e(-H_i, [alpha]2) == 1 (k_kzg_combine left the pairs in d_p)
+        ZK_TRY(pc.per_lane(d_p, n, 2, nullptr, 0, d_g2, false, accepted + c0));
     }
-    *n_accepted = total;
+    *n_accepted = pc.total;
     return ZK_OK;
 }
 

@@ -78,6 +78,34 @@ def test_golden_proofs_in_batches():
         assert not got[0] and got[0] == _host_verdicts([it0[0][0]], vk1, [it0[0][1]])[0]
 
 
+def test_chunk_boundary():
+    """2^16 + 3 proofs (the golden proofs of one key, tiled): two chunks, the second one three proofs long, and a bad proof in the second chunk only --
+    the first chunk is decided by its combined check, the second one proof by proof; every chunk decompresses its own G2 points in the same scratch"""
+    vk, items = _golden()["seq_r1cs_13"]
+    base, bpubs = [p for p, _ in items], np.stack([w for _, w in items])
+    bad = bytearray(base[0])
+    bad[96] ^= 0x40                                      # -Krs: still a valid encoding, a rejected proof
+    distinct = base + [bytes(bad)]
+    dpubs = np.concatenate([bpubs, bpubs[:1]])
+    host = _host_verdicts(distinct, vk, dpubs)
+    assert list(host) == [True] * len(base) + [False]
+    n = (1 << 16) + 3
+    idx = np.arange(n) % len(base)
+    idx[(1 << 16) + 1] = len(base)
+    ps = b"".join(distinct[i] for i in idx)
+    ws = dpubs[idx]
+    _lib.profile(True)
+    _lib.profile_reset()
+    try:
+        got = zv.groth16_verify_batch(ps, vk, ws)
+        prof = _lib.profile_read()
+    finally:
+        _lib.profile(False)
+    assert (got == host[idx]).all()
+    assert prof["vb_prep"][0] == 2 and prof["vb_single"][0] == 1 and prof["miller_loop"][0] == 3 and prof["fe_easy"][0] == 3
+    assert (zv.groth16_verify_batch(ps, vk, ws) == got).all()
+
+
 def _fresh(n_proofs, npub, seed):
     """n_proofs distinct proofs of one small random R1CS (256 constraints), each with its own witness and (r, s), made on the GPU."""
     g = ref.SplitMix64(seed)
