@@ -293,6 +293,20 @@ int zk_bn254_groth16_setup(uint64_t r1cs_handle, const zk_fr toxic[5], int flags
 /* groth16.Prove from the witness: a, b, c by the device solver step above, then zk_bn254_groth16_prove on resident data. */
 int zk_bn254_groth16_prove_r1cs(uint64_t r1cs_handle, uint64_t pk_handle, const void *w, size_t n_wires, const zk_fr *r,
                                 const zk_fr *s, int on_device, uint8_t proof_out[128]);
+/* Many witnesses against ONE key in one call.  a, b, c: row-major n_proofs x n_constraints; w: row-major n_proofs x n_wires; r, s: n_proofs elements each
+ * (all Montgomery fr.Element; on_device != 0: a, b, c, w are device pointers, only read).  proofs_out[128 i .. 128 i + 128) is byte for byte what
+ * zk_bn254_groth16_prove / zk_bn254_groth16_prove_r1cs writes for row i with r[i], s[i] -- whichever path the call takes: a single-device key with its window
+ * tables and log_domain <= 16 is served by a batched path (the rows of a chunk share one scalar preparation, one accumulate launch per base array and one
+ * reduction; csrc/groth16_batch.hip), every other key row by row by the single prover.  n_proofs == 0: ZK_OK, nothing written.  Errors are the single prover's
+ * (ZK_ERR_ARG null pointer / n_constraints above the domain, ZK_ERR_LEN len(w), ZK_ERR_HANDLE), checked before the device is touched where they can be; on any
+ * error proofs_out is unspecified. */
+int zk_bn254_groth16_prove_batch(uint64_t pk_handle, const void *a, const void *b, const void *c, size_t n_constraints, const void *w,
+                                 size_t n_wires, const zk_fr *r, const zk_fr *s, size_t n_proofs, int on_device, uint8_t *proofs_out);
+int zk_bn254_groth16_prove_r1cs_batch(uint64_t r1cs_handle, uint64_t pk_handle, const void *w, size_t n_wires, const zk_fr *r,
+                                      const zk_fr *s, size_t n_proofs, int on_device, uint8_t *proofs_out);
+/* Rows per chunk of the batched path for this key (a function of its geometry and the call's 1 GiB workspace), and whether the batched path serves the key at
+ * all (*batched = 0: rows go through the single prover, *chunk_rows = 1).  Either out pointer may be NULL. */
+int zk_bn254_groth16_batch_info(uint64_t pk_handle, size_t *chunk_rows, int *batched);
 
 /* ---- Groth16 key wire formats (gnark v0.8.0 groth16 marshal.go): what the reference's intended Groth16 FFI moves as hex --
  * ProveWithPK(rawR1CS, encodedProvingKey) -> provingKey.ReadFrom at gnark_backend_ffi/backend/groth16/r1cs.go:107-143; Preprocess -> both keys at

@@ -162,6 +162,20 @@ inline Error Prove(const ProvingKey& pk, const fr::Vector& a, const fr::Vector& 
     if (w.size() != pk.NbWires()) return Error{ZK_ERR_LEN, "len(w) != number of wires of the proving key"};
     return make_error(zk_bn254_groth16_prove(pk.handle(), a.data(), b.data(), c.data(), a.size(), w.data(), w.size(), &r, &s, 0, proof->bytes));
 }
+// The same for many witnesses against one key in one call: a, b, c hold len(r) rows of n_constraints elements, w len(r) rows of NbWires(); proofs[i] is byte
+// for byte what Prove writes for row i with r[i], s[i].
+inline Error ProveBatch(const ProvingKey& pk, const fr::Vector& a, const fr::Vector& b, const fr::Vector& c, size_t n_constraints, const fr::Vector& w,
+                        const fr::Vector& r, const fr::Vector& s, std::vector<Proof>* proofs) {
+    const size_t n = r.size();
+    if (s.size() != n) return Error{ZK_ERR_LEN, "len(r) != len(s)"};
+    if (a.size() != n * n_constraints || b.size() != a.size() || c.size() != a.size()) return Error{ZK_ERR_LEN, "a, b, c must hold len(r) rows of n_constraints"};
+    if (n_constraints > pk.DomainCardinality()) return Error{ZK_ERR_LEN, "n_constraints exceeds the domain cardinality"};
+    if (w.size() != n * pk.NbWires()) return Error{ZK_ERR_LEN, "w must hold len(r) rows of the proving key's wires"};
+    proofs->resize(n);
+    static_assert(sizeof(Proof) == 128, "proofs are written back to back");
+    return make_error(zk_bn254_groth16_prove_batch(pk.handle(), a.data(), b.data(), c.data(), n_constraints, w.data(), pk.NbWires(), r.data(), s.data(), n, 0,
+                                                   n ? (*proofs)[0].bytes : nullptr));
+}
 
 }  // namespace groth16
 

@@ -20,6 +20,7 @@
 
 #include "ctx.hpp"
 #include "curve.hpp"
+#include "groth16_batch.hpp"
 #include "host_ff.hpp"
 #include "keyio.hpp"
 #include "msm.hpp"
@@ -374,6 +375,19 @@ int groth16_pk_view(uint64_t handle, Groth16View* v) {
     v->alpha = P.alpha; v->beta = P.beta; v->delta = P.delta;
     v->beta2 = P.beta2; v->delta2 = P.delta2;
     v->d_a = P.d_a; v->d_b = P.d_b; v->d_k = P.d_k; v->d_z = P.d_z; v->d_b2 = P.d_b2;
+    return ZK_OK;
+}
+// what the batch prover (groth16_batch.hip) needs of a key: its geometry and, when it has them, its window tables
+int groth16_pk_batch_view(uint64_t handle, Groth16BatchView* v) {
+    std::lock_guard<std::mutex> lk(g_pk_mu);
+    auto it = g_pks.find(handle);
+    if (it == g_pks.end()) return set_err(ZK_ERR_HANDLE, "unknown proving-key handle %llu", (unsigned long long)handle);
+    const Groth16PK& P = it->second;
+    v->log_domain = P.log_domain;
+    v->n_wires = P.n_wires; v->n_public = P.n_public; v->nz = P.nz;
+    v->tables = P.tables;
+    v->tab_w = P.tab_w; v->tab_h = P.tab_h;
+    v->t_a = P.t_a; v->t_b = P.t_b; v->t_k = P.t_k; v->t_z = P.t_z; v->t_b2 = P.t_b2;
     return ZK_OK;
 }
 }  // namespace zkmi

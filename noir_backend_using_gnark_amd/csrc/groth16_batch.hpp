@@ -1,0 +1,24 @@
+// Internal interface between the batch Groth16 prover (groth16_batch.hip) and the modules that own the resident objects it reads.
+#pragma once
+#include "ctx.hpp"
+#include "ff.hpp"
+#include "msm.hpp"
+
+namespace zkmi {
+
+// a loaded proving key as the batch prover sees it (groth16.hip); the table pointers stay the key's
+struct Groth16BatchView {
+    uint32_t log_domain;
+    size_t n_wires, n_public, nz;
+    bool tables;
+    MsmTable tab_w, tab_h;
+    const void *t_a, *t_b, *t_k, *t_z, *t_b2;
+};
+int groth16_pk_batch_view(uint64_t handle, Groth16BatchView* v);
+
+// r1cs.hip: the dimensions of a resident constraint system, and a, b, c = L w, R w, O w for `rows` wire vectors in one launch -- row i reads d_w + i * n_wires
+// and writes n_constraints elements at d_a / d_b / d_c + i * out_stride
+int r1cs_dims(uint64_t handle, size_t* n_constraints, size_t* n_wires);
+int r1cs_eval_abc_rows(uint64_t handle, Slot* s, hipStream_t st, const Fr* d_w, size_t rows, size_t out_stride, Fr* d_a, Fr* d_b, Fr* d_c);
+
+}  // namespace zkmi

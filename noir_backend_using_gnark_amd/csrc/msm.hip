@@ -141,14 +141,23 @@ __device__ __forceinline__ T shfl_xor_t(const T& v, unsigned d) {
 // plan and ONE accumulate launch serve all of them and the reduction yields one sum per vector.
 struct DigitSrc {
     const Fr* p[3];
+    __device__ __forceinline__ const Fr* vec(unsigned v) const { return p[v]; }
 };
-__global__ void k_msm_digits(DigitSrc src, uint32_t n, int mont, unsigned c, unsigned W, uint32_t* keys, uint32_t* vals,
+// The same for ANY number of vectors that are the rows of one matrix (a batch of Groth16 witnesses: row v = base + v * stride): the kernels below are
+// instantiated once per source type, so the three-pointer form PLONK launches is the code it always was.
+struct DigitRows {
+    const Fr* base;
+    size_t stride;  // elements between rows
+    __device__ __forceinline__ const Fr* vec(unsigned v) const { return base + (size_t)v * stride; }
+};
+template <class Src>
+__global__ void k_msm_digits(Src src, uint32_t n, int mont, unsigned c, unsigned W, uint32_t* keys, uint32_t* vals,
                              uint32_t table_stride, unsigned row_first, unsigned row_step, unsigned rows_per_set) {
     prio_hi();
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const unsigned vec = blockIdx.y, sets = gridDim.y;
-    const Fr* scalars = src.p[vec];
+    const Fr* scalars = src.vec(vec);
     Fr s;
     {
         const uint4* q = reinterpret_cast<const uint4*>(scalars + i);
@@ -241,7 +250,8 @@ __device__ __forceinline__ void digits_of(const Fr& s, unsigned c, unsigned W, b
 // memory -- 52-byte strides between lanes -- still +0.14 ms; staged through LDS but with the scalar read and converted twice +0.1 ms; this form -- read and
 // converted once, recoded twice, staged -- costs a uniform vector nothing (9.67-9.73 against 9.75 ms on one box) and a witness-like one 0.3-0.4 ms less:
 // profiles/rnd5_d_*, rnd5_e_*, rnd5_f_*, rnd5_g_*.)  Dynamic LDS: 256 * W pairs of 8 bytes.
-__global__ __launch_bounds__(256) void k_msm_digits_compact(DigitSrc src, uint32_t n, int mont, unsigned c, unsigned W, unsigned row_first, unsigned row_step,
+template <class Src>
+__global__ __launch_bounds__(256) void k_msm_digits_compact(Src src, uint32_t n, int mont, unsigned c, unsigned W, unsigned row_first, unsigned row_step,
                                                            uint32_t table_stride, uint32_t* __restrict__ total, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
     prio_hi();
     extern __shared__ uint32_t stage[];  // [0, 256 W): keys, [256 W, 512 W): values
@@ -254,7 +264,7 @@ __global__ __launch_bounds__(256) void k_msm_digits_compact(DigitSrc src, uint32
     uint32_t k = 0;
     Fr sc = Fr::zero();
     if (live) {
-        sc = canonical_scalar(src.p[vec], i, mont);  // read and converted once; recoded twice (count, then write)
+        sc = canonical_scalar(src.vec(vec), i, mont);  // read and converted once; recoded twice (count, then write)
         digits_of(sc, c, W, table_stride != 0, row_first, row_step, [&](unsigned, uint32_t mag, uint32_t) { k += mag != 0; });
     }
     // exclusive scan of k over the workgroup: inside the wave by shuffles, across the four waves through LDS
@@ -994,7 +1004,7 @@ static int msm_plan_uncached(size_t n, const zk_msm_cfg* cfg, hipStream_t st, Ms
     typedef XYZZ<F> Pt;
     memset(P, 0, sizeof *P);
     if (n == 0) return ZK_OK;
-    if (sets < 1 || sets > 3 || (sets > 1 && !tab)) return set_err(ZK_ERR_ARG, "a batch of %u scalar vectors needs a window table and at most three vectors", sets);
+    if (sets < 1 || sets > MSM_MAX_SETS || (sets > 1 && !tab)) return set_err(ZK_ERR_ARG, "a batch of %u scalar vectors needs a window table and at most %u vectors", sets, MSM_MAX_SETS);
     if (n > ((size_t)1 << 27)) return set_err(ZK_ERR_ARG, "n = %zu exceeds the per-call limit 2^27 (shard the MSM)", n);
     unsigned c = tab ? tab->c : ((cfg && cfg->window_bits) ? (unsigned)cfg->window_bits : msm_pick_window(n));
     // plain method: c <= 22 (one bucket set PER WINDOW: 12 x 2^21 partial sums already); against a window table all windows share one bucket set and c = 23, 24
@@ -1009,6 +1019,7 @@ static int msm_plan_uncached(size_t n, const zk_msm_cfg* cfg, hipStream_t st, Ms
     if (tab && P->Wrows == 0) { memset(P, 0, sizeof *P); return ZK_OK; }  // this rank owns no window: the MSM is empty
     P->table_stride = tab ? (uint32_t)tab->stride : 0;
     P->B = 1u << (c - 1);
+    if ((uint64_t)P->W << (c - 1) >= ((uint64_t)1 << 30)) return set_err(ZK_ERR_ARG, "%u bucket sets of 2^%u buckets overflow the sort keys", P->W, c - 1);
     P->nb = P->W * P->B;
     P->total = n * P->Wrows * (tab ? sets : 1);
     if (P->total >= ((size_t)1 << 31)) return set_err(ZK_ERR_ARG, "n * windows = %zu overflows 31-bit positions", P->total);
@@ -1065,7 +1076,7 @@ static int msm_plan_uncached(size_t n, const zk_msm_cfg* cfg, hipStream_t st, Ms
 // Scalar-side half of an MSM on stream `st`: digits, sort, bucket bounds, task plan.  The result only depends on the
 // scalars, so several MSMs over the same scalar vector (Groth16: A, B1, K and G2.B all pair with the wire values) share it.
 static int msm_prepare(Slot* s, hipStream_t st, const MsmPlan& P, const Fr* d_scalars, size_t n, const zk_msm_cfg* cfg, MsmPrep* out, const DigitSrc* batch = nullptr,
-                       bool drop_zero_digits = false) {
+                       bool drop_zero_digits = false, const DigitRows* rows = nullptr) {
     out->P = P;
     out->n = n;
     out->empty = (n == 0) || P.total == 0;  // no points, or a window-sharded table of which this rank owns no row
@@ -1111,11 +1122,16 @@ static int msm_prepare(Slot* s, hipStream_t st, const MsmPlan& P, const Fr* d_sc
             uint32_t* cnt = (uint32_t*)s->alloc(256);
             if (!cnt) return set_err(ZK_ERR_HIP, "MSM workspace was not reserved up front (zero-digit compaction)");
             ZK_HIP(hipMemsetAsync(cnt, 0, 4, st));
-            ZK_LAUNCH(s, st, "msm_digits", k_msm_digits_compact, grid, dim3(256), 256u * P.Wd * 8u, src, (uint32_t)n, mont, c, P.Wd, P.row_first, P.row_step, P.table_stride, cnt,
-                      keys0, vals0);
+            if (rows) ZK_LAUNCH(s, st, "msm_digits", (k_msm_digits_compact<DigitRows>), grid, dim3(256), 256u * P.Wd * 8u, *rows, (uint32_t)n, mont, c, P.Wd, P.row_first, P.row_step,
+                                P.table_stride, cnt, keys0, vals0);
+            else ZK_LAUNCH(s, st, "msm_digits", (k_msm_digits_compact<DigitSrc>), grid, dim3(256), 256u * P.Wd * 8u, src, (uint32_t)n, mont, c, P.Wd, P.row_first, P.row_step, P.table_stride, cnt,
+                           keys0, vals0);
             d_total = cnt;  // the number of pairs, where the kernels below read it
+        } else if (rows) {
+            ZK_LAUNCH(s, st, "msm_digits", (k_msm_digits<DigitRows>), grid, dim3(256), 0, *rows, (uint32_t)n, mont, c, P.Wd, keys0, vals0, P.table_stride, P.row_first, P.row_step,
+                      P.Wrows);
         } else {
-            ZK_LAUNCH(s, st, "msm_digits", k_msm_digits, grid, dim3(256), 0, src, (uint32_t)n, mont, c, P.Wd, keys0, vals0, P.table_stride, P.row_first, P.row_step,
+            ZK_LAUNCH(s, st, "msm_digits", (k_msm_digits<DigitSrc>), grid, dim3(256), 0, src, (uint32_t)n, mont, c, P.Wd, keys0, vals0, P.table_stride, P.row_first, P.row_step,
                       P.Wrows);
         }
     }
@@ -1470,6 +1486,24 @@ int msm_prepare_scalars_table_batch(Slot* s, hipStream_t st, const void* const* 
     for (unsigned v = 0; v < sets; v++) src.p[v] = (const Fr*)d_scalars[v];
     return msm_prepare(s, st, P, src.p[0], n, cfg, out, &src, drop_zero_digits);
 }
+// `sets` scalar vectors that are the rows of one matrix (row v = d_base + v * row_stride elements; n elements of each are used) against one window table, G1 or G2:
+// one recoding, one sort, one task plan; every accumulate over the result fills `sets` bucket sets and its reduction yields one sum per row (msm_*_finish_sets).
+int msm_prep_need_table_rows(size_t n, unsigned sets, const MsmTable& tab, hipStream_t st, size_t* need_prep, size_t* need_acc_g1, size_t* need_acc_g2) {
+    MsmPlan P1, P2;
+    ZK_TRY(msm_plan<Fp>(n, nullptr, st, &P1, &tab, sets));
+    ZK_TRY(msm_plan<Fp2>(n, nullptr, st, &P2, &tab, sets));
+    if (need_prep) *need_prep = P1.need_prep;
+    if (need_acc_g1) *need_acc_g1 = P1.need_acc;
+    if (need_acc_g2) *need_acc_g2 = P2.need_acc;
+    return ZK_OK;
+}
+int msm_prepare_scalars_table_rows(Slot* s, hipStream_t st, const void* d_base, size_t row_stride, unsigned sets, size_t n, const zk_msm_cfg* cfg, const MsmTable& tab,
+                                   MsmPrep* out, bool drop_zero_digits) {
+    MsmPlan P;
+    ZK_TRY(msm_plan<Fp>(n, cfg, st, &P, &tab, sets));
+    const DigitRows rows = {(const Fr*)d_base, row_stride};
+    return msm_prepare(s, st, P, rows.base, n, cfg, out, nullptr, drop_zero_digits, &rows);
+}
 int msm_prepare_scalars_table(Slot* s, hipStream_t st, const void* d_scalars, size_t n, const zk_msm_cfg* cfg, const MsmTable& tab, MsmPrep* out, bool drop_zero_digits) {
     MsmPlan P;
     ZK_TRY(msm_plan<Fp>(n, cfg, st, &P, &tab));
@@ -1626,6 +1660,19 @@ int msm_g1_finish_batch(const MsmJob& job, XYZZ<HFp> out[3]) {
     return msm_finish<HFp>(job, &unused, out);
 }
 int msm_g2_finish(const MsmJob& job, XYZZ<HFp2>* out) { return msm_finish<HFp2>(job, out); }
+// one sum per bucket set of a job over msm_prepare_scalars_table_rows (`sets` of them, at least three entries in `out`)
+int msm_g1_finish_sets(const MsmJob& job, XYZZ<HFp>* out, unsigned sets) {
+    XYZZ<HFp> unused;
+    for (unsigned k = 0; k < sets; k++) out[k] = XYZZ<HFp>::inf();
+    if (!job.empty && job.W != sets) return set_err(ZK_ERR_ARG, "the job holds %u bucket sets, not %u", job.W, sets);
+    return msm_finish<HFp>(job, &unused, out);
+}
+int msm_g2_finish_sets(const MsmJob& job, XYZZ<HFp2>* out, unsigned sets) {
+    XYZZ<HFp2> unused;
+    for (unsigned k = 0; k < sets; k++) out[k] = XYZZ<HFp2>::inf();
+    if (!job.empty && job.W != sets) return set_err(ZK_ERR_ARG, "the job holds %u bucket sets, not %u", job.W, sets);
+    return msm_finish<HFp2>(job, &unused, out);
+}
 int msm_g1_xyzz(Slot* s, hipStream_t st, const void* d_pts, const void* d_scalars, size_t n, const zk_msm_cfg* cfg, XYZZ<HFp>* out) {
     MsmJob job;
     ZK_TRY(msm_g1_launch(s, st, d_pts, d_scalars, n, cfg, &job));

@@ -90,6 +90,14 @@ int msm_prepare_scalars_table(Slot* s, hipStream_t st, const void* d_scalars, si
 int msm_prep_need_table_batch(size_t n, unsigned sets, const MsmTable& tab, hipStream_t st, size_t* need_prep, size_t* need_acc_g1);
 int msm_prepare_scalars_table_batch(Slot* s, hipStream_t st, const void* const* d_scalars, unsigned sets, size_t n, const zk_msm_cfg* cfg, const MsmTable& tab, MsmPrep* out,
                                     bool drop_zero_digits = false);
+// any number of vectors (up to MSM_MAX_SETS) that are the rows of one matrix -- row v = d_base + v * row_stride elements -- against one table, G1 or G2 (a batch of
+// Groth16 witnesses): the prepared scalars serve msm_g1_accumulate / msm_g2_accumulate as usual; msm_*_finish_sets returns one sum per row
+static constexpr unsigned MSM_MAX_SETS = 1024;
+int msm_prep_need_table_rows(size_t n, unsigned sets, const MsmTable& tab, hipStream_t st, size_t* need_prep, size_t* need_acc_g1, size_t* need_acc_g2);
+int msm_prepare_scalars_table_rows(Slot* s, hipStream_t st, const void* d_base, size_t row_stride, unsigned sets, size_t n, const zk_msm_cfg* cfg, const MsmTable& tab,
+                                   MsmPrep* out, bool drop_zero_digits = false);
+int msm_g1_finish_sets(const MsmJob& job, XYZZ<HFp>* out, unsigned sets);
+int msm_g2_finish_sets(const MsmJob& job, XYZZ<HFp2>* out, unsigned sets);
 size_t msm_compact_need(size_t n, unsigned sets);
 // zk_bn254_msm_bases_batch_dev for scalars known to be mostly small (wire values): zero digits dropped before the sort
 int msm_bases_batch_dev_sparse(uint64_t handle, size_t offset, const void* const* d_scalars, unsigned count, size_t n, const zk_msm_cfg* cfg, void* out);

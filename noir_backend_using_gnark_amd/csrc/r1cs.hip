@@ -23,6 +23,7 @@
 #include "curve.hpp"
 #include "ff.hpp"
 #include "fixedbase.hpp"
+#include "groth16_batch.hpp"
 #include "host_ff.hpp"
 #include "ntt.hpp"
 
@@ -101,6 +102,20 @@ __global__ __launch_bounds__(256) void k_spmv3(Csr3 M, const Fr* __restrict__ x,
     Fr acc = Fr::zero();
     for (uint32_t k = b; k < e; k++) acc = acc + ldf(M.val[m] + k) * ldf(x + M.idx[m][k]);
     (m == 0 ? out0 : m == 1 ? out1 : out2)[i] = acc;
+}
+// The same product for a batch of wire vectors (the rows of a matrix, x_stride elements apart): blockIdx.z is the vector, its three results go to out{0,1,2} +
+// z * out_stride.  By constraint only -- rows of a handful of terms -- so no long-row list.  One launch instead of one per witness: at 2^12 constraints a single
+// product is 48 workgroups on 256 CUs.
+__global__ __launch_bounds__(256) void k_spmv3_rows(Csr3 M, const Fr* __restrict__ x, size_t x_stride, size_t rows, size_t out_stride, Fr* __restrict__ out0, Fr* __restrict__ out1,
+                                                    Fr* __restrict__ out2) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int m = blockIdx.y;
+    if (i >= rows) return;
+    const Fr* __restrict__ xv = x + (size_t)blockIdx.z * x_stride;
+    const uint32_t b = M.ptr[m][i], e = M.ptr[m][i + 1];
+    Fr acc = Fr::zero();
+    for (uint32_t k = b; k < e; k++) acc = acc + ldf(M.val[m] + k) * ldf(xv + M.idx[m][k]);
+    (m == 0 ? out0 : m == 1 ? out1 : out2)[(size_t)blockIdx.z * out_stride + i] = acc;
 }
 // one workgroup per listed row: 256 partial sums over strided entries, folded through LDS
 __global__ __launch_bounds__(256) void k_spmv3_long(Csr3 M, const Fr* __restrict__ x, Fr* __restrict__ out0, Fr* __restrict__ out1, Fr* __restrict__ out2,
@@ -226,6 +241,25 @@ static int lookup_r1cs(uint64_t h, std::shared_ptr<R1csDev>* out) {
 }
 
 int groth16_pk_adopt(uint64_t handle);  // groth16.hip: the key takes ownership of its device arrays
+
+int r1cs_dims(uint64_t handle, size_t* n_constraints, size_t* n_wires) {
+    std::shared_ptr<R1csDev> D;
+    ZK_TRY(lookup_r1cs(handle, &D));
+    *n_constraints = D->n_constraints;
+    *n_wires = D->n_wires;
+    return ZK_OK;
+}
+int r1cs_eval_abc_rows(uint64_t handle, Slot* s, hipStream_t st, const Fr* d_w, size_t rows, size_t out_stride, Fr* d_a, Fr* d_b, Fr* d_c) {
+    std::shared_ptr<R1csDev> D;
+    ZK_TRY(lookup_r1cs(handle, &D));
+    if (!D->n_constraints || !rows) return ZK_OK;
+    if (rows > 65535) return set_err(ZK_ERR_ARG, "r1cs: %zu wire vectors in one launch", rows);
+    Csr3 M;
+    for (int m = 0; m < 3; m++) { M.ptr[m] = D->row[m].ptr; M.idx[m] = D->row[m].idx; M.val[m] = D->row[m].val; }
+    ZK_LAUNCH(s, st, "r1cs_spmv_rows", k_spmv3_rows, dim3(gridn(D->n_constraints), 3, (unsigned)rows), dim3(256), 0, M, d_w, D->n_wires, D->n_constraints, out_stride, d_a, d_b, d_c);
+    // (the launch holds the matrices' pointers: the caller keeps the system alive until its stream has drained -- it synchronises before it returns)
+    return ZK_OK;
+}
 
 // the by-wire (CSC) form of the three matrices, built once, on the device, when a Setup asks for it
 static int ensure_csc(R1csDev* D, Slot* s, hipStream_t st) {

@@ -236,3 +236,70 @@ def prove_r1cs(r1cs: R1CS, pk: ProvingKey, w, r, s) -> bytes:
         raise ValueError((lib().zk_last_error() or b"").decode())
     check(rc)
     return bytes(proof)
+
+
+def _rs_rows(r, s, n: int):
+    r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+    s = np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4)
+    if r.shape[0] != n or s.shape[0] != n:
+        raise ValueError("r and s need one element per row of w (%d): got %d and %d" % (n, r.shape[0], s.shape[0]))
+    return r, s
+
+
+def _rows(v, what: str) -> np.ndarray:
+    v = np.ascontiguousarray(v, dtype=np.uint64)
+    if v.ndim == 2 and v.shape[1] == 4:
+        raise ValueError("%s must be a matrix of limbs (rows, elements, 4), one row per proof" % what)
+    if v.ndim != 3 or v.shape[2] != 4:
+        raise ValueError("%s must have the shape (rows, elements, 4)" % what)
+    return v
+
+
+def batch_info(pk: ProvingKey) -> dict:
+    """rows per chunk of the batched path for this key, and whether the batched path serves it (else prove_batch runs the rows through prove)"""
+    rows, batched = C.c_size_t(0), C.c_int(0)
+    check(lib().zk_bn254_groth16_batch_info(pk.handle, C.byref(rows), C.byref(batched)))
+    return dict(chunk_rows=int(rows.value), batched=bool(batched.value))
+
+
+def prove_batch(pk: ProvingKey, a, b, c, w, r, s, on_device: bool = False, n_constraints: int | None = None) -> list:
+    """groth16.Prove for many witnesses against one key in one call: a, b, c (rows, n_constraints, 4), w (rows, n_wires, 4), r, s (rows, 4) -> one 128-byte
+    proof per row, each byte for byte what prove() returns for that row.  on_device=True: a, b, c, w are DeviceBuffers / device pointers of row-major
+    matrices (n_constraints says how wide a, b, c are; w is the key's wire count wide) and the row count comes from r."""
+    if on_device:
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        r, s = _rs_rows(r, s, r.shape[0])
+        if n_constraints is None:
+            raise ValueError("device matrices carry no shape: n_constraints is needed")
+        n, n_wires = r.shape[0], pk.n_wires
+    else:
+        a, b, c, w = _rows(a, "a"), _rows(b, "b"), _rows(c, "c"), _rows(w, "w")
+        n, n_wires = w.shape[0], w.shape[1]
+        if not (a.shape == b.shape == c.shape):
+            raise ValueError("a, b, c must have the same shape")
+        if a.shape[0] != n:
+            raise ValueError("a, b, c have %d rows, w has %d" % (a.shape[0], n))
+        r, s = _rs_rows(r, s, n)
+        n_constraints = a.shape[1]
+    proofs = (C.c_uint8 * (128 * max(n, 1)))()
+    rc = lib().zk_bn254_groth16_prove_batch(pk.handle, _ptr(a), _ptr(b), _ptr(c), C.c_size_t(n_constraints), _ptr(w), C.c_size_t(n_wires), vp(r), vp(s),
+                                            C.c_size_t(n), C.c_int(int(on_device)), proofs)
+    if rc == _lib.ZK_ERR_LEN:
+        raise ValueError((lib().zk_last_error() or b"").decode())
+    check(rc)
+    raw = bytes(proofs)
+    return [raw[128 * i:128 * i + 128] for i in range(n)]
+
+
+def prove_r1cs_batch(r1cs: R1CS, pk: ProvingKey, w, r, s) -> list:
+    """groth16.Prove(r1cs, pk, witness) for many witnesses: w (rows, n_wires, 4) -> one proof per row, each what prove_r1cs() returns for it."""
+    w = _rows(w, "w")
+    r, s = _rs_rows(r, s, w.shape[0])
+    n = w.shape[0]
+    proofs = (C.c_uint8 * (128 * max(n, 1)))()
+    rc = lib().zk_bn254_groth16_prove_r1cs_batch(r1cs.handle, pk.handle, vp(w), C.c_size_t(w.shape[1]), vp(r), vp(s), C.c_size_t(n), C.c_int(0), proofs)
+    if rc == _lib.ZK_ERR_LEN:
+        raise ValueError((lib().zk_last_error() or b"").decode())
+    check(rc)
+    raw = bytes(proofs)
+    return [raw[128 * i:128 * i + 128] for i in range(n)]
