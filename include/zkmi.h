@@ -170,9 +170,11 @@ int zk_bn254_msm_bases_prepared(uint64_t bases, size_t bases_offset, uint64_t sc
  * In place on a[0 .. 2^log_n).  decimation: ZK_DIF natural in -> bit-reversed out; ZK_DIT bit-reversed in ->
  * natural out.  coset != 0 evaluates on / interpolates from the coset g*H, g = 5 (FrMultiplicativeGen).
  * FFTInverse also scales by 1/N exactly like upstream.
- * Precondition (as for every zk_fr in this header): the elements are fr.Element images, i.e. Montgomery values REDUCED below r -- what gnark's arithmetic
- * always produces.  The butterflies keep lazily reduced 29-bit-limb values whose bounds (tools/u29_ntt_model.py) start from an entry below 2.2 r; an image in
- * [4r, 2^256) handed to the DIT transform without coset meets a subtraction bias of 4 r in the twiddle-free first stage and gives an undefined result. */
+ * INPUT CONTRACT (zk_bn254_ntt, zk_bn254_ntt_devices, zk_bn254_ntt_dev): every element is a CANONICAL fr.Element image, i.e. a Montgomery value REDUCED
+ * below r -- what gnark's arithmetic always produces.  The transforms do NOT reduce a 256-bit word mod r first: the butterflies unpack the word as it is and
+ * keep lazily reduced 29-bit-limb values whose proven bounds (tools/u29_ntt_model.py, bound_pass) start from an entry below 2.2 r, while a 256-bit word can
+ * be as large as 5.29 r.  For an image in [r, 2^256) the result is undefined (e.g. one in [4r, 2^256) handed to the DIT transform without coset meets a
+ * subtraction bias of 4 r in the twiddle-free first stage).  tests/test_gpu_ntt_shapes.py sweeps exactly this contract: canonical images up to r - 1. */
 int zk_bn254_ntt(zk_fr *a, uint32_t log_n, int inverse, int decimation, int coset);
 /* the same over several device entries of this process (bit i of device_mask = entry i; 2, 4 or 8 entries): block k of the array goes to entry k over that
  * GPU's own PCIe link, the transform runs block-sharded with two all-to-all transposes between the GPUs.  zk_bn254_ntt == device_mask 0 (process default). */
@@ -183,7 +185,9 @@ int zk_bn254_bit_reverse_dev(void *d_a, uint32_t log_n, void *stream);
 
 /* ---- Groth16: computeH and Prove (gnark v0.8.0 internal/backend/bn254/groth16/prove.go) -------------------------
  * computeH: a, b, c hold n <= 2^log_N evaluations each; h_out receives 2^log_N coefficients in the order gnark's
- * computeH leaves them (bit-reversed; the caller uses h[:N-1]). */
+ * computeH leaves them (bit-reversed; the caller uses h[:N-1]).
+ * INPUT CONTRACT: as for the NTT entries above -- a, b, c are canonical fr.Element images (< r); the first passes unpack the caller's words as they are, so
+ * an image in [r, 2^256) gives an undefined result. */
 int zk_bn254_groth16_compute_h(const zk_fr *a, const zk_fr *b, const zk_fr *c, size_t n, uint32_t log_N, zk_fr *h_out);
 int zk_bn254_groth16_compute_h_dev(const void *d_a, const void *d_b, const void *d_c, size_t n, uint32_t log_N,
                                    void *d_h_out, void *stream);

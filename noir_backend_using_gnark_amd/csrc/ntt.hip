@@ -28,6 +28,8 @@
 
 namespace zkmi {
 
+// TILE_LOG, K_STRIDED and plan_passes() below are re-stated in tests/ntt_shapes.py (plan_passes), from which tests/test_ntt_shapes_cpu.py checks that the swept
+// sizes run every pass shape: change them there too.
 static constexpr unsigned TILE_LOG = 11;        // 2048 elements = 64 KiB of LDS per workgroup
 static const unsigned K_STRIDED = (unsigned)std::min<long>(9, std::max<long>(2, ZK_EXP("ZKMI_NTT_KS", 9)));  // strided passes: k <= 9, rows of L >= 4 elements (128-byte runs); 2^20 = 11 + 9 bits = two passes
 static constexpr unsigned NTT_THREADS = 256;
