@@ -13,6 +13,7 @@
 #include <chrono>
 #include <vector>
 
+#include "codec_dev.hpp"
 #include "ctx.hpp"
 #include "ff.hpp"
 #include "ff29.hpp"
@@ -25,14 +26,6 @@
 namespace zkmi {
 
 // ---- hex
-__device__ __forceinline__ uint32_t hexdig4(uint32_t w, uint32_t* bad) {  // 4 characters -> 2 bytes (text order, low byte first); see wire.hip hex4
-    uint32_t nib = (w & 0x0f0f0f0fu) + ((w >> 6) & 0x01010101u) * 9u;
-    uint32_t gt9 = ((nib + 0x06060606u) >> 4) & 0x01010101u;
-    uint32_t enc = nib + 0x30303030u + gt9 * 0x27u;
-    *bad |= (enc ^ (w | ((w >> 1) & 0x20202020u))) | (nib & 0xf0f0f0f0u);
-    uint32_t b = ((nib << 4) | (nib >> 8)) & 0x00ff00ffu;
-    return (b & 0xffu) | ((b >> 8) & 0xff00u);
-}
 // one lane: 8 characters -> 4 bytes
 __global__ void k_hex_decode(const uint32_t* __restrict__ text, size_t n_words, uint32_t* __restrict__ out, int* __restrict__ status) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -42,11 +35,6 @@ __global__ void k_hex_decode(const uint32_t* __restrict__ text, size_t n_words, 
     out[i] = lo | (hi << 16);
     if (bad) atomicOr(status, 1);
 }
-__device__ __forceinline__ uint32_t hexenc2w(uint32_t b16) {
-    uint32_t nib = ((b16 >> 4) & 0x0fu) | ((b16 & 0x0fu) << 8) | (((b16 >> 12) & 0x0fu) << 16) | (((b16 >> 8) & 0x0fu) << 24);
-    uint32_t gt9 = ((nib + 0x06060606u) >> 4) & 0x01010101u;
-    return nib + 0x30303030u + gt9 * 0x27u;
-}
 __global__ void k_hex_encode(const uint32_t* __restrict__ bytes, size_t n_words, uint32_t* __restrict__ text) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_words) return;
@@ -55,266 +43,52 @@ __global__ void k_hex_encode(const uint32_t* __restrict__ bytes, size_t n_words,
     text[2 * i + 1] = hexenc2w(w >> 16);
 }
 
-// ---- 32-byte big-endian integers <-> 8 little-endian limbs, through 4-byte loads (the vectors inside a key sit at any 4-byte offset)
-template <class F>
-__device__ __forceinline__ F load_be32(const uint32_t* p) {
-    F x;
-#pragma unroll
-    for (int k = 0; k < 8; k++) x.l[7 - k] = __builtin_bswap32(p[k]);
-    return x;
-}
-template <class F>
-__device__ __forceinline__ void store_be32(uint32_t* p, const F& x) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) p[k] = __builtin_bswap32(x.l[7 - k]);
-}
-template <class P>
-__device__ __forceinline__ bool geq_mod(const uint32_t x[8]) {
-    for (int i = 7; i >= 0; i--)
-        if (x[i] != P::MOD[i]) return x[i] > P::MOD[i];
-    return true;
-}
+// ---- 32-byte big-endian fr.Elements
 __global__ void k_fr_from_be(const uint32_t* __restrict__ raw, size_t n, Fr* __restrict__ out, int* __restrict__ status) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Fr x = load_be32<Fr>(raw + 8 * i);
-    if (geq_mod<FrParams>(x.l)) { atomicOr(status, 2); return; }  // gnark-crypto: "invalid fr.Element encoding"
-    out[i] = x.to_mont();
+    if (!fr_from_be_one(raw + 8 * i, out + i)) atomicOr(status, 2);
 }
 __global__ void k_fr_to_be(const Fr* __restrict__ in, size_t n, uint32_t* __restrict__ raw) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    store_be32(raw + 8 * i, in[i].from_mont());
-}
-
-// ---- square roots: a^((q - 3) / 4) on the 29-bit multiplier (ff29.hpp)
-// Both decompressions end in this exponentiation (q = 3 mod 4: sqrt(a) = a^((q+1)/4) = a^((q-3)/4) * a; the Fp2 root takes two).  The saturated
-// Field::pow spends 252 squarings + 127 products of ~305 instructions; here the constant exponent is walked in sliding windows of three bits -- 250 squarings
-// of ~170 instructions and 55 products of 206 with a, a^3, a^5, a^7 -- 2.1 x fewer instructions.  One byte per window: squarings << 2 | (odd power >> 1),
-// most significant window first (the first one only selects the starting power); every value in the chain is a direct product output (< 1.03 p).
-__device__ __forceinline__ U29 u29_pow_qm3_4(const U29& a) {
-    static const uint8_t W[56] = {9,  29, 12, 16, 23, 23, 22, 9,  20, 17, 21, 8,  42, 17, 19, 30, 24, 26, 14, 14, 14, 33, 38, 13, 30, 9,  13, 22,
-                                  15, 38, 14, 18, 12, 26, 14, 31, 27, 22, 8,  21, 8,  23, 4,  20, 24, 21, 34, 14, 14, 4,  31, 9,  23, 15, 18, 16};
-    const U29 a2 = u29_sqr(a), a3 = u29_mul(a2, a), a5 = u29_mul(a3, a2), a7 = u29_mul(a5, a2);
-    U29 acc = a3;  // W[0] & 3 == 1
-#pragma unroll 1
-    for (int k = 1; k < 56; k++) {
-        const unsigned w = W[k];
-#pragma unroll 1
-        for (unsigned j = 0; j < (w >> 2); j++) acc = u29_sqr(acc);
-        switch (w & 3u) {
-            case 0: acc = u29_mul(acc, a); break;
-            case 1: acc = u29_mul(acc, a3); break;
-            case 2: acc = u29_mul(acc, a5); break;
-            default: acc = u29_mul(acc, a7); break;
-        }
-    }
-    return acc;
-}
-// canonical Montgomery image -> a^((q-3)/4) * a^mul_a as a canonical Montgomery image (mul_a: once more by a, the square-root candidate)
-__device__ __forceinline__ Fp fp_pow_qm3_4(const Fp& a, bool times_a) {
-    const U29 x = u29_mul(u29_load(a), u29_one());  // contracted: < 1.2 p
-    U29 e = u29_pow_qm3_4(x);
-    if (times_a) e = u29_mul(e, x);
-    return u29_store(e);
+    fr_to_be_one(in[i], raw + 8 * i);
 }
 
 // ---- G1 points
-__device__ __forceinline__ bool fp_lex_largest_dev(const Fp& canonical) {  // value > (q - 1) / 2
-    for (int i = 7; i >= 0; i--) {
-        uint32_t h = (FpParams::MOD[i] >> 1) | (i < 7 ? FpParams::MOD[i + 1] << 31 : 0);
-        if (canonical.l[i] != h) return canonical.l[i] > h;
-    }
-    return false;
-}
-// G1Affine.SetBytes on a compressed encoding: y = sqrt(x^3 + 3) = (x^3 + 3)^((q + 1) / 4)  (q = 3 mod 4), sign by the flag
 __global__ __launch_bounds__(256) void k_g1_decompress(const uint32_t* __restrict__ raw, size_t n, Affine<Fp>* __restrict__ out, int* __restrict__ status,
                                                      uint8_t* __restrict__ bad) {  // bad (may be null): 1 per invalid encoding
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Fp x = load_be32<Fp>(raw + 8 * i);
-    const uint32_t flag = x.l[7] >> 30;
-    x.l[7] &= 0x3fffffffu;
-    Affine<Fp> p = Affine<Fp>::inf();
-    if (flag == 1) {  // infinity: the rest must be zero
-        if (!x.is_zero()) {
-            atomicOr(status, 4);
-            if (bad) bad[i] = 1;
-        }
-        out[i] = p;
-        return;
-    }
-    if (flag == 0 || geq_mod<FpParams>(x.l)) {  // an uncompressed encoding inside a compressed slice / x >= q
+    g1_decompress_one(raw + 8 * i, out + i, [&] {
         atomicOr(status, 4);
         if (bad) bad[i] = 1;
-        out[i] = p;
-        return;
-    }
-    Fp xm = x.to_mont();
-    Fp three = Fp::one() + Fp::one() + Fp::one();
-    Fp rhs = xm.sqr() * xm + three;
-    Fp y = fp_pow_qm3_4(rhs, true);  // rhs^((q + 1) / 4)
-    if (y.sqr() != rhs) {  // not on the curve
-        atomicOr(status, 4);
-        if (bad) bad[i] = 1;
-        out[i] = p;
-        return;
-    }
-    if (fp_lex_largest_dev(y.from_mont()) != (flag == 3)) y = Fp::zero() - y;
-    p.x = xm;
-    p.y = y;
-    out[i] = p;
+    });
 }
 __global__ void k_g1_compress(const Affine<Fp>* __restrict__ pts, size_t n, uint32_t* __restrict__ raw) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Affine<Fp> p = pts[i];
-    Fp x = Fp::zero();
-    uint32_t flag = 1;
-    if (!p.is_inf()) {
-        x = p.x.from_mont();
-        flag = fp_lex_largest_dev(p.y.from_mont()) ? 3 : 2;
-    }
-    x.l[7] |= flag << 30;
-    store_be32(raw + 8 * i, x);
+    g1_compress_one(p, raw + 8 * i);
 }
 
-
-// ---- G2 points on the device (a Groth16 proving key holds one per wire)
-// Square root in Fp2 = Fp[u]/(u^2 + 1), q = 3 mod 4, by the complex method -- two exponentiations in Fp instead of the two in Fp2 of rounds 2-4 (Adj &
-// Rodriguez-Henriquez, Alg. 9: 1,778 base-field products per root; this: ~770).  For a = a0 + a1 u with a1 != 0: the norm n = a0^2 + a1^2 is a square in Fp
-// exactly when a is one in Fp2; with s^2 = n and t = (a0 + s) / 2, one exponentiation e = t^((q-3)/4) gives c = e t with c^2 = chi t (chi = +-1 the quadratic
-// character of t) AND 1 / c = c e^2 -- no inversion --, and the root is (c, a1 / 2c) if chi = 1, (a1 / 2c, c) otherwise (then c^2 = -t = -(a0 + s) / 2 and
-// (a1 / 2c)^2 = (a0 - s) / 2).  Either root will do: the caller picks the sign by the encoding's flag.  `half` = 1 / 2 (Montgomery).
-__device__ bool f2_sqrt_dev(const Fp2& a, const Fp& half, Fp2* out) {
-    if (a.is_zero()) { *out = a; return true; }
-    // every exponentiation below is by (q - 3) / 4: fp_pow_qm3_4
-    if (a.a1.is_zero()) {  // a in Fp: sqrt(a0) or u sqrt(-a0)
-        const Fp c = fp_pow_qm3_4(a.a0, true);
-        if (c.sqr() == a.a0) *out = Fp2{c, Fp::zero()};
-        else *out = Fp2{Fp::zero(), c};
-        return out->sqr() == a;
-    }
-    const Fp n = a.a0.sqr() + a.a1.sqr();
-    const Fp s = fp_pow_qm3_4(n, true);
-    if (s.sqr() != n) return false;  // the norm is not a square: neither is a
-    Fp t = (a.a0 + s) * half;
-    // (t = 0 would need a0 = -s, i.e. a1^2 = s^2 - a0^2 = 0: not on this branch)
-    const Fp e = fp_pow_qm3_4(t, false), c = e * t;
-    const Fp w = a.a1 * (c * e.sqr() * half);  // a1 / (2 c)
-    if (c.sqr() == t) *out = Fp2{c, w};
-    else *out = Fp2{w, c};
-    return out->sqr() == a;
-}
-__device__ __forceinline__ bool f2_lex_largest_dev(const Fp2& y) {  // gnark-crypto: compares A1 first, A0 when A1 = 0
-    return y.a1.is_zero() ? fp_lex_largest_dev(y.a0.from_mont()) : fp_lex_largest_dev(y.a1.from_mont());
-}
-// G2Affine.SetBytes on a compressed encoding (X.A1 | X.A0 big-endian, flags on the first byte) with the subgroup check the gnark-crypto Decoder
-// applies by default (r * P = infinity: the twist has a cofactor).  bt = 3 / (9 + u), Montgomery.
-// r-torsion membership on the twist, with the untwist-Frobenius-twist endomorphism psi: (x, y) -> (conj(x) * gx, conj(y) * gy), gx = xi^((q-1)/3),
-// gy = xi^((q-1)/2), xi = 9 + u, which acts on G2 as multiplication by q = 6 x0^2 (mod r); x0 = 4965661367192848881.  Two exact tests (both accept exactly
-// the points r * P = infinity accepts; tests/test_gpu_keyio.py holds twist points outside G2 and a G2 point shifted by a cofactor-torsion point):
-//   psi(P) == [6 x0^2] P                                       127 doublings + 64 additions     (rounds 2-4)
-//   [x0 + 1] P + psi([x0] P) + psi^2([x0] P) == psi^3([2 x0] P)  63 doublings + 27 + 4 additions  (eprint 2022/348 sec. 5.1 for BN curves; gnark-crypto's
-//                                                               G2Jac.IsInSubGroup): ONE multiplication by the 63-bit x0, three psi, a few additions -- half
-//                                                               the work of a decompression's larger half (68 -> see DESIGN.md 3.8 per 2^20 points)
-struct PsiConsts { Fp2 gx, gy; Fp half; };  // psi's two coefficients; 1 / 2 for the square root
-// The second test runs on the 29-bit multiplier (ff29.hpp: acc29g2_dbl / acc29g2_add, whose class invariant -- every coordinate component < 32 p, weakly
-// normalised, in and out -- tools/u29_model.py proves): 63 doublings and 27 + 3 full additions with one reduction per output component instead of three saturated
-// products per Fp2 product (29.5-30.5 ms per 2^20 points against 33.4-34.2 for the saturated form in the same kernel: profiles/rnd5_v_g2_subgroup_variants.txt).
-// psi keeps the invariant: X and Y times a contracted constant come out below 1.5 p; the conjugated ZZ / ZZZ components are contracted.
-__device__ __forceinline__ Acc29G2 g2_psi_dev29(const Acc29G2& t, const U29x2& gx, const U29x2& gy) {
-    if (t.inf) return t;
-    const U29 one = u29_one();
-    Acc29G2 r;
-    r.inf = false;
-    // conj(v) * g = (v0 g0 + v1 g1) + (v0 g1 - v1 g0) u
-    r.x = U29x2{u29_mul2(t.x.c0, gx.c0, t.x.c1, gx.c1), u29_mul2(t.x.c0, gx.c1, u29_neg<32>(t.x.c1), gx.c0)};
-    r.y = U29x2{u29_mul2(t.y.c0, gy.c0, t.y.c1, gy.c1), u29_mul2(t.y.c0, gy.c1, u29_neg<32>(t.y.c1), gy.c0)};
-    r.zz = U29x2{t.zz.c0, u29_mul(u29_neg<32>(t.zz.c1), one)};
-    r.zzz = U29x2{t.zzz.c0, u29_mul(u29_neg<32>(t.zzz.c1), one)};
-    return r;
-}
-__device__ __forceinline__ bool f2_eq29(const U29x2& a, const U29x2& b) {  // exact: through the canonical images
-    const Fp2 x = f2_store29(a), y = f2_store29(b);
-    return x == y;
-}
-// *pp is read again wherever P is added (28 times: 128 bytes from L2) instead of being held in 72 registers next to the accumulator and an addition's temporaries
-__device__ __forceinline__ void g2_add_affine29(Acc29G2& a, const Affine<Fp2>* __restrict__ pp) {
-    const Fp2 one2{Fp::one(), Fp::zero()};
-    Acc29G2 P1;
-    const Affine<Fp2> q = *pp;
-    acc29g2_load(P1, XYZZ<Fp2>{q.x, q.y, one2, one2});
-    acc29g2_add(a, P1);
-}
-// [x0] P, the long half of the test (63 doublings, 27 additions): a kernel of its own under a two-waves-per-SIMD register bound (256 registers and 132 bytes of
+// ---- G2 points (a Groth16 proving key holds one per wire)
+// [x0] P, the long half of the subgroup test: a kernel of its own under a two-waves-per-SIMD register bound (256 registers and 132 bytes of
 // scratch per lane; with the tail in the same kernel: 256 + 140 registers, one wave per SIMD)
 __global__ __launch_bounds__(128, 2) void k_g2_x0_mul(const Affine<Fp2>* __restrict__ pts, size_t n, XYZZ<Fp2>* __restrict__ out) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (pts[i].is_inf()) return;
-    const uint32_t x0[2] = {0x4a6909f1u, 0x44e992b4u};  // 4965661367192848881
-    Acc29G2 a;
-    a.inf = true;
-    a.x = a.y = a.zz = a.zzz = f2_load29(pts[i].x);  // (defined values; never read while inf)
-#pragma unroll 1
-    for (int k = 62; k >= 0; k--) {
-        acc29g2_dbl(a);
-        if ((x0[k >> 5] >> (k & 31)) & 1) g2_add_affine29(a, pts + i);
-    }
-    out[i] = acc29g2_to_xyzz(a);
-}
-// the rest: [x0 + 1] P + psi([x0] P) + psi^2([x0] P) == psi^3([2 x0] P)
-__device__ bool g2_subgroup_tail29(const Affine<Fp2>* __restrict__ pp, const XYZZ<Fp2>& x0p, const PsiConsts& K) {
-    Acc29G2 a;
-    acc29g2_load(a, x0p);
-    const U29x2 gx = f2_contract29(f2_load29(K.gx)), gy = f2_contract29(f2_load29(K.gy));
-    const Acc29G2 b = g2_psi_dev29(a, gx, gy);  // psi([x0] P)
-    g2_add_affine29(a, pp);                      // [x0 + 1] P
-    Acc29G2 lhs = a;
-    acc29g2_add(lhs, b);
-    const Acc29G2 c = g2_psi_dev29(b, gx, gy);  // psi^2([x0] P)
-    acc29g2_add(lhs, c);
-    Acc29G2 d = g2_psi_dev29(c, gx, gy);        // psi^3([x0] P)
-    acc29g2_dbl(d);                              // psi^3([2 x0] P)
-    if (lhs.inf || d.inf) return lhs.inf && d.inf;
-    // (a coordinate sum that came out as the point at infinity went through the canonical path of acc29g2_add / _dbl, which sets .inf)
-    return f2_eq29(f2_mulFK29<40>(lhs.x, d.zz), f2_mulFK29<40>(d.x, lhs.zz)) && f2_eq29(f2_mulFK29<40>(lhs.y, d.zzz), f2_mulFK29<40>(d.y, lhs.zzz));
+    out[i] = g2_x0_mul_one(pts + i);
 }
 __global__ __launch_bounds__(128) void k_g2_decompress(const uint32_t* __restrict__ raw, size_t n, Fp2 bt, PsiConsts psi, Affine<Fp2>* __restrict__ out,
                                                        int* __restrict__ status, uint8_t* __restrict__ bad) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Fp x1 = load_be32<Fp>(raw + 16 * i), x0 = load_be32<Fp>(raw + 16 * i + 8);
-    const uint32_t flag = x1.l[7] >> 30;
-    x1.l[7] &= 0x3fffffffu;
-    Affine<Fp2> p = Affine<Fp2>::inf();
-    if (flag == 1) {
-        if (!x1.is_zero() || !x0.is_zero()) {
-            atomicOr(status, 8);
-            if (bad) bad[i] = 1;
-        }
-        out[i] = p;
-        return;
-    }
-    if (flag == 0 || geq_mod<FpParams>(x1.l) || geq_mod<FpParams>(x0.l)) {
+    g2_decompress_one(raw + 16 * i, bt, psi.half, out + i, [&] {
         atomicOr(status, 8);
         if (bad) bad[i] = 1;
-        out[i] = p;
-        return;
-    }
-    Fp2 x{x0.to_mont(), x1.to_mont()};
-    Fp2 rhs = x.sqr() * x + bt, y;
-    if (!f2_sqrt_dev(rhs, psi.half, &y)) {
-        atomicOr(status, 8);
-        if (bad) bad[i] = 1;
-        out[i] = p;
-        return;
-    }
-    if (f2_lex_largest_dev(y) != (flag == 3)) y = y.neg();
-    p.x = x;
-    p.y = y;
-    out[i] = p;
+    });
 }
 // second half of G2Affine.SetBytes, a kernel of its own (the square root and the subgroup test in one kernel need 512 registers: one wave per SIMD; apart, each
 // runs with two or more): a point outside the r-torsion subgroup becomes the point at infinity and sets status bit 16
@@ -326,9 +100,8 @@ __global__ __launch_bounds__(128) void k_g2_subgroup(Affine<Fp2>* __restrict__ p
     if (pts[i].is_inf()) return;
     bool member;
     if (FULL) {  // ZKMI_G2_FULL_SUBGROUP_CHECK=1: the definition, r * P == infinity (A/B switch, four times the work)
-        const uint32_t rk[8] = {FrParams::MOD[0], FrParams::MOD[1], FrParams::MOD[2], FrParams::MOD[3], FrParams::MOD[4], FrParams::MOD[5], FrParams::MOD[6], FrParams::MOD[7]};
         const Affine<Fp2> p = pts[i];
-        member = scalar_mul(p, rk).is_inf();
+        member = g2_subgroup_full_one(p);
     } else {
         member = g2_subgroup_tail29(pts + i, x0p[i], psi);
     }
@@ -343,29 +116,13 @@ __global__ void k_g2_compress(const Affine<Fp2>* __restrict__ pts, const uint32_
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Affine<Fp2> p = pts[idx ? idx[i] : i];
-    Fp x1 = Fp::zero(), x0 = Fp::zero();
-    uint32_t flag = 1;
-    if (!p.is_inf()) {
-        x1 = p.x.a1.from_mont();
-        x0 = p.x.a0.from_mont();
-        flag = f2_lex_largest_dev(p.y) ? 3 : 2;
-    }
-    x1.l[7] |= flag << 30;
-    store_be32(raw + 16 * i, x1);
-    store_be32(raw + 16 * i + 8, x0);
+    g2_compress_one(p, raw + 16 * i);
 }
 __global__ void k_g1_compress_idx(const Affine<Fp>* __restrict__ pts, const uint32_t* __restrict__ idx, size_t n, uint32_t* __restrict__ raw) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Affine<Fp> p = pts[idx[i]];
-    Fp x = Fp::zero();
-    uint32_t flag = 1;
-    if (!p.is_inf()) {
-        x = p.x.from_mont();
-        flag = fp_lex_largest_dev(p.y.from_mont()) ? 3 : 2;
-    }
-    x.l[7] |= flag << 30;
-    store_be32(raw + 8 * i, x);
+    g1_compress_one(p, raw + 8 * i);
 }
 // InfinityA / InfinityB of a wire-indexed array: one byte per point
 template <class F>
@@ -404,22 +161,10 @@ int g1_compress_dev(Slot* s, hipStream_t st, const void* d_pts, size_t n, void* 
     return ZK_OK;
 }
 
-static HFp2 f2_pow(HFp2 a, const uint64_t e[4]);
 int g2_decompress_dev(Slot* s, hipStream_t st, const void* d_raw, size_t n, void* d_out, int* d_status, uint8_t* d_bad) {
-    HFp nine = HFp::zero(), three = HFp::one() + HFp::one() + HFp::one();
-    for (int i = 0; i < 3; i++) nine = nine + three;
-    const HFp2 bt = HFp2{three, HFp::zero()} * HFp2{nine, HFp::one()}.inv();
-    Fp2 btd;
-    memcpy(&btd, &bt, sizeof btd);
-    // psi's coefficients: xi^((q-1)/3), xi^((q-1)/2)
-    static const uint64_t E3[4] = {0x69602eb24829a9c2ULL, 0xdd2b2385cd7b4384ULL, 0xe81ac1e7808072c9ULL, 0x10216f7ba065e00dULL};
-    static const uint64_t E2h[4] = {0x9e10460b6c3e7ea3ULL, 0xcbc0b548b438e546ULL, 0xdc2822db40c0ac2eULL, 0x183227397098d014ULL};
-    const HFp2 xi{nine, HFp::one()}, gx = f2_pow(xi, E3), gy = f2_pow(xi, E2h);
-    PsiConsts psi;
-    memcpy(&psi.gx, &gx, sizeof gx);
-    memcpy(&psi.gy, &gy, sizeof gy);
-    const HFp half = (HFp::one() + HFp::one()).inv();
-    memcpy(&psi.half, &half, sizeof half);
+    const G2CodecConsts K = g2_codec_consts();
+    const Fp2 btd = K.bt;
+    const PsiConsts psi = K.psi;
     static const int full = ZK_EXP("ZKMI_G2_FULL_SUBGROUP_CHECK", 0);
     if (n) {
         ZK_LAUNCH(s, st, "g2_decompress", k_g2_decompress, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, (const uint32_t*)d_raw, n, btd, psi, (Affine<Fp2>*)d_out, d_status, d_bad);
@@ -450,15 +195,7 @@ int inf_flags_dev(Slot* s, hipStream_t st, int is_g2, const void* d_pts, size_t 
     return ZK_OK;
 }
 
-// ---- G2 on the host (two points per SRS)
-static HFp2 f2_pow(HFp2 a, const uint64_t e[4]) {
-    HFp2 r = HFp2::one();
-    for (int i = 0; i < 256; i++) {
-        if ((e[i >> 6] >> (i & 63)) & 1) r = r * a;
-        a = a.sqr();
-    }
-    return r;
-}
+// ---- G2 on the host (two points per SRS); f2_pow: codec_dev.hpp
 // square root in Fp2 = Fp[u]/(u^2 + 1), q = 3 mod 4 (Adj & Rodriguez-Henriquez, Alg. 9)
 static bool f2_sqrt(const HFp2& a, HFp2* out) {
     if (a.is_zero()) { *out = a; return true; }

@@ -1,5 +1,5 @@
-// Test-only probe of the device arithmetic: every op runs ONE production inline function (ff.hpp, ff29.hpp, curve.hpp, pairing_dev.hpp,
-// sha256_dev.hpp) on one test vector per lane and writes back the raw limbs it returns -- nothing is canonicalised that the function under test
+// Test-only probe of the device arithmetic and codecs: every op runs ONE production inline function (ff.hpp, ff29.hpp, curve.hpp, pairing_dev.hpp,
+// sha256_dev.hpp, codec_dev.hpp) on one test vector per lane and writes back the raw limbs it returns -- nothing is canonicalised that the function under test
 // did not canonicalise.  Built into libzkmi_probe.so (Makefile `all`), never into libzkmi.so; tests/probe.py binds it.
 //
 // A vector is a fixed number of 32-bit words (IN), a result another (OUT), both per op (PROBE_OPS).  Lane t reads in[t * IN ..] and writes
@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
+#include "codec_dev.hpp"
 #include "ff29.hpp"
 #include "pairing_dev.hpp"
 #include "sha256_dev.hpp"
@@ -41,7 +42,10 @@ namespace probe {
     X(ACC29_MADD, 74, 37) X(ACC29_ADD, 74, 37) X(ACC29_DBL, 74, 37) X(ACC29_ADD_QUAD, 74, 37) X(ACC29_DBL_QUAD, 74, 37)                     \
     X(ACC29_PACK_LOAD, 74, 69) X(ACC29_MADD_CHAIN, 37 + 16 * 100, 37)                                                                        \
     X(ACC29G2_MADD, 146, 73) X(ACC29G2_ADD, 146, 73) X(ACC29G2_DBL, 146, 73) X(ACC29G2_MADD_CHAIN, 73 + 32 * 100, 73)                       \
-    X(SHA256, 12 + SHA_MAX_BYTES / 4, 8)
+    X(SHA256, 12 + SHA_MAX_BYTES / 4, 8)                                                                                                     \
+    X(FP_POW_QM3_4, 8, 8) X(FP_SQRT_CAND, 8, 8) X(F2_SQRT, 16, 17) X(G1_DECOMPRESS, 8, 17) X(G1_COMPRESS, 16, 8)                           \
+    X(G2_DECOMPRESS, 16, 33) X(G2_COMPRESS, 32, 16) X(G2_IN_SUBGROUP, 32, 1) X(G2_IN_SUBGROUP_FULL, 32, 1)                                  \
+    X(FR_FROM_BE, 8, 9) X(FR_TO_BE, 8, 8) X(HEX_DECODE4, 1, 2) X(HEX_ENCODE2, 1, 1)
 
 constexpr int SHA_MAX_BYTES = 320;
 constexpr int CHAIN = 100;  // madds per lane of the *_MADD_CHAIN ops
@@ -166,9 +170,51 @@ __device__ __forceinline__ U29 sub_k(const U29& a, const U29& b) { return u29_su
 template <int K>
 __device__ __forceinline__ U29 neg_k(const U29& a) { return u29_neg<K>(a); }
 
+// codec ops (codec_dev.hpp): the bytes of an encoding as they lie in the file, read as 32-bit words; points and field elements as Montgomery images;
+// a verdict as one word after the value.  K: the production constants of the G2 decoder (g2_codec_consts)
 template <int OP>
-__device__ __forceinline__ void run(const uint32_t* in, uint32_t* out, unsigned lane) {
+__device__ __forceinline__ void codec_op(const uint32_t* in, uint32_t* out, const G2CodecConsts& K) {
+    if constexpr (OP == FP_POW_QM3_4 || OP == FP_SQRT_CAND) st(out, fp_pow_qm3_4(ld<Fp>(in), OP == FP_SQRT_CAND));
+    else if constexpr (OP == F2_SQRT) {
+        Fp2 r = Fp2::zero();
+        out[0] = f2_sqrt_dev(ld<Fp2>(in), K.psi.half, &r) ? 1u : 0u;
+        st(out + 1, r);
+    } else if constexpr (OP == G1_DECOMPRESS) {
+        Affine<Fp> p;
+        out[16] = g1_decompress_one(in, &p, NoReject()) ? 0u : 1u;
+        st(out, p);
+    } else if constexpr (OP == G1_COMPRESS) g1_compress_one(ld<Affine<Fp>>(in), out);
+    else if constexpr (OP == G2_DECOMPRESS) {
+        Affine<Fp2> p;
+        out[32] = g2_decompress_one(in, K.bt, K.psi.half, &p, NoReject()) ? 0u : 1u;
+        st(out, p);
+    } else if constexpr (OP == G2_COMPRESS) g2_compress_one(ld<Affine<Fp2>>(in), out);
+    else if constexpr (OP == G2_IN_SUBGROUP || OP == G2_IN_SUBGROUP_FULL) {
+        // the two kernels of the production test in one (k_g2_x0_mul, k_g2_subgroup), with their guard: the point at infinity is not tested
+        const Affine<Fp2>* pp = reinterpret_cast<const Affine<Fp2>*>(in);
+        const Affine<Fp2> p = *pp;
+        bool member = true;
+        if (!p.is_inf()) {
+            if constexpr (OP == G2_IN_SUBGROUP) member = g2_subgroup_tail29(pp, g2_x0_mul_one(pp), K.psi);
+            else member = g2_subgroup_full_one(p);
+        }
+        out[0] = member ? 1u : 0u;
+    } else if constexpr (OP == FR_FROM_BE) {
+        Fr x = Fr::zero();
+        out[8] = fr_from_be_one(in, &x) ? 0u : 2u;  // the kernel's status bit
+        st(out, x);
+    } else if constexpr (OP == FR_TO_BE) fr_to_be_one(ld<Fr>(in), out);
+    else if constexpr (OP == HEX_DECODE4) {
+        uint32_t bad = 0;
+        out[0] = hexdig4(in[0], &bad);
+        out[1] = bad ? 1u : 0u;
+    } else out[0] = hexenc2w(in[0] & 0xffffu);
+}
+
+template <int OP>
+__device__ __forceinline__ void run(const uint32_t* in, uint32_t* out, unsigned lane, const G2CodecConsts& K) {
     (void)lane;
+    (void)K;
     if constexpr (OP >= FP_MUL && OP <= FP_FROM_MONT) field_op<Fp, FP_MUL, OP>(in, out);
     else if constexpr (OP >= FR_MUL && OP <= FR_FROM_MONT) field_op<Fr, FR_MUL, OP>(in, out);
     else if constexpr (OP >= FP2_MUL && OP <= FP2_INV) {
@@ -296,7 +342,8 @@ __device__ __forceinline__ void run(const uint32_t* in, uint32_t* out, unsigned 
             for (int i = 0; i < CHAIN; i++) xyzz_madd29(A, ld<Fp2>(in + 73 + 32 * i), ld<Fp2>(in + 89 + 32 * i));
         }
         st_acc2(out, A);
-    } else {
+    } else if constexpr (OP >= FP_POW_QM3_4 && OP <= HEX_ENCODE2) codec_op<OP>(in, out, K);
+    else {
         // SHA256 record: mode, length L (bytes, <= SHA_MAX_BYTES), piece size, resume offset, midstate[8], message bytes.
         // mode 0: update in pieces of `piece` bytes; 1: resume(midstate, offset) then update the L bytes; 2: put256 of L / 32 little-endian 8-word integers
         const uint32_t mode = in[0], piece = in[2] ? in[2] : 1u;
@@ -327,18 +374,19 @@ __device__ __forceinline__ void run(const uint32_t* in, uint32_t* out, unsigned 
 constexpr unsigned BLOCK = 64;
 
 template <int OP>
-__global__ __launch_bounds__(BLOCK) void k_probe(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n) {
+__global__ __launch_bounds__(BLOCK) void k_probe(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n, G2CodecConsts K) {
     const size_t t = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (t >= n) return;
-    run<OP>(in + t * (size_t)IN_W[OP], out + t * (size_t)OUT_W[OP], threadIdx.x);
+    run<OP>(in + t * (size_t)IN_W[OP], out + t * (size_t)OUT_W[OP], threadIdx.x, K);
 }
 
 int launch(int op, const uint32_t* in, uint32_t* out, size_t n) {
     const dim3 grid((unsigned)((n + BLOCK - 1) / BLOCK)), block(BLOCK);
+    const G2CodecConsts K = g2_codec_consts();
     switch (op) {
 #define PROBE_CASE(name, i, o)                          \
     case name:                                          \
-        k_probe<name><<<grid, block, 0, 0>>>(in, out, n); \
+        k_probe<name><<<grid, block, 0, 0>>>(in, out, n, K); \
         break;
         PROBE_OPS(PROBE_CASE)
 #undef PROBE_CASE

@@ -591,6 +591,8 @@ def g2_decompress(b: bytes, subgroup_check: bool = True):
     checks r-torsion membership by default (the twist has a cofactor): restated as r * P = infinity."""
     flag = b[0] >> 6
     if flag == 1:
+        if any(b[1:64]) or b[0] & 0x3F:  # as G1: gnark-crypto's SetBytes wants every other bit of an infinity encoding zero
+            raise ValueError("invalid infinity encoding")
         return None
     if flag == 0:
         raise ValueError("uncompressed point where a compressed one is expected")
