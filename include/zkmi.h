@@ -180,6 +180,13 @@ int zk_bn254_ntt(zk_fr *a, uint32_t log_n, int inverse, int decimation, int cose
  * GPU's own PCIe link, the transform runs block-sharded with two all-to-all transposes between the GPUs.  zk_bn254_ntt == device_mask 0 (process default). */
 int zk_bn254_ntt_devices(zk_fr *a, uint32_t log_n, int inverse, int decimation, int coset, uint32_t device_mask);
 int zk_bn254_ntt_dev(void *d_a, uint32_t log_n, int inverse, int decimation, int coset, void *stream);
+/* Row batches: the same transform on `rows` vectors of one domain in ONE launch per pass (the row is a grid dimension), instead of one under-filled launch per
+ * pass per vector.  Row i is a[i * row_stride .. i * row_stride + 2^log_n), row_stride in elements and >= 2^log_n; elements between the rows are not touched.
+ * The input contract is the one above, per row; row i's result is bit for bit zk_bn254_ntt_dev's on that row.  rows == 0 does nothing.
+ * zk_bn254_ntt_batch takes contiguous host rows (row_stride = 2^log_n) on one device: it never spreads over device entries.  ZK_ERR_ARG, before the device is
+ * touched: null pointer, log_n > 28, bad decimation, row_stride < 2^log_n. */
+int zk_bn254_ntt_batch_dev(void *d_a, uint32_t log_n, size_t rows, size_t row_stride, int inverse, int decimation, int coset, void *stream);
+int zk_bn254_ntt_batch(zk_fr *a, uint32_t log_n, size_t rows, int inverse, int decimation, int coset);
 int zk_bn254_bit_reverse(zk_fr *a, uint32_t log_n);
 int zk_bn254_bit_reverse_dev(void *d_a, uint32_t log_n, void *stream);
 
@@ -191,6 +198,16 @@ int zk_bn254_bit_reverse_dev(void *d_a, uint32_t log_n, void *stream);
 int zk_bn254_groth16_compute_h(const zk_fr *a, const zk_fr *b, const zk_fr *c, size_t n, uint32_t log_N, zk_fr *h_out);
 int zk_bn254_groth16_compute_h_dev(const void *d_a, const void *d_b, const void *d_c, size_t n, uint32_t log_N,
                                    void *d_h_out, void *stream);
+/* computeH of `rows` triples in the launches of one (the six transforms with the row as a grid dimension).  Row i of a, b, c holds n <= 2^log_N evaluations at
+ * element i * in_stride (in_stride >= n) and is zero-padded to the domain; the inputs are only read.  Row i of the result, 2^log_N coefficients in computeH's order,
+ * goes to element i * out_stride (out_stride >= 2^log_N) of d_h_out; elements between the rows are not touched.  d_h_out may be d_a itself when row i of both is
+ * the same memory (in_stride == out_stride, or one row); any other overlap of d_h_out with an input is ZK_ERR_ARG.  Same input contract as above; row i's result
+ * is bit for bit zk_bn254_groth16_compute_h_dev's on that row.  The host entry takes contiguous rows: a, b, c (rows, n), h_out (rows, 2^log_N).  Scratch comes
+ * from the slot's arena, at most 1 GiB at a time: more rows than fit run in chunks.  ZK_ERR_ARG, before the device is touched: null pointer, log_N > 28,
+ * n > 2^log_N, in_stride < n, out_stride < 2^log_N.  rows == 0 does nothing. */
+int zk_bn254_groth16_compute_h_batch_dev(const void *d_a, const void *d_b, const void *d_c, size_t n, size_t in_stride, uint32_t log_N, size_t rows,
+                                         void *d_h_out, size_t out_stride, void *stream);
+int zk_bn254_groth16_compute_h_batch(const zk_fr *a, const zk_fr *b, const zk_fr *c, size_t n, uint32_t log_N, size_t rows, zk_fr *h_out);
 /* computeH sharded over G = 2^log_g GPUs (one process per GPU; SURVEY.md 8e: the transposes are all-to-all over xGMI,
  * issued by the host between the phases -- the library never communicates).  Rank rho owns the block
  * [rho*M, (rho+1)*M), M = 2^log_D / G, of a, b, c (natural order) and receives the same block of h (gnark's

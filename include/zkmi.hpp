@@ -85,8 +85,21 @@ public:
     Error FFT(fr::Vector& a, Decimation decimation, bool coset = false) const { return run(a, 0, decimation, coset); }
     // (*Domain).FFTInverse: same data movement with the inverse twiddles, scaled by 1/N (and the inverse coset table)
     Error FFTInverse(fr::Vector& a, Decimation decimation, bool coset = false) const { return run(a, 1, decimation, coset); }
+    // the same on `rows` vectors of Cardinality elements each, row-major in a, in one launch per pass (zk_bn254_ntt_batch); no upstream counterpart
+    Error FFTBatch(fr::Vector& a, size_t rows, Decimation decimation, bool coset = false) const { return run_batch(a, rows, 0, decimation, coset); }
+    Error FFTInverseBatch(fr::Vector& a, size_t rows, Decimation decimation, bool coset = false) const { return run_batch(a, rows, 1, decimation, coset); }
 
 private:
+    uint32_t log_n() const {
+        uint32_t l = 0;
+        while ((uint64_t(1) << l) < Cardinality) l++;
+        return l;
+    }
+    Error run_batch(fr::Vector& a, size_t rows, int inverse, Decimation decimation, bool coset) const {
+        if (a.size() != rows * Cardinality) return Error{ZK_ERR_ARG, "len(a) != rows * domain.Cardinality"};
+        if (rows == 0) return Error{};
+        return make_error(zk_bn254_ntt_batch(a.data(), log_n(), rows, inverse, (int)decimation, coset ? 1 : 0));
+    }
     Error run(fr::Vector& a, int inverse, Decimation decimation, bool coset) const {
         if (a.size() != Cardinality) return Error{ZK_ERR_ARG, "len(a) != domain.Cardinality"};
         uint32_t log_n = 0;

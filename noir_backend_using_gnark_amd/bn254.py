@@ -232,6 +232,45 @@ class Domain:
         check(lib().zk_bn254_ntt(vp(a), C.c_uint32(self.log_n), C.c_int(int(inverse)), C.c_int(decimation), C.c_int(int(bool(coset)))))
         return a
 
+    def _run_batch(self, a, inverse, decimation, coset, rows, row_stride):
+        """`rows` vectors of this domain in one launch per pass (zk_bn254_ntt_batch[_dev]); every shape / dtype / stride error is raised before the library is called"""
+        if decimation not in (DIT, DIF):
+            raise ValueError("decimation must be DIT or DIF")
+        n = self.cardinality
+        if isinstance(a, (int, _lib.DeviceBuffer)):
+            if rows is None:
+                raise ValueError("rows is required with device-resident data")
+            rows, row_stride = int(rows), int(n if row_stride is None else row_stride)
+            if rows < 0:
+                raise ValueError("rows must not be negative")
+            if row_stride < n:
+                raise ValueError("row_stride = %d is below the domain cardinality %d" % (row_stride, n))
+            if isinstance(a, _lib.DeviceBuffer) and rows and ((rows - 1) * row_stride + n) * 32 > a.nbytes:
+                raise ValueError("%d rows at stride %d do not fit the device buffer (%d bytes)" % (rows, row_stride, a.nbytes))
+            ptr = a if isinstance(a, int) else a.ptr
+            check(lib().zk_bn254_ntt_batch_dev(C.c_void_p(ptr), C.c_uint32(self.log_n), C.c_size_t(rows), C.c_size_t(row_stride), C.c_int(int(inverse)),
+                                               C.c_int(decimation), C.c_int(int(bool(coset))), C.c_void_p(0)))
+            return a
+        if not (isinstance(a, np.ndarray) and a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"]):
+            raise TypeError("in-place transform needs a C-contiguous uint64 numpy array (or a device buffer)")
+        if a.ndim != 3 or a.shape[1:] != (n, 4):
+            raise ValueError("a has shape %s, not (rows, %d, 4)" % (a.shape, n))
+        if rows is not None and int(rows) != a.shape[0]:
+            raise ValueError("rows = %d != %d rows of the array" % (rows, a.shape[0]))
+        if row_stride is not None and int(row_stride) != n:
+            raise ValueError("the rows of a host array are contiguous: row_stride must be %d" % n)
+        check(lib().zk_bn254_ntt_batch(vp(a), C.c_uint32(self.log_n), C.c_size_t(a.shape[0]), C.c_int(int(inverse)), C.c_int(decimation), C.c_int(int(bool(coset)))))
+        return a
+
+    def fft_batch(self, a, decimation: int, coset: bool = False, rows: int | None = None, row_stride: int | None = None):
+        """(*Domain).FFT on every row of a -- an (rows, N, 4) uint64 array, or a device buffer / pointer with `rows` rows `row_stride` elements apart (default N) --
+        in place, one launch per pass for all rows.  Row i's result is fft's on that row."""
+        return self._run_batch(a, False, decimation, coset, rows, row_stride)
+
+    def fft_inverse_batch(self, a, decimation: int, coset: bool = False, rows: int | None = None, row_stride: int | None = None):
+        """(*Domain).FFTInverse on every row of a, as fft_batch."""
+        return self._run_batch(a, True, decimation, coset, rows, row_stride)
+
     def fft(self, a, decimation: int, coset: bool = False):
         """(*Domain).FFT(a, decimation, coset...) -- in place."""
         return self._run(a, False, decimation, coset)

@@ -8,7 +8,8 @@
 //     dropped before the sort as in the single prover), one sort, one task plan; the same once more over the h matrix for Z;
 //   * one accumulate launch per base array -- G2.B, A, B1, K, Z, chained as in the single prover -- over S bucket sets, and one reduction that yields S sums;
 //   * the R1CS step (prove_r1cs_batch) as one launch with the row as a grid dimension (r1cs.hip k_spmv3_rows);
-//   * computeH per row on one stream (the transforms are not batched across rows yet: DESIGN.md 3.12), the host tail per row on a few host threads.
+//   * computeH of the whole chunk in the launches of ONE computeH (ntt.hip compute_h_rows_inplace: the row is a grid dimension of every pass);
+//   * the host tail per row on a few host threads (not batched yet: DESIGN.md 3.12).
 #include <string.h>
 
 #include <algorithm>
@@ -102,14 +103,14 @@ static int prove_chunk(uint64_t pk_handle, const Groth16BatchView& V, Slot* sl[5
             w_rows = d_w;
         }
         ZK_TRY(msm_prepare_scalars_table_rows(sl[4], st4, w_rows, nw, (unsigned)S, nw, &kMontCfg, V.tab_w, &prep_w, true));
-        // ---- a, b, c rows, zero-padded to the domain (the inputs are only read), then h = computeH row by row, left in the a rows
+        // ---- a, b, c rows, zero-padded to the domain (the inputs are only read), then h = computeH of all S rows at once, left in the a rows
         Fr* dst[3] = {d_a, d_b, d_c};
         const char* src[3] = {in.a, in.b, in.c};
         for (int m = 0; m < 3; m++) {
             if (nc) ZK_HIP(hipMemcpy2DAsync(dst[m], N * 32, src[m] + first * nc * 32, nc * 32, nc * 32, S, kind, st0));
             if (nc < N) ZK_HIP(hipMemset2DAsync(dst[m] + nc, N * 32, 0, (N - nc) * 32, S, st0));
         }
-        for (size_t i = 0; i < S; i++) ZK_TRY(compute_h_inplace(sl[0], st0, d_a + i * N, d_b + i * N, d_c + i * N, V.log_domain));
+        ZK_TRY(compute_h_rows_inplace(sl[0], st0, d_a, d_b, d_c, V.log_domain, S, N));
         ZK_HIP(hipEventCreateWithFlags(&ev_h, hipEventDisableTiming));
         ZK_HIP(hipEventRecord(ev_h, st0));
         // ---- accumulate chain G2.B -> A -> B1 -> K -> Z, each launch over all S bucket sets, each reduction tail under the next accumulate

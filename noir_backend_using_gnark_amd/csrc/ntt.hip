@@ -225,9 +225,10 @@ __device__ __forceinline__ void lds_store9(uint4* lo, uint4* hi, uint32_t* top, 
 //   2  forward half of k_ntt_pass29_if: A.tw2, no tables, canonical image if A.canonical
 //   3  k_ntt_pass29_if's third vector, a plain FFTInverse ending: A.tw, * A.post_const, canonical image
 // SUB (compile-time too: its extra live values would cost every other pass a wave of occupancy) adds computeH's closing step.
-template <int G, bool DIF, unsigned THREADS, bool SUB, int MODE, bool UNIT>
+// ROWS (the row-batched kernels below): `pre` and `sub` may be per-row operands, found pre_off / sub_off elements further on (0 where all rows share the table).
+template <int G, bool DIF, unsigned THREADS, bool SUB, int MODE, bool UNIT, bool ROWS = false>
 __device__ __forceinline__ void ntt_group29(const PassArgs& A, uint4* lo, uint4* hi, uint32_t* top, size_t base, unsigned E, unsigned s0,
-                                            bool load_packed, bool apply_pre, bool apply_post, bool store_packed) {
+                                            bool load_packed, bool apply_pre, bool apply_post, bool store_packed, size_t pre_off = 0, size_t sub_off = 0) {
     constexpr unsigned NE = 1u << G;
     const unsigned L = 1u << A.logL;
     const unsigned ql = DIF ? (A.k - s0 - G) : s0;
@@ -239,7 +240,7 @@ __device__ __forceinline__ void ntt_group29(const PassArgs& A, uint4* lo, uint4*
         for (unsigned e = 0; e < NE; e++) {
             const unsigned t = ((mid0 | (e << ql)) << A.logL) + l;
             x[e] = load_packed ? u29_unpack(lds_load(lo, hi, t)) : lds_load9(lo, hi, top, t);
-            if (MODE == 0 && apply_pre && A.pre) x[e] = u29r_mul(x[e], u29r_load5(gload_fr(A.pre + base + ((size_t)(mid0 | (e << ql)) << A.bit_lo) + l)));
+            if (MODE == 0 && apply_pre && A.pre) x[e] = u29r_mul(x[e], u29r_load5(gload_fr(A.pre + (ROWS ? pre_off : 0) + base + ((size_t)(mid0 | (e << ql)) << A.bit_lo) + l)));
         }
 #pragma unroll
         for (int sl = 0; sl < G; sl++) {
@@ -289,7 +290,7 @@ __device__ __forceinline__ void ntt_group29(const PassArgs& A, uint4* lo, uint4*
                 if ((MODE == 0 || MODE == 1) && A.post) x[e] = u29r_mul(x[e], u29r_load5(gload_fr(A.post + base + ((size_t)(mid0 | (e << ql)) << A.bit_lo) + l)));
                 else if (MODE == 3 || (MODE == 0 && A.has_post_const)) x[e] = u29r_mul(x[e], u29r_load5(A.post_const));
                 if (SUB) {  // x < 2 r after the product above; sub[i] canonical: the difference stays below 6 r, a legal multiplicand (tools/u29_ntt_model.py)
-                    const U29 c = u29_unpack(gload_fr(A.sub + base + ((size_t)(mid0 | (e << ql)) << A.bit_lo) + l));
+                    const U29 c = u29_unpack(gload_fr(A.sub + (ROWS ? sub_off : 0) + base + ((size_t)(mid0 | (e << ql)) << A.bit_lo) + l));
                     x[e] = u29r_mul(u29r_sub<4>(x[e], c), u29r_load5(A.post_const));
                 }
             }
@@ -300,21 +301,22 @@ __device__ __forceinline__ void ntt_group29(const PassArgs& A, uint4* lo, uint4*
 }
 
 // all k stages of a pass, GMAX at a time.  packed_in / packed_out: the tile sits in LDS as 8 packed words before / after.
-template <int GMAX, unsigned THREADS, bool DIF, bool SUB, int MODE>
-__device__ __forceinline__ void ntt_stages29(const PassArgs& A, uint4* lo, uint4* hi, uint32_t* top, size_t base, unsigned E, bool packed_in, bool packed_out) {
+template <int GMAX, unsigned THREADS, bool DIF, bool SUB, int MODE, bool ROWS = false>
+__device__ __forceinline__ void ntt_stages29(const PassArgs& A, uint4* lo, uint4* hi, uint32_t* top, size_t base, unsigned E, bool packed_in, bool packed_out,
+                                             size_t pre_off = 0, size_t sub_off = 0) {
     for (unsigned s0 = 0; s0 < A.k;) {
         const unsigned G = (A.k - s0 >= (unsigned)GMAX) ? (unsigned)GMAX : (A.k - s0);
         const bool first = (s0 == 0), last = (s0 + G == A.k);
         const bool lp = first && packed_in, sp = last && packed_out;
         const bool ug = A.unit_skip && A.bit_lo == 0 && (DIF ? last : first);  // the group that holds index bit 0 (uniform)
         if (ug) {
-            if (GMAX >= 3 && G == 3) ntt_group29<(GMAX >= 3 ? 3 : 1), DIF, THREADS, SUB, MODE, true>(A, lo, hi, top, base, E, s0, lp, first, last, sp);
-            else if (G == 2) ntt_group29<2, DIF, THREADS, SUB, MODE, true>(A, lo, hi, top, base, E, s0, lp, first, last, sp);
-            else ntt_group29<1, DIF, THREADS, SUB, MODE, true>(A, lo, hi, top, base, E, s0, lp, first, last, sp);
+            if (GMAX >= 3 && G == 3) ntt_group29<(GMAX >= 3 ? 3 : 1), DIF, THREADS, SUB, MODE, true, ROWS>(A, lo, hi, top, base, E, s0, lp, first, last, sp, pre_off, sub_off);
+            else if (G == 2) ntt_group29<2, DIF, THREADS, SUB, MODE, true, ROWS>(A, lo, hi, top, base, E, s0, lp, first, last, sp, pre_off, sub_off);
+            else ntt_group29<1, DIF, THREADS, SUB, MODE, true, ROWS>(A, lo, hi, top, base, E, s0, lp, first, last, sp, pre_off, sub_off);
         } else {
-            if (GMAX >= 3 && G == 3) ntt_group29<(GMAX >= 3 ? 3 : 1), DIF, THREADS, SUB, MODE, false>(A, lo, hi, top, base, E, s0, lp, first, last, sp);
-            else if (G == 2) ntt_group29<2, DIF, THREADS, SUB, MODE, false>(A, lo, hi, top, base, E, s0, lp, first, last, sp);
-            else ntt_group29<1, DIF, THREADS, SUB, MODE, false>(A, lo, hi, top, base, E, s0, lp, first, last, sp);
+            if (GMAX >= 3 && G == 3) ntt_group29<(GMAX >= 3 ? 3 : 1), DIF, THREADS, SUB, MODE, false, ROWS>(A, lo, hi, top, base, E, s0, lp, first, last, sp, pre_off, sub_off);
+            else if (G == 2) ntt_group29<2, DIF, THREADS, SUB, MODE, false, ROWS>(A, lo, hi, top, base, E, s0, lp, first, last, sp, pre_off, sub_off);
+            else ntt_group29<1, DIF, THREADS, SUB, MODE, false, ROWS>(A, lo, hi, top, base, E, s0, lp, first, last, sp, pre_off, sub_off);
         }
         s0 += G;
         __syncthreads();
@@ -415,6 +417,76 @@ __global__ ZK_NTT_BOUNDS(THREADS) void k_ntt_pass29_if(PassArgs A) {
         ntt_stages29<GMAX, THREADS, false, false, 2>(A, lo, hi, top, base, E, false, true);  // forward half
     }
     tile_copy_out<THREADS>(data, 0, 0, lo, hi, base, E);
+}
+
+// ------------------------------------------------------------------------------------------------ row-batched passes
+// The same pass on MANY vectors of one domain in one launch: blockIdx.z is the row, blockIdx.y keeps its meaning (vector a / b / c of computeH).  What belongs
+// to a row moves by row * stride elements (stride >= N): data / data2 / data3, src / src2 / src3, and `pre` / `sub` where they are per-row operands (computeH's
+// closing transform: pre = b, sub = c; pre_stride / sub_stride = 0 where every row shares the table).  Twiddles, a coset table in `post`, tw2: one per domain.
+// One workgroup still handles one tile of one row, so a domain below 2^11 leaves lanes of its 512 idle exactly as in the single-vector kernels.
+// The existing kernels are untouched: ROWS is a template parameter of the stage helpers and their instantiations with ROWS = false compile to what they did.
+struct RowArgs {
+    size_t stride, pre_stride, sub_stride;  // in Fr elements
+};
+// the row's byte offset joins the vector's address before tile_copy_in / tile_copy_out restate its address space: resolved once per workgroup, in scalar registers
+__device__ __forceinline__ Fr* row_data(const PassArgs& A, size_t off) {
+    return reinterpret_cast<Fr*>(pick3((uintptr_t)A.data, (uintptr_t)A.data2, (uintptr_t)A.data3) + off * sizeof(Fr));
+}
+__device__ __forceinline__ const Fr* row_src(const PassArgs& A, const Fr* data, size_t off) {
+    const uintptr_t src = pick3((uintptr_t)A.src, (uintptr_t)A.src2, (uintptr_t)A.src3);
+    return src ? reinterpret_cast<const Fr*>(src + off * sizeof(Fr)) : data;
+}
+
+template <int GMAX, unsigned THREADS, bool SUB = false>
+__global__ ZK_NTT_BOUNDS(THREADS) void k_ntt_pass29_rows(PassArgs A, RowArgs R) {
+    prio_mid();
+    extern __shared__ uint4 lds[];
+    const unsigned E = 1u << (A.k + A.logL);
+    uint4* lo = lds;
+    uint4* hi = lds + E;
+    uint32_t* top = reinterpret_cast<uint32_t*>(lds + 2 * E);
+    const unsigned lo_blks = (1u << A.bit_lo) >> A.logL;  // >= 1
+    const size_t tile = blockIdx.x;
+    const size_t hi_idx = tile / lo_blks;
+    const unsigned lo_blk = (unsigned)(tile % lo_blks);
+    const size_t base = (hi_idx << (A.bit_lo + A.k)) + ((size_t)lo_blk << A.logL);
+    const size_t row = blockIdx.z;
+    Fr* const data = row_data(A, row * R.stride);
+    tile_copy_in<THREADS>(row_src(A, data, row * R.stride), A.logL, A.bit_lo, lo, hi, base, E);
+    __syncthreads();
+    if (A.dif) ntt_stages29<GMAX, THREADS, true, SUB, 0, true>(A, lo, hi, top, base, E, true, true, row * R.pre_stride, row * R.sub_stride);
+    else ntt_stages29<GMAX, THREADS, false, SUB, 0, true>(A, lo, hi, top, base, E, true, true, row * R.pre_stride, row * R.sub_stride);
+    tile_copy_out<THREADS>(data, A.logL, A.bit_lo, lo, hi, base, E);
+}
+
+// k_ntt_pass29_if with the row as blockIdx.z (its `post` is the coset table of the domain: shared)
+template <int GMAX, unsigned THREADS>
+__global__ ZK_NTT_BOUNDS(THREADS) void k_ntt_pass29_if_rows(PassArgs A, RowArgs R) {
+    prio_mid();
+    extern __shared__ uint4 lds[];
+    const unsigned E = 1u << (A.k + A.logL);
+    uint4* lo = lds;
+    uint4* hi = lds + E;
+    uint32_t* top = reinterpret_cast<uint32_t*>(lds + 2 * E);
+    const size_t base = (size_t)blockIdx.x << A.k;  // contiguous tiles only (bit_lo = 0, logL = 0)
+    const size_t off = (size_t)blockIdx.z * R.stride;
+    Fr* const data = row_data(A, off);
+    tile_copy_in<THREADS>(row_src(A, data, off), 0, 0, lo, hi, base, E);
+    __syncthreads();
+    if (blockIdx.y == 2) {
+        ntt_stages29<GMAX, THREADS, true, false, 3>(A, lo, hi, top, base, E, true, true);
+    } else {
+        ntt_stages29<GMAX, THREADS, true, false, 1>(A, lo, hi, top, base, E, true, false);
+        ntt_stages29<GMAX, THREADS, false, false, 2>(A, lo, hi, top, base, E, false, true);
+    }
+    tile_copy_out<THREADS>(data, 0, 0, lo, hi, base, E);
+}
+
+// a[row * stride] *= t[0]: the N == 1 transform of `rows` rows of one element
+__global__ void k_scale_table_rows(Fr* a, size_t stride, const Fr* t, size_t rows) {
+    prio_mid();
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < rows) a[i * stride] = a[i * stride] * gload_fr(t);
 }
 
 // a[i] *= t[i]  (used when a transform has no stage to fold a scaling into: N == 1)
@@ -665,6 +737,140 @@ static int run_inverse_forward(Slot* s, hipStream_t st, Fr* data, const Domain* 
     return ZK_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ row-batched launchers
+// Twins of launch_pass / run_passes / run_inverse_forward over `rows` vectors `stride` elements apart: the SAME number of launches as for one vector whatever the
+// row count (gridDim.z = rows), up to the 65535 a grid's z extent holds; more rows are taken in several launches, never folded into x.
+static constexpr size_t ROWS_PER_LAUNCH = 65535;
+
+static void advance_rows(PassArgs& A, const RowArgs& R, size_t r0) {
+    const size_t d = r0 * R.stride;
+    A.data += d;
+    if (A.data2) A.data2 += d;
+    if (A.data3) A.data3 += d;
+    if (A.src) A.src += d;
+    if (A.src2) A.src2 += d;
+    if (A.src3) A.src3 += d;
+    if (A.pre) A.pre += r0 * R.pre_stride;
+    if (A.sub) A.sub += r0 * R.sub_stride;
+}
+
+static int launch_pass_rows(Slot* s, hipStream_t st, const PassArgs& A_, const RowArgs& R, size_t rows) {
+    const unsigned E = 1u << (A_.k + A_.logL);
+    const unsigned tiles = (unsigned)(((size_t)1 << A_.logn) / E);
+    const char* name = A_.logL ? "ntt_pass_strided_rows" : "ntt_pass_contig_rows";
+    const unsigned ny = 1 + (A_.data2 ? 1 : 0) + (A_.data2 && A_.data3 ? 1 : 0);
+    for (size_t r0 = 0; r0 < rows; r0 += ROWS_PER_LAUNCH) {
+        const unsigned nz = (unsigned)std::min(rows - r0, ROWS_PER_LAUNCH);
+        PassArgs A = A_;
+        A.tw_and = g_tw_and;
+        A.unit_skip = g_unit_skip;
+        advance_rows(A, R, r0);
+        if (A.sub && g_ntt_g2) ZK_LAUNCH(s, st, name, (k_ntt_pass29_rows<2, 512, true>), dim3(tiles, ny, nz), dim3(512), (size_t)E * 36, A, R);
+        else if (A.sub) ZK_LAUNCH(s, st, name, (k_ntt_pass29_rows<3, 256, true>), dim3(tiles, ny, nz), dim3(NTT_THREADS), (size_t)E * 36, A, R);
+        else if (g_ntt_g2) ZK_LAUNCH(s, st, name, (k_ntt_pass29_rows<2, 512>), dim3(tiles, ny, nz), dim3(512), (size_t)E * 36, A, R);
+        else ZK_LAUNCH(s, st, name, (k_ntt_pass29_rows<3, 256>), dim3(tiles, ny, nz), dim3(NTT_THREADS), (size_t)E * 36, A, R);
+    }
+    return ZK_OK;
+}
+
+// run_passes on `rows` vectors.  pre_stride / sub_stride: 0 = `pre` / `sub` is one table for every row, else the distance between the rows' operands.
+static int run_passes_rows(Slot* s, hipStream_t st, Fr* data, size_t stride, size_t rows, const Domain* dom, int inverse, int dif, const Fr* pre, size_t pre_stride,
+                           const Fr* post, const Fr* post_const, const Fr* sub = nullptr, size_t sub_stride = 0) {
+    const unsigned logn = dom->logn;
+    if (g_ntt_saturated) {  // the saturated kernels (A/B switch) have no row form: row by row
+        for (size_t i = 0; i < rows; i++)
+            ZK_TRY(run_passes(s, st, data + i * stride, dom, inverse, dif, pre ? pre + i * pre_stride : nullptr, post, post_const, nullptr, sub ? sub + i * sub_stride : nullptr));
+        return ZK_OK;
+    }
+    if (logn == 0) {  // rows of one element: a transform of one point is its scaling (1/N = 1)
+        if (pre_stride || sub) return set_err(ZK_ERR_ARG, "per-row operands need a domain of at least two points");
+        const unsigned grid = (unsigned)((rows + 255) / 256);
+        if (pre) ZK_LAUNCH(s, st, "ntt_scale_rows", k_scale_table_rows, dim3(grid), dim3(256), 0, data, stride, pre, rows);
+        if (post) ZK_LAUNCH(s, st, "ntt_scale_rows", k_scale_table_rows, dim3(grid), dim3(256), 0, data, stride, post, rows);
+        return ZK_OK;
+    }
+    const Fr* tw = inverse ? dom->tw29_inv : dom->tw29;
+    const RowArgs R = {stride, pre_stride, sub_stride};
+    std::vector<PassPlan> passes = plan_passes(logn);
+    const size_t npass = passes.size();
+    for (size_t idx = 0; idx < npass; idx++) {
+        const PassPlan& p = dif ? passes[npass - 1 - idx] : passes[idx];
+        PassArgs A;
+        A.data2 = nullptr; A.src2 = nullptr; A.data3 = nullptr; A.src3 = nullptr; A.src = nullptr;
+        A.data = data; A.tw = tw; A.tw2 = nullptr; A.logn = logn; A.bit_lo = p.bit_lo; A.k = p.k; A.logL = p.logL; A.dif = dif;
+        A.pre = (idx == 0) ? pre : nullptr;
+        A.post = (idx + 1 == npass) ? post : nullptr;
+        A.has_post_const = (idx + 1 == npass && post_const && !post) ? 1 : 0;
+        A.sub = (idx + 1 == npass) ? sub : nullptr;
+        if (A.has_post_const || A.sub) A.post_const = *post_const; else A.post_const = Fr::zero();
+        A.canonical = (idx + 1 == npass) ? 1 : 0;
+        ZK_TRY(launch_pass_rows(s, st, A, R, rows));
+    }
+    return ZK_OK;
+}
+
+// run_inverse_forward on `rows` vectors (and their second / third vectors data2 / data3, the same distance apart): in place
+static int run_inverse_forward_rows(Slot* s, hipStream_t st, Fr* data, size_t stride, size_t rows, const Domain* dom, const Fr* mid, Fr* data2 = nullptr,
+                                    Fr* data3 = nullptr, const Fr* end3 = nullptr, const Fr* const* src = nullptr) {
+    // src (optional): the rows of the three inputs live in src[0..2], `stride` apart like the data, and stay untouched -- the first pass reads them
+    const unsigned logn = dom->logn;
+    if (g_ntt_saturated || !g_ntt_fuse_if || logn == 0) {  // the unfused A/B variants: row by row
+        for (size_t i = 0; i < rows; i++)
+            ZK_TRY(run_inverse_forward(s, st, data + i * stride, dom, mid, src ? src[0] + i * stride : nullptr, data2 ? data2 + i * stride : nullptr,
+                                       src ? src[1] + i * stride : nullptr, data3 ? data3 + i * stride : nullptr, src ? src[2] + i * stride : nullptr, end3));
+        return ZK_OK;
+    }
+    const RowArgs R = {stride, 0, 0};
+    std::vector<PassPlan> passes = plan_passes(logn);
+    const size_t npass = passes.size();
+    PassArgs A;
+    A.data = data; A.logn = logn; A.pre = nullptr; A.post = nullptr; A.has_post_const = 0; A.post_const = Fr::zero(); A.tw2 = nullptr;
+    A.sub = nullptr;
+    A.data2 = data2;
+    A.data3 = data2 ? data3 : nullptr;
+    A.src = (src && src[0] != data) ? src[0] : nullptr;  // consumed by whichever pass runs first
+    A.src2 = (src && data2 && src[1] != data2) ? src[1] : nullptr;
+    A.src3 = (src && A.data3 && src[2] != data3) ? src[2] : nullptr;
+    if (A.data3) A.post_const = *end3;
+    const unsigned ny = 1 + (data2 ? 1 : 0) + (A.data3 ? 1 : 0);
+    for (size_t idx = npass - 1; idx >= 1; idx--) {  // strided passes of the inverse transform, top bits first
+        const PassPlan& p = passes[idx];
+        A.tw = dom->tw29_inv; A.bit_lo = p.bit_lo; A.k = p.k; A.logL = p.logL; A.dif = 1; A.canonical = 0;
+        ZK_TRY(launch_pass_rows(s, st, A, R, rows));
+        A.src = nullptr;
+        A.src2 = nullptr;
+        A.src3 = nullptr;
+    }
+    {
+        const PassPlan& p = passes[0];
+        A.tw = dom->tw29_inv; A.tw2 = dom->tw29; A.bit_lo = 0; A.k = p.k; A.logL = 0; A.dif = 1; A.post = mid;
+        A.canonical = (npass == 1) ? 1 : 0;
+        A.tw_and = g_tw_and;
+        A.unit_skip = g_unit_skip;
+        const unsigned E = 1u << p.k;
+        const unsigned tiles = (unsigned)(((size_t)1 << logn) / E);
+        for (size_t r0 = 0; r0 < rows; r0 += ROWS_PER_LAUNCH) {
+            const unsigned nz = (unsigned)std::min(rows - r0, ROWS_PER_LAUNCH);
+            PassArgs B = A;
+            advance_rows(B, R, r0);
+            if (g_ntt_g2) ZK_LAUNCH(s, st, "ntt_pass_contig_if_rows", (k_ntt_pass29_if_rows<2, 512>), dim3(tiles, ny, nz), dim3(512), (size_t)E * 36, B, R);
+            else ZK_LAUNCH(s, st, "ntt_pass_contig_if_rows", (k_ntt_pass29_if_rows<3, 256>), dim3(tiles, ny, nz), dim3(NTT_THREADS), (size_t)E * 36, B, R);
+        }
+        A.post = nullptr;
+        A.tw2 = nullptr;
+        A.src = nullptr;
+        A.src2 = nullptr;
+        A.data3 = nullptr;  // c is done
+        A.src3 = nullptr;
+    }
+    for (size_t idx = 1; idx < npass; idx++) {  // strided passes of the forward transform, low bits first
+        const PassPlan& p = passes[idx];
+        A.tw = dom->tw29; A.bit_lo = p.bit_lo; A.k = p.k; A.logL = p.logL; A.dif = 0; A.canonical = (idx + 1 == npass) ? 1 : 0;
+        ZK_TRY(launch_pass_rows(s, st, A, R, rows));
+    }
+    return ZK_OK;
+}
+
 static std::mutex g_lds_mu;
 static uint64_t g_lds_attr_set = 0;  // bit e: done for device entry e (the attribute belongs to the device's copy of the function)
 static int ensure_lds_attr() {
@@ -678,6 +884,12 @@ static int ensure_lds_attr() {
         ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29<2, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
         ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_if<3, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
         ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_if<2, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
+        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_rows<3, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
+        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_rows<2, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
+        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_rows<3, 256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
+        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_rows<2, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
+        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_if_rows<3, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
+        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_if_rows<2, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
         g_lds_attr_set |= bit;
     }
     return ZK_OK;
@@ -705,11 +917,37 @@ int ntt_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn, int inverse, int de
     return run_passes(s, st, d_a, d, 1, dif, nullptr, post, &cinv);
 }
 
+// ntt_dev on `rows` vectors, row i at d_a + i * row_stride (row_stride >= 2^logn): one launch per pass for all of them
+int ntt_rows_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn, size_t rows, size_t row_stride, int inverse, int decimation, int coset) {
+    if (rows == 0) return ZK_OK;
+    ZK_TRY(ensure_lds_attr());
+    unsigned need = inverse ? DOM_TW_INV : DOM_TW;
+    if (coset) {
+        if (!inverse) need |= (decimation == ZK_DIT) ? DOM_COSET_REV : DOM_COSET;
+        else need |= (decimation == ZK_DIT) ? DOM_COSET_INV_N : DOM_COSET_INV_N_REV;
+    }
+    Domain* d;
+    ZK_TRY(get_domain(s, st, logn, need, &d));
+    const int dif = (decimation == ZK_DIF);
+    if (!inverse) {
+        const Fr* pre = coset ? (dif ? d->coset_tab : d->coset_rev) : nullptr;
+        return run_passes_rows(s, st, d_a, row_stride, rows, d, 0, dif, pre, 0, nullptr, nullptr);
+    }
+    const Fr* post = coset ? (dif ? d->coset_inv_n_rev : d->coset_inv_n) : nullptr;
+    const Fr cinv = to_dev(d->card_inv);
+    return run_passes_rows(s, st, d_a, row_stride, rows, d, 1, dif, nullptr, 0, post, &cinv);
+}
+
 int bit_reverse_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn) {
     size_t n = (size_t)1 << logn;
     ZK_LAUNCH(s, st, "bit_reverse", k_bit_reverse, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d_a, logn);
     return ZK_OK;
 }
+
+// the A/B switches of computeH's schedule (explained where compute_h_inplace uses them)
+static const bool skip_c = (ZK_EXP("ZKMI_H_SKIP_C", 1) != 0);
+static const bool h_batch = ZK_EXP("ZKMI_H_BATCH", 1) == 1;
+static const bool fuse_pw = ZK_EXP("ZKMI_H_FUSE_PW", 1) == 1;
 
 // gnark v0.8.0 computeH on device buffers a (in/out, N), b, c (scratch, N); result left in a, bit-reversed order.
 //   3 x FFTInverse(DIF) ; 3 x FFT(DIT, coset) ; a = (a*b - c) / (g^N - 1) ; FFTInverse(a, DIF, coset)
@@ -728,13 +966,11 @@ int compute_h_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned log
     // By linearity (exact field arithmetic, so bit for bit for ANY input): FFTInverse(coset)((a'b' - c') den) = den (FFTInverse(coset)(a'b') - FFTInverse(c)),
     // where c' = FFT(coset)(FFTInverse(c)) -- the coset transform of c and its way back cancel.  c therefore only needs its first FFTInverse(DIF)
     // (coefficients, bit-reversed like the result): six transforms instead of gnark's seven.  ZKMI_H_SKIP_C=0 restores the literal sequence.
-    static const bool skip_c = (ZK_EXP("ZKMI_H_SKIP_C", 1) != 0);
     if (skip_c && !side && logN > 0) {
         const Fr cinv = to_dev(d->card_inv);
         // a, b (and c for the inverse half) go through their passes in the SAME launches (gridDim.y = vector): at 2^20 a pass is ONE round of workgroups moving
         // in lock-step (load, butterflies, store); with two or three rounds per launch one round's loads and stores run under another's butterflies, and seven
         // launches disappear.  ZKMI_H_BATCH=0 (A/B switch): one vector per launch.
-        static const bool h_batch = ZK_EXP("ZKMI_H_BATCH", 1) == 1;
         if (h_batch) {
             ZK_TRY(run_inverse_forward(s, st, a, d, d->coset_rev_n, src ? src[0] : nullptr, b, src ? src[1] : nullptr, c, src ? src[2] : nullptr, &cinv));
         } else {
@@ -746,7 +982,6 @@ int compute_h_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned log
         const Fr den = to_dev((gN - HFr::one()).inv());
         // the product a*b rides on the loads of the closing transform's first stage (`pre` = b) and (x - c) * den on the stores of its last one (`sub` = c)
         // instead of two element-wise kernels (96 B per element each).  ZKMI_H_FUSE_PW=0 (A/B switch): the two kernels.
-        static const bool fuse_pw = ZK_EXP("ZKMI_H_FUSE_PW", 1) == 1;
         if (fuse_pw && !g_ntt_saturated) return run_passes(s, st, a, d, 1, 1, b, d->coset_inv_n_rev, &den, nullptr, c);
         ZK_LAUNCH(s, st, "fr_mul", k_fr_mul, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, a, (const Fr*)a, (const Fr*)b, N);
         ZK_TRY(run_passes(s, st, a, d, 1, 1, nullptr, d->coset_inv_n_rev, nullptr));
@@ -779,6 +1014,29 @@ int compute_h_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned log
     ZK_LAUNCH(s, st, "h_pointwise", k_h_pointwise, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, a, (const Fr*)b, (const Fr*)c, to_dev(den), N);
     ZK_TRY(run_passes(s, st, a, d, 1, 1, nullptr, d->coset_inv_n_rev, nullptr));
     return ZK_OK;
+}
+
+// compute_h_inplace on `rows` triples, row i at a / b / c + i * row_stride: the six transforms of the production branch above with the row as a grid dimension --
+// as many launches as ONE computeH whatever the row count.  h of row i is left in a + i * row_stride, bit-reversed, as there.
+int compute_h_rows_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned logN, size_t rows, size_t row_stride, const Fr* const* src) {
+    // src (optional): the rows of the three inputs live in src[0..2] (full 2^logN vectors, row_stride apart) and are left untouched
+    if (rows == 0) return ZK_OK;
+    if (!(skip_c && h_batch && fuse_pw) || g_ntt_saturated || logN == 0) {  // the A/B variants and the one-point domain: row by row
+        for (size_t i = 0; i < rows; i++) {
+            const Fr* si[3] = {src ? src[0] + i * row_stride : nullptr, src ? src[1] + i * row_stride : nullptr, src ? src[2] + i * row_stride : nullptr};
+            ZK_TRY(compute_h_inplace(s, st, a + i * row_stride, b + i * row_stride, c + i * row_stride, logN, src ? si : nullptr));
+        }
+        return ZK_OK;
+    }
+    ZK_TRY(ensure_lds_attr());
+    Domain* d;
+    ZK_TRY(get_domain(s, st, logN, DOM_TW | DOM_TW_INV | DOM_COSET_REV_N | DOM_COSET_INV_N_REV, &d));
+    const Fr cinv = to_dev(d->card_inv);
+    ZK_TRY(run_inverse_forward_rows(s, st, a, row_stride, rows, d, d->coset_rev_n, b, c, &cinv, src));
+    HFr gN = d->coset;
+    for (unsigned i = 0; i < logN; i++) gN = gN.sqr();
+    const Fr den = to_dev((gN - HFr::one()).inv());
+    return run_passes_rows(s, st, a, row_stride, rows, d, 1, 1, b, row_stride, d->coset_inv_n_rev, &den, c, row_stride);
 }
 
 int fr_mul_dev(Slot* s, hipStream_t st, Fr* out, const Fr* a, const Fr* b, size_t n) {
@@ -1017,6 +1275,51 @@ int zk_bn254_ntt_devices(zk_fr* a, uint32_t log_n, int inverse, int decimation, 
 }
 int zk_bn254_ntt(zk_fr* a, uint32_t log_n, int inverse, int decimation, int coset) { return zk_bn254_ntt_devices(a, log_n, inverse, decimation, coset, 0); }
 
+// ---- row batches: many vectors of one domain per call (one launch per pass for all rows)
+static constexpr size_t ROWS_SCRATCH = (size_t)1 << 30;  // arena bytes one batch entry takes at a time; more rows than fit go in chunks, on the same slot
+
+static int ntt_batch_args(const void* a, uint32_t log_n, size_t row_stride, int decimation) {
+    if (!a) return set_err(ZK_ERR_ARG, "null data pointer");
+    if (log_n > 28) return set_err(ZK_ERR_ARG, "log_n = %u exceeds Fr two-adicity 28", log_n);
+    if (decimation != ZK_DIT && decimation != ZK_DIF) return set_err(ZK_ERR_ARG, "decimation must be ZK_DIT or ZK_DIF");
+    if (row_stride < ((size_t)1 << log_n)) return set_err(ZK_ERR_ARG, "row_stride = %zu is below the domain size %zu", row_stride, (size_t)1 << log_n);
+    return ZK_OK;
+}
+
+int zk_bn254_ntt_batch_dev(void* d_a, uint32_t log_n, size_t rows, size_t row_stride, int inverse, int decimation, int coset, void* stream) {
+    ZK_TRY(ntt_batch_args(d_a, log_n, row_stride, decimation));
+    if (rows == 0) return ZK_OK;
+    if (rows == 1) return zk_bn254_ntt_dev(d_a, log_n, inverse, decimation, coset, stream);
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    ZK_TRY(ntt_rows_dev(g.s, st, (Fr*)d_a, log_n, rows, row_stride, inverse, decimation, coset));
+    if (!stream || profiling_on()) ZK_TRY(slot_sync(g.s, st));  // in place, no workspace
+    return ZK_OK;
+}
+
+// host rows, contiguous (row i at a + i * 2^log_n); one device: a batch of small transforms is not worth a transpose between GPUs
+int zk_bn254_ntt_batch(zk_fr* a, uint32_t log_n, size_t rows, int inverse, int decimation, int coset) {
+    ZK_TRY(ntt_batch_args(a, log_n, (size_t)-1, decimation));  // contiguous rows: no stride to check
+    if (rows == 0) return ZK_OK;
+    const size_t N = (size_t)1 << log_n, row_bytes = N * 32;
+    const size_t chunk = std::min(rows, std::max<size_t>(1, ROWS_SCRATCH / row_bytes));
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    ZK_TRY(g.s->reserve(chunk * row_bytes));
+    Fr* d = (Fr*)g.s->alloc(chunk * row_bytes);
+    if (!d) return set_err(ZK_ERR_ARG, "ntt batch: workspace");
+    hipStream_t st = g.s->stream;
+    for (size_t first = 0; first < rows; first += chunk) {
+        const size_t R = std::min(chunk, rows - first);
+        char* h = (char*)a + first * row_bytes;
+        ZK_HIP(hipMemcpyAsync(d, h, R * row_bytes, hipMemcpyHostToDevice, st));
+        ZK_TRY(ntt_rows_dev(g.s, st, d, log_n, R, N, inverse, decimation, coset));
+        ZK_HIP(hipMemcpyAsync(h, d, R * row_bytes, hipMemcpyDeviceToHost, st));
+    }
+    return slot_sync(g.s, st);
+}
+
 int zk_bn254_bit_reverse_dev(void* d_a, uint32_t log_n, void* stream) {
     if (!d_a || log_n > 28) return set_err(ZK_ERR_ARG, "bad argument");
     SlotGuard g;
@@ -1081,6 +1384,100 @@ int zk_bn254_groth16_compute_h(const zk_fr* a, const zk_fr* b, const zk_fr* c, s
     }
     ZK_TRY(compute_h_inplace(g.s, st, d[0], d[1], d[2], log_N));
     ZK_HIP(hipMemcpyAsync(h_out, d[0], N * 32, hipMemcpyDeviceToHost, st));
+    return slot_sync(g.s, st);
+}
+
+// rows of `width` bytes: one plain copy where both sides are contiguous, else a pitched one
+static int copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, hipMemcpyKind kind, hipStream_t st) {
+    if (!width || !rows) return ZK_OK;
+    if (rows == 1 || (dpitch == width && spitch == width)) ZK_HIP(hipMemcpyAsync(dst, src, width * rows, kind, st));
+    else ZK_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, kind, st));
+    return ZK_OK;
+}
+static int zero_rows(Fr* dst, size_t pitch_elems, size_t width_elems, size_t rows, hipStream_t st) {
+    if (!width_elems || !rows) return ZK_OK;
+    if (rows == 1 || pitch_elems == width_elems) ZK_HIP(hipMemsetAsync(dst, 0, width_elems * rows * 32, st));
+    else ZK_HIP(hipMemset2DAsync(dst, pitch_elems * 32, 0, width_elems * 32, rows, st));
+    return ZK_OK;
+}
+
+static int compute_h_batch_args(const void* a, const void* b, const void* c, const void* h, size_t n, size_t in_stride, uint32_t log_N, size_t out_stride) {
+    if (!a || !b || !c || !h) return set_err(ZK_ERR_ARG, "null pointer");
+    if (log_N > 28) return set_err(ZK_ERR_ARG, "log_N exceeds 28");
+    const size_t N = (size_t)1 << log_N;
+    if (n > N) return set_err(ZK_ERR_ARG, "n = %zu exceeds the domain size %zu", n, N);
+    if (in_stride < n) return set_err(ZK_ERR_ARG, "in_stride = %zu is below the row length %zu", in_stride, n);
+    if (out_stride < N) return set_err(ZK_ERR_ARG, "out_stride = %zu is below the domain size %zu", out_stride, N);
+    return ZK_OK;
+}
+
+// computeH of `rows` triples resident in HBM.  The a rows are taken to d_h_out (out_stride apart) and transformed there; the b and c rows go to the slot's arena
+// at the same stride, so the row kernels see one stride; the caller's inputs are only read.
+int zk_bn254_groth16_compute_h_batch_dev(const void* d_a, const void* d_b, const void* d_c, size_t n, size_t in_stride, uint32_t log_N, size_t rows, void* d_h_out,
+                                         size_t out_stride, void* stream) {
+    ZK_TRY(compute_h_batch_args(d_a, d_b, d_c, d_h_out, n, in_stride, log_N, out_stride));
+    if (rows == 0) return ZK_OK;
+    const size_t N = (size_t)1 << log_N;
+    // d_h_out may be d_a itself where row i of both is the same memory (one row, or equal strides); any other overlap of the output with an input is refused
+    const bool in_place = d_h_out == d_a && (rows == 1 || in_stride == out_stride);
+    const char* out_lo = (const char*)d_h_out;
+    const char* out_hi = out_lo + ((rows - 1) * out_stride + N) * 32;
+    const void* ins[3] = {d_a, d_b, d_c};
+    for (int i = in_place ? 1 : 0; i < 3; i++) {
+        const char* lo = (const char*)ins[i];
+        const char* hi = lo + ((rows - 1) * in_stride + n) * 32;
+        if (lo < out_hi && out_lo < hi) return set_err(ZK_ERR_ARG, "d_h_out overlaps an input (only d_h_out == d_a with equal strides may alias)");
+    }
+    if (rows == 1) return zk_bn254_groth16_compute_h_dev(d_a, d_b, d_c, n, log_N, d_h_out, stream);
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    const size_t chunk = std::min(rows, std::max<size_t>(1, ROWS_SCRATCH / (2 * out_stride * 32)));
+    Fr *b = nullptr, *c = nullptr;
+    ZK_TRY(plan_workspace(g.s, "computeH batch", [&](ArenaPlan& p) { p.take(chunk * out_stride, b, c); }));
+    // full rows at the output's stride are read where they are by the first pass (its `src`): no staging copy
+    const bool direct = n == N && in_stride == out_stride && log_N > 0;
+    for (size_t first = 0; first < rows; first += chunk) {
+        const size_t R = std::min(chunk, rows - first);
+        Fr* a = (Fr*)d_h_out + first * out_stride;
+        const Fr* src[3];
+        for (int i = 0; i < 3; i++) src[i] = (const Fr*)ins[i] + first * in_stride;
+        if (direct) {
+            ZK_TRY(compute_h_rows_inplace(g.s, st, a, b, c, log_N, R, out_stride, src));
+            continue;
+        }
+        Fr* dst[3] = {a, b, c};
+        for (int i = 0; i < 3; i++) {
+            if ((const Fr*)dst[i] != src[i]) ZK_TRY(copy_rows(dst[i], out_stride * 32, src[i], in_stride * 32, n * 32, R, hipMemcpyDeviceToDevice, st));
+            ZK_TRY(zero_rows(dst[i] + n, out_stride, N - n, R, st));
+        }
+        ZK_TRY(compute_h_rows_inplace(g.s, st, a, b, c, log_N, R, out_stride));
+    }
+    return slot_sync(g.s, st);  // scratch lives in the slot's arena
+}
+
+// host rows, contiguous: a, b, c are (rows, n), h_out is (rows, 2^log_N)
+int zk_bn254_groth16_compute_h_batch(const zk_fr* a, const zk_fr* b, const zk_fr* c, size_t n, uint32_t log_N, size_t rows, zk_fr* h_out) {
+    ZK_TRY(compute_h_batch_args(a, b, c, h_out, n, n, log_N, (size_t)-1));  // contiguous rows: no strides to check
+    if (rows == 0) return ZK_OK;
+    if (rows == 1) return zk_bn254_groth16_compute_h(a, b, c, n, log_N, h_out);
+    const size_t N = (size_t)1 << log_N;
+    const size_t chunk = std::min(rows, std::max<size_t>(1, ROWS_SCRATCH / (3 * N * 32)));
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = g.s->stream;
+    Fr* d[3] = {nullptr, nullptr, nullptr};
+    ZK_TRY(plan_workspace(g.s, "computeH batch", [&](ArenaPlan& p) { p.take(chunk * N, d[0], d[1], d[2]); }));
+    const zk_fr* src[3] = {a, b, c};
+    for (size_t first = 0; first < rows; first += chunk) {
+        const size_t R = std::min(chunk, rows - first);
+        for (int i = 0; i < 3; i++) {
+            ZK_TRY(copy_rows(d[i], N * 32, (const char*)src[i] + first * n * 32, n * 32, n * 32, R, hipMemcpyHostToDevice, st));
+            ZK_TRY(zero_rows(d[i] + n, N, N - n, R, st));
+        }
+        ZK_TRY(compute_h_rows_inplace(g.s, st, d[0], d[1], d[2], log_N, R, N));
+        ZK_HIP(hipMemcpyAsync((char*)h_out + first * N * 32, d[0], R * N * 32, hipMemcpyDeviceToHost, st));
+    }
     return slot_sync(g.s, st);
 }
 

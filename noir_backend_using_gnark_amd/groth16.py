@@ -165,6 +165,27 @@ def compute_h(a, b, c, log_domain: int) -> np.ndarray:
     return h
 
 
+def compute_h_batch(a, b, c, log_domain: int) -> np.ndarray:
+    """computeH of every row of the (rows, n, 4) arrays a, b, c in the launches of one (zk_bn254_groth16_compute_h_batch): (rows, N, 4), row i what compute_h gives
+    for a[i], b[i], c[i].  Shape and dtype errors are raised before the library is called."""
+    for v in (a, b, c):
+        if not (isinstance(v, np.ndarray) and v.dtype == np.uint64):
+            raise TypeError("a, b, c must be uint64 numpy arrays")
+        if v.ndim != 3 or v.shape[2] != 4:
+            raise ValueError("a, b, c must have shape (rows, n, 4), not %s" % (v.shape,))
+    if not (a.shape == b.shape == c.shape):
+        raise ValueError("a, b, c must have the same shape")
+    if not 0 <= int(log_domain) <= 28:
+        raise ValueError("log_domain must be in 0 .. 28")
+    rows, n = a.shape[0], a.shape[1]
+    if n > (1 << log_domain):
+        raise ValueError("n = %d exceeds the domain size %d" % (n, 1 << log_domain))
+    a, b, c = (np.ascontiguousarray(v) for v in (a, b, c))
+    h = np.zeros((rows, 1 << log_domain, 4), dtype=np.uint64)
+    check(lib().zk_bn254_groth16_compute_h_batch(vp(a), vp(b), vp(c), C.c_size_t(n), C.c_uint32(log_domain), C.c_size_t(rows), vp(h)))
+    return h
+
+
 class R1CS:
     """cs.R1CS resident in HBM: constraints (L w) o (R w) = (O w) over the wires [ONE, public..., secret..., internal...]; n_public counts the
     ONE wire (gnark's GetNbPublicVariables).  `constraints`: list of (L, R, O), each a dict wire -> Montgomery coefficient (4 limbs)."""
