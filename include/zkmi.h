@@ -423,6 +423,18 @@ int zk_bn254_groth16_msm5_pk_abort(uint64_t session);
 int zk_bn254_groth16_msm5_session_stream(uint64_t session, void **stream_out);
 int zk_bn254_groth16_finalize(uint64_t pk_handle, const uint64_t *partials, size_t n_partials, const zk_fr *r,
                               const zk_fr *s, uint8_t proof_out[128]);
+/* finalize for MANY rows in one device launch (csrc/groth16_tail.hip): one lane group per row sums the row's records, multiplies delta / delta2 through the
+ * key's 8-bit window tables in HBM (built at the key's first call, freed with the key, counted by zk_bn254_groth16_pk_bytes), computes s*(A + alpha) and
+ * r*(B1 + beta), shares one inversion among the three proof elements and compresses them.
+ * n_proofs rows; partials: row-major n_proofs x n_partials x 96 limbs; r, s: n_proofs elements; proofs_out: 128 bytes per row.
+ * proofs_out[128 i ..] is byte for byte what zk_bn254_groth16_finalize writes for row i.
+ * n_proofs == 0: ZK_OK, nothing written.  A null pointer or n_partials == 0: ZK_ERR_ARG; an unknown key: ZK_ERR_HANDLE.  A key spread over several device
+ * entries finalizes row by row on the host from the host form; the _dev form refuses it with ZK_ERR_ARG.  _dev with `stream`: enqueued behind it, returns
+ * without a sync; with stream == NULL: on a stream of the library's own, returns when the bytes are there.  Both may be called from concurrent threads. */
+int zk_bn254_groth16_finalize_batch(uint64_t pk_handle, const uint64_t *partials, size_t n_partials, const zk_fr *r, const zk_fr *s,
+                                    size_t n_proofs, uint8_t *proofs_out);                      /* host pointers */
+int zk_bn254_groth16_finalize_batch_dev(uint64_t pk_handle, const void *d_partials, size_t n_partials, const void *d_r, const void *d_s,
+                                        size_t n_proofs, void *d_proofs_out, void *stream);      /* device pointers; inputs only read */
 
 /* ---- PLONK: plonk.Setup / plonk.Prove (gnark v0.8.0 internal/backend/bn254/plonk/{setup,prove}.go) ------------------------------
  * The reference's only live prove path: PlonkProveWithPK (gnark_backend_ffi/main.go:24-37) -> plonk.Prove at

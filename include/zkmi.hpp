@@ -189,6 +189,18 @@ inline Error ProveBatch(const ProvingKey& pk, const fr::Vector& a, const fr::Vec
     return make_error(zk_bn254_groth16_prove_batch(pk.handle(), a.data(), b.data(), c.data(), n_constraints, w.data(), pk.NbWires(), r.data(), s.data(), n, 0,
                                                    n ? (*proofs)[0].bytes : nullptr));
 }
+// The second half of Prove for many rows in one device launch (zk_bn254_groth16_finalize_batch): partials holds len(r) rows of n_partials records of 96 limbs
+// (the five un-normalised MSM sums A, B1, K, Z, G2.B of zk_bn254_groth16_msm5_*); proofs[i] is byte for byte what zk_bn254_groth16_finalize writes for row i.
+inline Error FinalizeBatch(const ProvingKey& pk, const std::vector<uint64_t>& partials, size_t n_partials, const fr::Vector& r, const fr::Vector& s,
+                           std::vector<Proof>* proofs) {
+    const size_t n = r.size();
+    if (s.size() != n) return Error{ZK_ERR_LEN, "len(r) != len(s)"};
+    if (n_partials == 0) return Error{ZK_ERR_ARG, "n_partials must be at least 1"};
+    if (partials.size() != n * n_partials * 96) return Error{ZK_ERR_LEN, "partials must hold len(r) rows of n_partials records of 96 limbs"};
+    proofs->resize(n);
+    static_assert(sizeof(Proof) == 128, "proofs are written back to back");
+    return make_error(zk_bn254_groth16_finalize_batch(pk.handle(), partials.data(), n_partials, r.data(), s.data(), n, n ? (*proofs)[0].bytes : nullptr));
+}
 
 }  // namespace groth16
 

@@ -20,6 +20,7 @@
 
 #include "ctx.hpp"
 #include "curve.hpp"
+#include "fixedbase.hpp"
 #include "groth16_batch.hpp"
 #include "host_ff.hpp"
 #include "keyio.hpp"
@@ -77,6 +78,8 @@ struct Groth16PK {
     bool tables = false;
     MsmTable tab_w, tab_h;
     void *t_a = nullptr, *t_b = nullptr, *t_k = nullptr, *t_z = nullptr, *t_b2 = nullptr;
+    // 8-bit window tables of delta / delta2 in HBM for the device tail (groth16_tail.hip): built at the key's first device tail (groth16_pk_tail_view)
+    void *d_fb_delta = nullptr, *d_fb_delta2 = nullptr;
 };
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static std::mutex g_pk_mu;
@@ -300,6 +303,8 @@ int zk_bn254_groth16_pk_free(uint64_t handle) {
     }
     if (P.tables)
         for (void* d : {P.t_a, P.t_b, P.t_k, P.t_z, P.t_b2}) (void)hipFree(d);
+    for (void* d : {P.d_fb_delta, P.d_fb_delta2})
+        if (d) (void)hipFree(d);
     g_pks.erase(it);
     return ZK_OK;
 }
@@ -350,6 +355,7 @@ int zk_bn254_groth16_pk_bytes(uint64_t handle, size_t* bytes) {
     if (P.owns) b += nw * (64 + 64 + 128) + nk * 64 + N * 64;
     else if (P.owns_abb) b += nw * (64 + 64 + 128);
     if (P.tables) b += (size_t)P.tab_w.rows() * nw * (3 * 64 + 128) + (size_t)P.tab_h.rows() * N * 64;
+    if (P.d_fb_delta) b += FIXED_BASE_TABLE_POINTS * (64 + 128);
     *bytes = b;
     return ZK_OK;
 }
@@ -388,6 +394,45 @@ int groth16_pk_batch_view(uint64_t handle, Groth16BatchView* v) {
     v->tables = P.tables;
     v->tab_w = P.tab_w; v->tab_h = P.tab_h;
     v->t_a = P.t_a; v->t_b = P.t_b; v->t_k = P.t_k; v->t_z = P.t_z; v->t_b2 = P.t_b2;
+    return ZK_OK;
+}
+// what the device tail needs of a key.  The window tables of delta / delta2 are built here at the key's first device tail (host arithmetic, a few tens of ms,
+// then one upload) under a mutex of their own: two threads that race a fresh key build ONE set, and a key's table never serves another key (it hangs off the
+// key's own record).  g_pk_mu is not held while building; a key freed meanwhile takes its tables with it here.
+static std::mutex g_tail_tab_mu;
+int groth16_pk_tail_view(uint64_t handle, Groth16TailView* v) {
+    std::lock_guard<std::mutex> build_lk(g_tail_tab_mu);
+    Groth16PK P;
+    {
+        std::lock_guard<std::mutex> lk(g_pk_mu);
+        auto it = g_pks.find(handle);
+        if (it == g_pks.end()) return set_err(ZK_ERR_HANDLE, "unknown proving-key handle %llu", (unsigned long long)handle);
+        P = it->second;
+    }
+    if (!P.d_fb_delta) {
+        Affine<Fp> d1;
+        Affine<Fp2> d2;
+        memcpy(&d1, &P.delta, sizeof d1);
+        memcpy(&d2, &P.delta2, sizeof d2);
+        Affine<Fp>* t1 = nullptr;
+        Affine<Fp2>* t2 = nullptr;
+        ZK_TRY(fixed_base_table_g1(d1, &t1));
+        const int rc = fixed_base_table_g2(d2, &t2);
+        std::lock_guard<std::mutex> lk(g_pk_mu);
+        auto it = g_pks.find(handle);
+        if (rc != ZK_OK || it == g_pks.end()) {
+            (void)hipFree(t1);
+            if (t2) (void)hipFree(t2);
+            return rc != ZK_OK ? rc : set_err(ZK_ERR_HANDLE, "unknown proving-key handle %llu", (unsigned long long)handle);
+        }
+        it->second.d_fb_delta = P.d_fb_delta = t1;
+        it->second.d_fb_delta2 = P.d_fb_delta2 = t2;
+    }
+    memcpy(&v->alpha, &P.alpha, sizeof v->alpha);
+    memcpy(&v->beta, &P.beta, sizeof v->beta);
+    memcpy(&v->beta2, &P.beta2, sizeof v->beta2);
+    v->t_delta = P.d_fb_delta;
+    v->t_delta2 = P.d_fb_delta2;
     return ZK_OK;
 }
 }  // namespace zkmi

@@ -9,7 +9,8 @@
 //   * one accumulate launch per base array -- G2.B, A, B1, K, Z, chained as in the single prover -- over S bucket sets, and one reduction that yields S sums;
 //   * the R1CS step (prove_r1cs_batch) as one launch with the row as a grid dimension (r1cs.hip k_spmv3_rows);
 //   * computeH of the whole chunk in the launches of ONE computeH (ntt.hip compute_h_rows_inplace: the row is a grid dimension of every pass);
-//   * the host tail per row on a few host threads (not batched yet: DESIGN.md 3.12).
+//   * the tail -- five sums + (r, s) -> 128 proof bytes -- of all S rows in ONE launch (groth16_tail.hip) for domains up to DEVICE_TAIL_MAX_LOG_DOMAIN, on a few
+//     host threads per row above it (DESIGN.md 3.12 says where that constant comes from).
 #include <string.h>
 
 #include <algorithm>
@@ -30,6 +31,12 @@ namespace zkmi {
 static constexpr unsigned BATCH_MAX_LOG_DOMAIN = 16;
 static constexpr size_t BATCH_MAX_ROWS = 256;
 static constexpr size_t BATCH_WORKSPACE = (size_t)1 << 30;
+// Largest domain whose chunks take the device tail (groth16_tail.hip); above it the rows' tails stay on host threads.  The rule is the parent / this-commit
+// table of tools/groth16_batch_bench.py: the device tail serves a size only where the batch time stayed within the 3 % run-to-run band of the
+// parent's.  That table has NOT been measured yet, and the estimate in DESIGN.md 3.12 (one launch costs the latency of a 254-bit double-and-add chain, about
+// 4 ms, whatever S is; the host tail costs S x 0.35 ms / 8 threads) favours the host below 128 rows per chunk: until the table exists no size takes the device
+// tail here (0: every domain is above it).  The public entries (zk_bn254_groth16_finalize_batch[_dev]) do not depend on this.
+static constexpr unsigned DEVICE_TAIL_MAX_LOG_DOMAIN = 0;
 static const zk_msm_cfg kMontCfg = {0, 1, 0, 0};  // scalars are Montgomery fr.Element images
 
 // Which keys the batched path serves.  It needs ONE device's window tables with every window in one bucket set per row, so: not a composite (multi-device) key,
@@ -77,10 +84,41 @@ struct BatchIn {
     int on_device;
 };
 
+// The tail per row on the host like the single prover's (zk_bn254_groth16_finalize: the same arithmetic from the same five sums), over a few threads: two
+// 254-bit scalar multiplications per proof in ONE thread would bound a batch's rate whatever the kernels do.  Serves the domains above DEVICE_TAIL_MAX_LOG_DOMAIN.
+static int host_tail(uint64_t pk_handle, const BatchIn& in, size_t first, size_t S, const XYZZ<HFp>* m_a, const XYZZ<HFp>* m_b, const XYZZ<HFp>* m_k,
+                     const XYZZ<HFp>* m_z, const XYZZ<HFp2>* m_b2, uint8_t* proofs_out) {
+    const unsigned nthreads = (unsigned)std::min<size_t>(8, (S + 3) / 4);
+    std::vector<int> rcs(nthreads, ZK_OK);
+    std::vector<std::string> msgs(nthreads);
+    auto work = [&](unsigned t) {
+        for (size_t i = t; i < S; i += nthreads) {
+            uint64_t parts[96];
+            memcpy(parts, &m_a[i], 128);
+            memcpy(parts + 16, &m_b[i], 128);
+            memcpy(parts + 32, &m_k[i], 128);
+            memcpy(parts + 48, &m_z[i], 128);
+            memcpy(parts + 64, &m_b2[i], 256);
+            const int r1 = zk_bn254_groth16_finalize(pk_handle, parts, 1, in.r + first + i, in.s + first + i, proofs_out + 128 * (first + i));
+            if (r1 != ZK_OK && rcs[t] == ZK_OK) { rcs[t] = r1; msgs[t] = g_err; }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned t = 1; t < nthreads; t++) pool.emplace_back(work, t);
+    work(0);
+    for (auto& th : pool) th.join();
+    for (unsigned t = 0; t < nthreads; t++)
+        if (rcs[t] != ZK_OK) return set_err(rcs[t], "%s", msgs[t].c_str());
+    return ZK_OK;
+}
+
 // one chunk of S rows starting at row `first`, on the call's five slots
 static int prove_chunk(uint64_t pk_handle, const Groth16BatchView& V, Slot* sl[5], const BatchIn& in, size_t first, size_t S, uint8_t* proofs_out) {
     const size_t N = (size_t)1 << V.log_domain, nw = V.n_wires, nc = in.n_constraints;
     for (int i = 0; i < 5; i++) sl[i]->reset();
+    const bool device_tail = V.log_domain <= DEVICE_TAIL_MAX_LOG_DOMAIN;
+    Groth16TailView tail_view;
+    if (device_tail) ZK_TRY(groth16_pk_tail_view(pk_handle, &tail_view));  // (a key's first device tail builds its delta tables: before anything is enqueued)
     BatchNeed need;
     ZK_TRY(batch_need(V, S, &need));
     Fr *d_a = nullptr, *d_b = nullptr, *d_c = nullptr, *d_w = nullptr;
@@ -150,30 +188,34 @@ static int prove_chunk(uint64_t pk_handle, const Groth16BatchView& V, Slot* sl[5
         if (jobs[i].acc_done) (void)hipEventDestroy(jobs[i].acc_done);
     if (ev_h) (void)hipEventDestroy(ev_h);
     ZK_TRY(rc);
-    // ---- the tail of groth16.Prove per row, on the host like the single prover's (zk_bn254_groth16_finalize: the same arithmetic from the same five sums), over a
-    // few threads: two 254-bit scalar multiplications per proof in ONE thread would bound a batch's rate whatever the kernels do
-    const unsigned nthreads = (unsigned)std::min<size_t>(8, (S + 3) / 4);
-    std::vector<int> rcs(nthreads, ZK_OK);
-    std::vector<std::string> msgs(nthreads);
-    auto work = [&](unsigned t) {
-        for (size_t i = t; i < S; i += nthreads) {
-            uint64_t parts[96];
-            memcpy(parts, &m_a[i], 128);
-            memcpy(parts + 16, &m_b[i], 128);
-            memcpy(parts + 32, &m_k[i], 128);
-            memcpy(parts + 48, &m_z[i], 128);
-            memcpy(parts + 64, &m_b2[i], 256);
-            const int r1 = zk_bn254_groth16_finalize(pk_handle, parts, 1, in.r + first + i, in.s + first + i, proofs_out + 128 * (first + i));
-            if (r1 != ZK_OK && rcs[t] == ZK_OK) { rcs[t] = r1; msgs[t] = g_err; }
-        }
-    };
-    std::vector<std::thread> pool;
-    for (unsigned t = 1; t < nthreads; t++) pool.emplace_back(work, t);
-    work(0);
-    for (auto& th : pool) th.join();
-    for (unsigned t = 0; t < nthreads; t++)
-        if (rcs[t] != ZK_OK) return set_err(rcs[t], "%s", msgs[t].c_str());
-    return ZK_OK;
+    // ---- the tail of groth16.Prove.  msm_*_finish_sets finished the last reduction step on the host, so the sums are host data: S x 768 bytes go up with the
+    // r, s slices, ONE launch computes the S tails (groth16_tail.hip), S x 128 bytes come back.  The slots' streams are idle by now: slot 0's arena is free again.
+    if (!device_tail) return host_tail(pk_handle, in, first, S, m_a.data(), m_b.data(), m_k.data(), m_z.data(), m_b2.data(), proofs_out);
+    uint64_t* d_parts = nullptr;
+    Fr *d_r = nullptr, *d_s = nullptr;
+    uint8_t* d_out = nullptr;
+    sl[0]->reset();
+    ZK_TRY(plan_workspace(sl[0], "groth16 batch tail", [&](ArenaPlan& p) {
+        p.take(S * 96, d_parts);
+        p.take(S, d_r, d_s);
+        p.take(S * 128, d_out);
+    }));
+    std::vector<uint64_t> parts(S * 96);
+    for (size_t i = 0; i < S; i++) {
+        uint64_t* q = parts.data() + 96 * i;
+        memcpy(q, &m_a[i], 128);
+        memcpy(q + 16, &m_b[i], 128);
+        memcpy(q + 32, &m_k[i], 128);
+        memcpy(q + 48, &m_z[i], 128);
+        memcpy(q + 64, &m_b2[i], 256);
+    }
+    ZK_HIP(hipMemcpyAsync(d_parts, parts.data(), S * 768, hipMemcpyHostToDevice, st0));
+    ZK_HIP(hipMemcpyAsync(d_r, in.r + first, S * 32, hipMemcpyHostToDevice, st0));
+    ZK_HIP(hipMemcpyAsync(d_s, in.s + first, S * 32, hipMemcpyHostToDevice, st0));
+    rc = groth16_tail_rows(sl[0], st0, tail_view, d_parts, 1, d_r, d_s, S, d_out);
+    if (rc == ZK_OK && hipMemcpyAsync(proofs_out + 128 * first, d_out, S * 128, hipMemcpyDeviceToHost, st0) != hipSuccess) rc = set_err(ZK_ERR_HIP, "proof download failed");
+    const int rc_sync = slot_sync(sl[0], st0);  // also on an error: what was enqueued drains before `parts` goes
+    return rc != ZK_OK ? rc : rc_sync;
 }
 
 }  // namespace zkmi

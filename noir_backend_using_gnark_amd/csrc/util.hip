@@ -184,6 +184,8 @@ static int fixed_base_table(const Affine<F>& gen_dev, Affine<F>** d_out) {
     ZK_HIP(hipMemcpy(*d_out, aff.data(), aff.size() * sizeof(Affine<F>), hipMemcpyHostToDevice));
     return ZK_OK;
 }
+int fixed_base_table_g1(const Affine<Fp>& base, Affine<Fp>** d_out) { return fixed_base_table<HFp, Fp>(base, d_out); }
+int fixed_base_table_g2(const Affine<Fp2>& base, Affine<Fp2>** d_out) { return fixed_base_table<HFp2, Fp2>(base, d_out); }
 static std::mutex g_fb_mu;
 static Affine<Fp>* g_fb_g1s[MAX_ENTRIES] = {};   // per device entry
 static Affine<Fp2>* g_fb_g2s[MAX_ENTRIES] = {};

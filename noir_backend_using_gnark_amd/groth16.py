@@ -312,6 +312,25 @@ def prove_batch(pk: ProvingKey, a, b, c, w, r, s, on_device: bool = False, n_con
     return [raw[128 * i:128 * i + 128] for i in range(n)]
 
 
+def finalize_batch(pk: ProvingKey, partials, r, s) -> list:
+    """The second half of prove() for many rows in one device launch (zk_bn254_groth16_finalize_batch): partials (n_proofs, n_partials, 96) -- or (n_proofs, 96)
+    for one record per row -- of uint64 limbs as zk_bn254_groth16_msm5_* writes them (A, B1, K, Z as G1 XYZZ, then G2.B), r, s (n_proofs, 4) -> one 128-byte
+    proof per row, each byte for byte what parallel.groth16_finalize returns for that row."""
+    partials = np.ascontiguousarray(partials, dtype=np.uint64)
+    if partials.ndim == 2:
+        partials = partials.reshape(partials.shape[0], 1, partials.shape[1])
+    if partials.ndim != 3 or partials.shape[2] != 96:
+        raise ValueError("partials must have the shape (n_proofs, n_partials, 96) or (n_proofs, 96)")
+    n, n_partials = partials.shape[0], partials.shape[1]
+    if n and n_partials == 0:
+        raise ValueError("a row needs at least one record")
+    r, s = _rs_rows(r, s, n)
+    proofs = (C.c_uint8 * (128 * max(n, 1)))()
+    check(lib().zk_bn254_groth16_finalize_batch(pk.handle, vp(partials), C.c_size_t(n_partials), vp(r), vp(s), C.c_size_t(n), proofs))
+    raw = bytes(proofs)
+    return [raw[128 * i:128 * i + 128] for i in range(n)]
+
+
 def prove_r1cs_batch(r1cs: R1CS, pk: ProvingKey, w, r, s) -> list:
     """groth16.Prove(r1cs, pk, witness) for many witnesses: w (rows, n_wires, 4) -> one proof per row, each what prove_r1cs() returns for it."""
     w = _rows(w, "w")
