@@ -498,6 +498,37 @@ int zk_bn254_plonk_prove(uint64_t pk_handle, const void *solution, size_t n_vars
 int zk_bn254_plonk_synth_qk_dev(void *d_qk, const void *d_ql, const void *d_qr, const void *d_qo, const void *d_qm, const void *d_xa,
                                 const void *d_xb, const void *d_xc, const void *d_solution, size_t n_constraints, void *stream);
 
+/* ---- iop: the copy-constraint ratio (gnark-crypto ecc/bn254/fr/iop BuildRatioCopyConstraint, round 2 of plonk.Prove) for MANY witnesses of one domain -----
+ * For `rows` triples l, r, o in Lagrange form, regular order, over the domain of 2^log_n points, and one permutation of the 3 * 2^log_n wire slots:
+ *     num_i = prod_j (w_j(i) + beta u^j omega^i + gamma)        den_i = prod_j (w_j(i) + beta sigma_j(i) + gamma)        z[0] = 1,  z[i+1] = z[i] num_i / den_i
+ * with u the domain's multiplicative generator (fft.Domain.FrMultiplicativeGen, as getSupportIdentityPermutation shifts the three copies) and sigma_j(i) =
+ * id(perm[j n + i]), id(p) = u^(p / n) omega^(p mod n).  Z comes back in Lagrange form, regular order.  fr.BatchInvert's rule holds: the inverse of 0 is 0, so
+ * a zero num_i or den_i makes every later z zero, as upstream's rolling products do.  Every row has its own challenges: beta[v], gamma[v].
+ * Row v of l, r, o starts at element v * in_stride (in_stride >= n), row v of Z at element v * out_stride (out_stride >= n); the inputs are only read and
+ * elements between the rows are not touched.  The row is a grid dimension: one launch per step for all rows (three launches in all up to n = 2^11, five
+ * above), against five small launches per witness.  One row runs the five launches of zk_bn254_plonk_prove's own round 2, and row v of a batch is bit for bit
+ * the one-row call on that row.
+ * INPUT CONTRACT, each entry below: every field element in and out is a canonical fr.Element image in Montgomery form (< r); another 256-bit word gives an
+ * undefined result.
+ * ARGUMENT ERRORS, each entry below, decided before a device is looked for: a null pointer, log_n > 28, in_stride or out_stride below n, d_z overlapping an
+ * input -> ZK_ERR_ARG; an unknown key -> ZK_ERR_HANDLE; rows == 0 (n == 0 for the inversion) -> ZK_OK, nothing happens.
+ * STREAMS: the workspace of these entries is the slot's arena, which the next call reuses, so they synchronise `stream` (NULL: the slot's own) before they
+ * return, as zk_bn254_groth16_compute_h_batch_dev does.  At most 1 GiB of workspace at a time: more rows than fit run in chunks.
+ *   zk_bn254_iop_sigma_dev             3n uint32 positions (gnark's pk.Permutation, L | R | O) -> the 3n elements S1 | S2 | S3 in Lagrange form: sigma above.
+ *                                      ZK_ERR_ARG if an entry is >= 3n (d_sigma is then undefined).
+ *   zk_bn254_iop_ratio_copy_batch_dev  device rows; d_sigma as zk_bn254_iop_sigma_dev leaves it; d_beta, d_gamma: `rows` device elements each.
+ *   zk_bn254_iop_ratio_copy_batch      host arrays, contiguous rows: l, r, o, z_out (rows, n); perm 3n positions; beta, gamma `rows` elements.
+ *   zk_bn254_plonk_ratio_batch_dev     the same through a resident PLONK key: its permutation, its domain and that domain's twiddles (n = the key's domain).
+ *   zk_bn254_fr_batch_invert_dev       fr.BatchInvert in place on n device elements: a[i] <- 1 / a[i], zeros stay zeros. */
+int zk_bn254_iop_sigma_dev(const void *d_perm, uint32_t log_n, void *d_sigma, void *stream);
+int zk_bn254_iop_ratio_copy_batch_dev(const void *d_l, const void *d_r, const void *d_o, size_t in_stride, uint32_t log_n, size_t rows, const void *d_sigma,
+                                      const void *d_beta, const void *d_gamma, void *d_z, size_t out_stride, void *stream);
+int zk_bn254_iop_ratio_copy_batch(const zk_fr *l, const zk_fr *r, const zk_fr *o, uint32_t log_n, size_t rows, const uint32_t *perm, const zk_fr *beta,
+                                  const zk_fr *gamma, zk_fr *z_out);
+int zk_bn254_plonk_ratio_batch_dev(uint64_t pk_handle, const void *d_l, const void *d_r, const void *d_o, size_t in_stride, size_t rows, const void *d_beta,
+                                   const void *d_gamma, void *d_z, size_t out_stride, void *stream);
+int zk_bn254_fr_batch_invert_dev(void *d_a, size_t n, void *stream);
+
 /* ---- the callers either side of the PLONK path: the reference's exported entry points, restated over the device path -----------------------
  * PlonkPreprocess (gnark_backend_ffi/main.go:58-78) and PlonkProveWithPK (main.go:24-37) take the ACIR as JSON (acir/acir.go:17-75), the witness
  * values as the hex felt vector (internal/backend/helpers.go:24-33) and the key as hex of ProvingKey.WriteTo (helpers.go:49-60, 82-87); the

@@ -3,6 +3,7 @@
 // INTEGRATION.md, line for line -- writes: same names, same argument meaning, same error behaviour as
 //   gnark-crypto v0.9.1  ecc/bn254  (*G1Affine).MultiExp / (*G2Affine).MultiExp, ecc.MultiExpConfig      [REF gnark_backend_ffi/go.mod:5]
 //   gnark-crypto v0.9.1  ecc/bn254/fr/fft  NewDomain, (*Domain).FFT / FFTInverse, BitReverse, Decimation
+//   gnark-crypto v0.9.1  ecc/bn254/fr/iop  BuildRatioCopyConstraint (three entries, Lagrange regular), and its form for many witnesses
 //   gnark v0.8.0         groth16.Prove (with the prover randomness as arguments)                          [REF gnark_backend_ffi/main.go:131]
 //   the reference's      DeserializeFelts                                                                 [REF internal/backend/helpers.go:24-33]
 // Go's `(value, error)` returns become `Error` return values (nil == ok()); nothing throws.
@@ -117,6 +118,31 @@ inline Error BitReverse(fr::Vector& a) {
 }
 
 }  // namespace fft
+
+namespace iop {
+
+// iop.BuildRatioCopyConstraint(entries = {l, r, o}, permutation, beta, gamma, expectedForm = {Lagrange, Regular}, domain) for `rows` witnesses of one domain
+// in one call (zk_bn254_iop_ratio_copy_batch): l, r, o hold rows x Cardinality values row-major, permutation the 3 x Cardinality positions (L | R | O) that
+// every row shares, beta and gamma one challenge per row; z is resized to rows x Cardinality.  No upstream counterpart takes rows.
+inline Error BuildRatioCopyConstraintBatch(const fr::Vector& l, const fr::Vector& r, const fr::Vector& o, size_t rows, const std::vector<uint32_t>& permutation,
+                                           const fr::Vector& beta, const fr::Vector& gamma, const fft::Domain& domain, fr::Vector& z) {
+    const uint64_t n = domain.Cardinality;
+    uint32_t log_n = 0;
+    while ((uint64_t(1) << log_n) < n) log_n++;
+    if (l.size() != rows * n || r.size() != rows * n || o.size() != rows * n) return Error{ZK_ERR_ARG, "len(entry) != rows * domain.Cardinality"};
+    if (permutation.size() != 3 * n) return Error{ZK_ERR_ARG, "len(permutation) != 3 * domain.Cardinality"};
+    if (beta.size() != rows || gamma.size() != rows) return Error{ZK_ERR_ARG, "one beta and one gamma per row"};
+    z.resize(rows * n);
+    if (rows == 0) return Error{};
+    return make_error(zk_bn254_iop_ratio_copy_batch(l.data(), r.data(), o.data(), log_n, rows, permutation.data(), beta.data(), gamma.data(), z.data()));
+}
+// the upstream call: one witness
+inline Error BuildRatioCopyConstraint(const fr::Vector& l, const fr::Vector& r, const fr::Vector& o, const std::vector<uint32_t>& permutation, const fr::Element& beta,
+                                      const fr::Element& gamma, const fft::Domain& domain, fr::Vector& z) {
+    return BuildRatioCopyConstraintBatch(l, r, o, 1, permutation, fr::Vector(1, beta), fr::Vector(1, gamma), domain, z);
+}
+
+}  // namespace iop
 
 namespace groth16 {
 

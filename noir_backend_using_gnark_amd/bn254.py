@@ -290,3 +290,32 @@ def bit_reverse(a):
         raise ValueError("BitReverse needs a power-of-two length")
     check(lib().zk_bn254_bit_reverse(vp(a), C.c_uint32(log_n)))
     return a
+
+
+def fr_batch_invert(a, n: int | None = None):
+    """fr.BatchInvert(a): every element's inverse, zeros stay zeros (zk_bn254_fr_batch_invert_dev).  An (n, 4) uint64 array of Montgomery images gives a new
+    array; a device buffer / pointer together with n is inverted in place and returned."""
+    if isinstance(a, (int, _lib.DeviceBuffer)):
+        if n is None:
+            raise ValueError("n is required with device-resident data")
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must not be negative")
+        if isinstance(a, _lib.DeviceBuffer) and n * 32 > a.nbytes:
+            raise ValueError("%d elements do not fit the device buffer (%d bytes)" % (n, a.nbytes))
+        check(lib().zk_bn254_fr_batch_invert_dev(C.c_void_p(a if isinstance(a, int) else a.ptr), C.c_size_t(n), C.c_void_p(0)))
+        return a
+    if not (isinstance(a, np.ndarray) and a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"]):
+        raise TypeError("needs a C-contiguous uint64 numpy array (or a device buffer)")
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError("a has shape %s, not (n, 4)" % (a.shape,))
+    if n is not None and int(n) != a.shape[0]:
+        raise ValueError("n = %d != %d elements of the array" % (n, a.shape[0]))
+    if a.shape[0] == 0:
+        return a.copy()
+    d = _lib.DeviceBuffer.from_numpy(a)
+    try:
+        check(lib().zk_bn254_fr_batch_invert_dev(C.c_void_p(d.ptr), C.c_size_t(a.shape[0]), C.c_void_p(0)))
+        return d.to_numpy(np.uint64, a.shape)
+    finally:
+        d.free()

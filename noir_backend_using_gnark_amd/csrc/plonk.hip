@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <functional>
 #include <memory>
@@ -191,6 +192,136 @@ __global__ __launch_bounds__(256) void k_pscan_apply(const Fr* __restrict__ num,
     size_t gt = (size_t)blockIdx.x * 256 + threadIdx.x, base = gt * K;
     if (base >= n) return;
     Fr p = ld(bexcl + blockIdx.x) * ld(texcl + gt);
+    for (uint32_t k = 0; k < K; k++) {
+        size_t i = base + k;
+        if (i >= n) break;
+        z[i] = p;
+        p = p * (ld(num + i) * ld(dinv + i));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ row form of the ratio (ratio_rows_dev below)
+// The kernels above with the ROW as a grid dimension: R witnesses of one domain, every row with its own challenges.  num / den of a chunk of rows are ONE flat
+// array (row v at v * n), so k_batch_inverse serves all rows in one launch as it is.  An edit of a kernel above belongs in its row form.
+// omega^k as omega_pow, also for the domain of one element (whose half table holds omega^0 alone)
+__device__ __forceinline__ Fr omega_pow_any(const Fr* __restrict__ tw, uint32_t k, uint32_t n) { return n > 1 ? omega_pow(tw, k, n) : Fr::one(); }
+// k_sigma_lagrange for a caller's permutation: an entry >= 3n raises bit 8 of *status (and counts as 0), as k_perm_from_be does it
+__global__ void k_sigma_lagrange_checked(const uint32_t* __restrict__ perm, const Fr* __restrict__ tw, uint32_t n, Fr u, Fr uu, Fr* __restrict__ out,
+                                         int* __restrict__ status) {
+    size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= 3 * (size_t)n) return;
+    uint32_t p = perm[idx];
+    if (p >= 3 * (size_t)n) { atomicOr(status, 8); p = 0; }
+    uint32_t j = p / n, k = p - j * n;
+    Fr w = omega_pow_any(tw, k, n);
+    if (j == 1) w = w * u;
+    else if (j == 2) w = w * uu;
+    out[idx] = w;
+}
+// k_z_terms, row blockIdx.y: wires at l / r / o + row * in_stride, challenges beta[row], gamma[row].  beta u omega^i is formed as u (beta omega^i): the
+// three products of k_z_terms, with u and u^2 as the launch's constants instead of beta u and beta u^2
+__global__ void k_z_terms_rows(const Fr* __restrict__ l, const Fr* __restrict__ r, const Fr* __restrict__ o, size_t in_stride, const Fr* __restrict__ sig,
+                               const Fr* __restrict__ tw, uint32_t n, const Fr* __restrict__ beta_v, const Fr* __restrict__ gamma_v, Fr u, Fr uu,
+                               Fr* __restrict__ num, Fr* __restrict__ den) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t row = blockIdx.y, in = row * in_stride + i, out = row * n + i;
+    const Fr beta = ld(beta_v + row), gamma = ld(gamma_v + row);
+    Fr lv = ld(l + in) + gamma, rv = ld(r + in) + gamma, ov = ld(o + in) + gamma;
+    Fr w = beta * omega_pow_any(tw, i, n);
+    num[out] = (lv + w) * (rv + u * w) * (ov + uu * w);
+    den[out] = (lv + beta * ld(sig + i)) * (rv + beta * ld(sig + n + i)) * (ov + beta * ld(sig + 2 * (size_t)n + i));
+}
+// inclusive product scan of one value per lane over a workgroup of 256 (Hillis-Steele in LDS, the loop of k_pscan_local): the caller's lane gets its
+// EXCLUSIVE prefix, *total (lane 255's inclusive value) is valid in lane 255
+__device__ __forceinline__ Fr pscan_wg256(Fr* sh, Fr tot, Fr* total) {
+    sh[threadIdx.x] = tot;
+    __syncthreads();
+    Fr inc = tot;
+    for (unsigned d = 1; d < 256; d <<= 1) {
+        Fr o = threadIdx.x >= d ? sh[threadIdx.x - d] : Fr::one();
+        __syncthreads();
+        inc = inc * o;
+        sh[threadIdx.x] = inc;
+        __syncthreads();
+    }
+    *total = inc;
+    return threadIdx.x ? sh[threadIdx.x - 1] : Fr::one();
+}
+// k_pscan_local, row blockIdx.y: num / dinv rows n apart, lane prefixes nb * 256 apart, block totals nb apart (nb = gridDim.x)
+__global__ __launch_bounds__(256) void k_pscan_local_rows(const Fr* __restrict__ num, const Fr* __restrict__ dinv, uint32_t n, uint32_t K, Fr* __restrict__ texcl,
+                                                          Fr* __restrict__ btot) {
+    __shared__ Fr sh[256];
+    const size_t row = blockIdx.y, gt = (size_t)blockIdx.x * 256 + threadIdx.x, base = gt * K;
+    num += row * n;
+    dinv += row * n;
+    Fr tot = Fr::one();
+    for (uint32_t k = 0; k < K; k++) {
+        size_t i = base + k;
+        if (i < n) tot = tot * (ld(num + i) * ld(dinv + i));
+    }
+    Fr inc;
+    const Fr excl = pscan_wg256(sh, tot, &inc);
+    texcl[row * gridDim.x * 256 + gt] = excl;
+    if (threadIdx.x == 255) btot[row * gridDim.x + blockIdx.x] = inc;
+}
+// k_pscan_blocks, one workgroup per row: row blockIdx.x's nb block totals in place
+__global__ __launch_bounds__(1024) void k_pscan_blocks_rows(Fr* __restrict__ btot, uint32_t nb) {
+    __shared__ Fr sh[1024];
+    btot += (size_t)blockIdx.x * nb;
+    Fr carry = Fr::one();
+    for (uint32_t c0 = 0; c0 < nb; c0 += 1024) {
+        uint32_t b = c0 + threadIdx.x;
+        Fr v = b < nb ? ld(btot + b) : Fr::one();
+        sh[threadIdx.x] = v;
+        __syncthreads();
+        Fr inc = v;
+        for (unsigned d = 1; d < 1024; d <<= 1) {
+            Fr o = threadIdx.x >= d ? sh[threadIdx.x - d] : Fr::one();
+            __syncthreads();
+            inc = inc * o;
+            sh[threadIdx.x] = inc;
+            __syncthreads();
+        }
+        Fr excl = carry * (threadIdx.x ? sh[threadIdx.x - 1] : Fr::one());
+        Fr total = sh[1023];
+        __syncthreads();
+        if (b < nb) btot[b] = excl;
+        carry = carry * total;
+    }
+}
+// k_pscan_apply, row blockIdx.y: row v's n values of Z to z + v * out_stride
+__global__ __launch_bounds__(256) void k_pscan_apply_rows(const Fr* __restrict__ num, const Fr* __restrict__ dinv, uint32_t n, uint32_t K, const Fr* __restrict__ texcl,
+                                                          const Fr* __restrict__ bexcl, Fr* __restrict__ z, size_t out_stride) {
+    const size_t row = blockIdx.y, gt = (size_t)blockIdx.x * 256 + threadIdx.x, base = gt * K;
+    if (base >= n) return;
+    num += row * n;
+    dinv += row * n;
+    z += row * out_stride;
+    Fr p = ld(bexcl + row * gridDim.x + blockIdx.x) * ld(texcl + row * gridDim.x * 256 + gt);
+    for (uint32_t k = 0; k < K; k++) {
+        size_t i = base + k;
+        if (i >= n) break;
+        z[i] = p;
+        p = p * (ld(num + i) * ld(dinv + i));
+    }
+}
+// A row that is ONE scan workgroup (n <= 256 K): the blocks pass is the identity, so lane totals, the workgroup scan and the apply are one kernel, one
+// workgroup per row (blockIdx.x), and nothing goes through HBM between them.  The products are formed twice, as the three passes form them.
+__global__ __launch_bounds__(256) void k_pscan_fused_rows(const Fr* __restrict__ num, const Fr* __restrict__ dinv, uint32_t n, uint32_t K, Fr* __restrict__ z,
+                                                          size_t out_stride) {
+    __shared__ Fr sh[256];
+    const size_t row = blockIdx.x, base = (size_t)threadIdx.x * K;
+    num += row * n;
+    dinv += row * n;
+    z += row * out_stride;
+    Fr tot = Fr::one();
+    for (uint32_t k = 0; k < K; k++) {
+        size_t i = base + k;
+        if (i < n) tot = tot * (ld(num + i) * ld(dinv + i));
+    }
+    Fr inc;
+    Fr p = pscan_wg256(sh, tot, &inc);
     for (uint32_t k = 0; k < K; k++) {
         size_t i = base + k;
         if (i >= n) break;
@@ -800,6 +931,127 @@ static int domains_for(size_t size_system, unsigned* logn, unsigned* logN4) {
     std::string e;
     const int rc = plonk_domains_for(size_system, logn, logN4, &e);
     return rc == ZK_OK ? ZK_OK : set_err(rc, "%s", e.c_str());
+}
+
+// ------------------------------------------------------------------------------------------------ round 2 for R witnesses of one domain
+// iop.BuildRatioCopyConstraint on `rows` triples (l, r, o) that share a domain and a permutation: Z in Lagrange form, regular order, per row.
+//   one row     the five launches of zk_bn254_plonk_prove's round 2, kernel for kernel, on the scan plan the prover uses (scan_bufs of n + 8)
+//   more rows   k_z_terms_rows (row = blockIdx.y), ONE k_batch_inverse over the rows * n denominators of the chunk, then
+//                 n <= 256 K:  k_pscan_fused_rows, one workgroup per row                                    -- three launches in all
+//                 above:       k_pscan_local_rows, k_pscan_blocks_rows (one workgroup per row), k_pscan_apply_rows -- five
+//               on the plan of n itself: K = max(8, ceil(n / 2^18)) elements per lane, nb = ceil(n / 256 K) workgroups per row
+// The workspace comes from the slot's arena, RATIO_SCRATCH bytes at a time: more rows than fit (or than a grid's y holds) go in chunks on the same stream.
+constexpr size_t RATIO_SCRATCH = (size_t)1 << 30;
+constexpr size_t RATIO_GRID_ROWS = 65535;
+struct RatioWs {
+    uint32_t K = 0, nb = 0;
+    size_t chunk = 0;    // rows per group of launches
+    bool single = false; // the one-row form: `one` is the prover's scan plan
+    Fr *num = nullptr, *den = nullptr, *scr = nullptr, *t = nullptr, *b = nullptr;
+    ScanBufs one;
+};
+static void ratio_plan(size_t n, uint32_t* K, uint32_t* nb) {
+    uint32_t k = (uint32_t)((n + 256 * 1024 - 1) / (256 * 1024));
+    if (k < 8) k = 8;
+    *K = k;
+    *nb = (uint32_t)(((n + k - 1) / k + 255) / 256);
+}
+static size_t ratio_row_bytes(size_t n) {
+    uint32_t K, nb;
+    ratio_plan(n, &K, &nb);
+    return (3 * n + (size_t)nb * 257) * sizeof(Fr);
+}
+// rows per chunk when every row also takes `extra` bytes of the caller's (the staging rows of the host entry)
+static size_t ratio_chunk(size_t n, size_t rows, size_t extra) {
+    return std::min(std::min(rows, RATIO_GRID_ROWS), std::max<size_t>(1, RATIO_SCRATCH / (ratio_row_bytes(n) + extra)));
+}
+static size_t ratio_ws_bytes(size_t n, size_t chunk, bool single) {
+    return single ? 3 * (n * sizeof(Fr) + 256) + scan_need(n + 8) + 4096 : chunk * ratio_row_bytes(n) + 5 * 256;
+}
+// after the caller's reserve() of at least ratio_ws_bytes
+static int ratio_ws_take(Slot* s, size_t n, size_t chunk, bool single, RatioWs* W) {
+    W->single = single;
+    W->chunk = single ? 1 : chunk;
+    W->num = (Fr*)s->alloc(W->chunk * n * sizeof(Fr));
+    W->den = (Fr*)s->alloc(W->chunk * n * sizeof(Fr));
+    W->scr = (Fr*)s->alloc(W->chunk * n * sizeof(Fr));
+    if (!W->num || !W->den || !W->scr) return set_err(ZK_ERR_HIP, "ratio workspace was not reserved");
+    if (single) return scan_bufs(s, n + 8, &W->one);
+    ratio_plan(n, &W->K, &W->nb);
+    W->t = (Fr*)s->alloc(W->chunk * W->nb * 256 * sizeof(Fr));
+    W->b = (Fr*)s->alloc(W->chunk * W->nb * sizeof(Fr));
+    if (!W->t || !W->b) return set_err(ZK_ERR_HIP, "ratio workspace was not reserved");
+    return ZK_OK;
+}
+// row v: wires at l / r / o + v * in_stride, challenges d_beta[v], d_gamma[v] (device), Z to z + v * out_stride.  sig = S1 | S2 | S3 in Lagrange form.
+static int ratio_rows_dev(Slot* s, hipStream_t st, const Domain* d0, const Fr* sig, const Fr* l, const Fr* r, const Fr* o, size_t in_stride, size_t rows,
+                          const Fr* d_beta, const Fr* d_gamma, Fr* z, size_t out_stride, const RatioWs& W) {
+    const size_t n = (size_t)1 << d0->logn;
+    const HFr u = d0->coset, uu = u * u;
+    const Fr* tw = d0->tw;
+    if (W.single) {
+        if (rows != 1) return set_err(ZK_ERR_ARG, "internal: one-row ratio workspace for %zu rows", rows);
+        HFr bg[2];
+        ZK_HIP(hipMemcpyAsync(&bg[0], d_beta, sizeof(Fr), hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipMemcpyAsync(&bg[1], d_gamma, sizeof(Fr), hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipStreamSynchronize(st));
+        const HFr beta = bg[0], gamma = bg[1];
+        const ScanBufs& SB = W.one;
+        ZK_LAUNCH(s, st, "plonk_z_terms", k_z_terms, dim3(grid_of(n)), dim3(256), 0, l, r, o, sig, tw, (uint32_t)n, to_dev(beta), to_dev(beta * u), to_dev(beta * uu),
+                  to_dev(gamma), W.num, W.den);
+        {
+            size_t lanes = (n + BINV_K - 1) / BINV_K;
+            ZK_LAUNCH(s, st, "plonk_batch_inverse", k_batch_inverse, dim3(grid_of(lanes)), dim3(256), 0, W.den, n, W.scr);
+        }
+        ZK_LAUNCH(s, st, "plonk_pscan_local", k_pscan_local, dim3(SB.nb), dim3(256), 0, (const Fr*)W.num, (const Fr*)W.den, n, SB.K, SB.t, SB.b);
+        ZK_LAUNCH(s, st, "plonk_pscan_blocks", k_pscan_blocks, dim3(1), dim3(1024), 0, SB.b, SB.nb);
+        ZK_LAUNCH(s, st, "plonk_pscan_apply", k_pscan_apply, dim3(SB.nb), dim3(256), 0, (const Fr*)W.num, (const Fr*)W.den, n, SB.K, (const Fr*)SB.t, (const Fr*)SB.b, z);
+        return ZK_OK;
+    }
+    for (size_t first = 0; first < rows; first += W.chunk) {
+        const unsigned R = (unsigned)std::min(W.chunk, rows - first);
+        ZK_LAUNCH(s, st, "plonk_z_terms_rows", k_z_terms_rows, dim3(grid_of(n), R), dim3(256), 0, l + first * in_stride, r + first * in_stride, o + first * in_stride,
+                  in_stride, sig, tw, (uint32_t)n, d_beta + first, d_gamma + first, to_dev(u), to_dev(uu), W.num, W.den);
+        {
+            const size_t cnt = (size_t)R * n, lanes = (cnt + BINV_K - 1) / BINV_K;
+            ZK_LAUNCH(s, st, "plonk_batch_inverse", k_batch_inverse, dim3(grid_of(lanes)), dim3(256), 0, W.den, cnt, W.scr);
+        }
+        Fr* zc = z + first * out_stride;
+        if (W.nb == 1) {
+            ZK_LAUNCH(s, st, "plonk_pscan_fused_rows", k_pscan_fused_rows, dim3(R), dim3(256), 0, (const Fr*)W.num, (const Fr*)W.den, (uint32_t)n, W.K, zc, out_stride);
+            continue;
+        }
+        ZK_LAUNCH(s, st, "plonk_pscan_local_rows", k_pscan_local_rows, dim3(W.nb, R), dim3(256), 0, (const Fr*)W.num, (const Fr*)W.den, (uint32_t)n, W.K, W.t, W.b);
+        ZK_LAUNCH(s, st, "plonk_pscan_blocks_rows", k_pscan_blocks_rows, dim3(R), dim3(1024), 0, W.b, W.nb);
+        ZK_LAUNCH(s, st, "plonk_pscan_apply_rows", k_pscan_apply_rows, dim3(W.nb, R), dim3(256), 0, (const Fr*)W.num, (const Fr*)W.den, (uint32_t)n, W.K, (const Fr*)W.t,
+                  (const Fr*)W.b, zc, out_stride);
+    }
+    return ZK_OK;
+}
+// S1 | S2 | S3 in Lagrange form from 3n positions; *h_flag != 0 after the stream is synchronised: an entry was out of range
+static int sigma_checked_dev(Slot* s, hipStream_t st, const Domain* d0, const uint32_t* d_perm, Fr* d_sigma, int* d_flag) {
+    const size_t n = (size_t)1 << d0->logn;
+    const HFr u = d0->coset;
+    ZK_HIP(hipMemsetAsync(d_flag, 0, 4, st));
+    ZK_LAUNCH(s, st, "plonk_sigma_lagrange", k_sigma_lagrange_checked, dim3(grid_of(3 * n)), dim3(256), 0, d_perm, (const Fr*)d0->tw, (uint32_t)n, to_dev(u), to_dev(u * u),
+              d_sigma, d_flag);
+    return ZK_OK;
+}
+static bool spans_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const char *a0 = (const char*)a, *b0 = (const char*)b;
+    return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+static size_t rows_span(size_t rows, size_t stride, size_t n) { return rows ? ((rows - 1) * stride + n) * sizeof(Fr) : 0; }
+// the argument contract of the ratio entries that take device rows (sigma_elems: 3n, or 0 where the key supplies it)
+static int ratio_dev_args(const void* l, const void* r, const void* o, size_t in_stride, size_t n, size_t rows, const void* sigma, size_t sigma_elems, const void* beta,
+                          const void* gamma, const void* z, size_t out_stride) {
+    if (in_stride < n) return set_err(ZK_ERR_ARG, "in_stride = %zu is below the domain size %zu", in_stride, n);
+    if (out_stride < n) return set_err(ZK_ERR_ARG, "out_stride = %zu is below the domain size %zu", out_stride, n);
+    const size_t zb = rows_span(rows, out_stride, n), ib = rows_span(rows, in_stride, n);
+    if (spans_overlap(z, zb, l, ib) || spans_overlap(z, zb, r, ib) || spans_overlap(z, zb, o, ib) || spans_overlap(z, zb, sigma, sigma_elems * sizeof(Fr)) ||
+        spans_overlap(z, zb, beta, rows * sizeof(Fr)) || spans_overlap(z, zb, gamma, rows * sizeof(Fr)))
+        return set_err(ZK_ERR_ARG, "d_z overlaps an input");
+    return ZK_OK;
 }
 
 }  // namespace zkmi
@@ -1611,6 +1863,147 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
     g1_compress(c_zopen, o); o += 32;
     fr_to_be(zu, o); o += 32;
     return (o - proof_out) == ZK_PLONK_PROOF_BYTES ? ZK_OK : set_err(ZK_ERR_ARG, "internal: proof length");
+}
+
+// ---- iop: the copy-constraint ratio of many witnesses (gnark-crypto ecc/bn254/fr/iop BuildRatioCopyConstraint) and its two ingredients behind doors of
+// their own.  Every entry decides its argument errors before it looks for a device; the entries with workspace synchronise before they return (the workspace
+// is the slot's arena, which the next call on the slot reuses), as zk_bn254_groth16_compute_h_batch_dev does.
+int zk_bn254_iop_sigma_dev(const void* d_perm, uint32_t log_n, void* d_sigma, void* stream) {
+    if (!d_perm || !d_sigma) return set_err(ZK_ERR_ARG, "null pointer");
+    if (log_n > 28) return set_err(ZK_ERR_ARG, "log_n = %u exceeds Fr two-adicity 28", log_n);
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    Domain* d0;
+    ZK_TRY(get_domain(g.s, st, log_n, DOM_TW, &d0));
+    ZK_TRY(g.s->reserve(4096));
+    int* d_flag = (int*)g.s->alloc(64);
+    if (!d_flag) return set_err(ZK_ERR_HIP, "sigma: workspace");
+    int h_flag = 0;
+    ZK_TRY(sigma_checked_dev(g.s, st, d0, (const uint32_t*)d_perm, (Fr*)d_sigma, d_flag));
+    ZK_HIP(hipMemcpyAsync(&h_flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    ZK_TRY(slot_sync(g.s, st));  // the status is read here
+    if (h_flag) return set_err(ZK_ERR_ARG, "permutation entry out of range (>= 3 * 2^%u)", log_n);
+    return ZK_OK;
+}
+
+int zk_bn254_iop_ratio_copy_batch_dev(const void* d_l, const void* d_r, const void* d_o, size_t in_stride, uint32_t log_n, size_t rows, const void* d_sigma,
+                                      const void* d_beta, const void* d_gamma, void* d_z, size_t out_stride, void* stream) {
+    if (!d_l || !d_r || !d_o || !d_sigma || !d_beta || !d_gamma || !d_z) return set_err(ZK_ERR_ARG, "null pointer");
+    if (log_n > 28) return set_err(ZK_ERR_ARG, "log_n = %u exceeds Fr two-adicity 28", log_n);
+    const size_t n = (size_t)1 << log_n;
+    ZK_TRY(ratio_dev_args(d_l, d_r, d_o, in_stride, n, rows, d_sigma, 3 * n, d_beta, d_gamma, d_z, out_stride));
+    if (rows == 0) return ZK_OK;
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    Domain* d0;
+    ZK_TRY(get_domain(g.s, st, log_n, DOM_TW, &d0));
+    const size_t chunk = ratio_chunk(n, rows, 0);
+    RatioWs W;
+    ZK_TRY(g.s->reserve(ratio_ws_bytes(n, chunk, rows == 1)));
+    ZK_TRY(ratio_ws_take(g.s, n, chunk, rows == 1, &W));
+    ZK_TRY(ratio_rows_dev(g.s, st, d0, (const Fr*)d_sigma, (const Fr*)d_l, (const Fr*)d_r, (const Fr*)d_o, in_stride, rows, (const Fr*)d_beta, (const Fr*)d_gamma, (Fr*)d_z,
+                          out_stride, W));
+    return slot_sync(g.s, st);  // the workspace lives in the slot's arena
+}
+
+// host rows, contiguous: l, r, o, z_out (rows, n), perm 3n positions, beta and gamma one per row
+int zk_bn254_iop_ratio_copy_batch(const zk_fr* l, const zk_fr* r, const zk_fr* o, uint32_t log_n, size_t rows, const uint32_t* perm, const zk_fr* beta,
+                                  const zk_fr* gamma, zk_fr* z_out) {
+    if (!l || !r || !o || !perm || !beta || !gamma || !z_out) return set_err(ZK_ERR_ARG, "null pointer");
+    if (log_n > 28) return set_err(ZK_ERR_ARG, "log_n = %u exceeds Fr two-adicity 28", log_n);
+    const size_t n = (size_t)1 << log_n;
+    ZK_TRY(ratio_dev_args(l, r, o, n, n, rows, nullptr, 0, beta, gamma, z_out, n));
+    if (rows == 0) return ZK_OK;
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    Slot* s = g.s;
+    hipStream_t st = s->stream;
+    Domain* d0;
+    ZK_TRY(get_domain(s, st, log_n, DOM_TW, &d0));
+    const size_t row_bytes = n * sizeof(Fr), chunk = ratio_chunk(n, rows, 4 * row_bytes);
+    ZK_TRY(s->reserve(3 * row_bytes + 3 * n * 4 + 2 * rows * sizeof(Fr) + 4 * chunk * row_bytes + ratio_ws_bytes(n, chunk, rows == 1) + 16 * 256));
+    Fr* sig = (Fr*)s->alloc(3 * row_bytes);
+    uint32_t* d_perm = (uint32_t*)s->alloc(3 * n * 4);
+    int* d_flag = (int*)s->alloc(64);
+    Fr *d_beta = (Fr*)s->alloc(rows * sizeof(Fr)), *d_gamma = (Fr*)s->alloc(rows * sizeof(Fr));
+    Fr* d[4];
+    for (int i = 0; i < 4; i++) d[i] = (Fr*)s->alloc(chunk * row_bytes);
+    if (!sig || !d_perm || !d_flag || !d_beta || !d_gamma || !d[0] || !d[1] || !d[2] || !d[3]) return set_err(ZK_ERR_HIP, "ratio batch: workspace");
+    RatioWs W;
+    ZK_TRY(ratio_ws_take(s, n, chunk, rows == 1, &W));
+    int h_flag = 0;
+    ZK_HIP(hipMemcpyAsync(d_perm, perm, 3 * n * 4, hipMemcpyHostToDevice, st));
+    ZK_TRY(sigma_checked_dev(s, st, d0, d_perm, sig, d_flag));
+    ZK_HIP(hipMemcpyAsync(&h_flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipMemcpyAsync(d_beta, beta, rows * sizeof(Fr), hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_gamma, gamma, rows * sizeof(Fr), hipMemcpyHostToDevice, st));
+    ZK_TRY(slot_sync(s, st));
+    if (h_flag) return set_err(ZK_ERR_ARG, "permutation entry out of range (>= 3 * 2^%u)", log_n);
+    const zk_fr* src[3] = {l, r, o};
+    for (size_t first = 0; first < rows; first += chunk) {
+        const size_t R = std::min(chunk, rows - first);
+        for (int i = 0; i < 3; i++) ZK_HIP(hipMemcpyAsync(d[i], (const char*)src[i] + first * row_bytes, R * row_bytes, hipMemcpyHostToDevice, st));
+        ZK_TRY(ratio_rows_dev(s, st, d0, sig, d[0], d[1], d[2], n, R, d_beta + first, d_gamma + first, d[3], n, W));
+        ZK_HIP(hipMemcpyAsync((char*)z_out + first * row_bytes, d[3], R * row_bytes, hipMemcpyDeviceToHost, st));
+    }
+    return slot_sync(s, st);
+}
+
+// the same through a resident PLONK key: its permutation (S1 | S2 | S3 in Lagrange form), its domain and that domain's twiddles
+int zk_bn254_plonk_ratio_batch_dev(uint64_t handle, const void* d_l, const void* d_r, const void* d_o, size_t in_stride, size_t rows, const void* d_beta,
+                                   const void* d_gamma, void* d_z, size_t out_stride, void* stream) {
+    if (!d_l || !d_r || !d_o || !d_beta || !d_gamma || !d_z) return set_err(ZK_ERR_ARG, "null pointer");
+    if (rows == 0) return ZK_OK;
+    PlonkPK* P;
+    std::shared_ptr<std::mutex> mu;
+    {   // the table of keys is the host's: an unknown handle is answered without a device
+        std::lock_guard<std::mutex> lk(g_ppk_mu);
+        auto it = g_ppks.find(handle);
+        if (it == g_ppks.end()) return set_err(ZK_ERR_HANDLE, "unknown PLONK proving-key handle %llu", (unsigned long long)handle);
+        P = it->second;
+        mu = P->mu;
+    }
+    ZK_ON_ENTRY_OF(handle);
+    std::lock_guard<std::mutex> key_lock(*mu);  // a key in use is not freed (zk_bn254_plonk_pk_free waits on this mutex)
+    {
+        std::lock_guard<std::mutex> lk(g_ppk_mu);
+        auto it = g_ppks.find(handle);
+        if (it == g_ppks.end() || it->second != P) return set_err(ZK_ERR_HANDLE, "PLONK proving key %llu was freed", (unsigned long long)handle);
+    }
+    const size_t n = P->n;
+    ZK_TRY(ratio_dev_args(d_l, d_r, d_o, in_stride, n, rows, nullptr, 0, d_beta, d_gamma, d_z, out_stride));
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    Domain* d0;
+    ZK_TRY(get_domain(g.s, st, P->logn, DOM_TW, &d0));
+    const size_t chunk = ratio_chunk(n, rows, 0);
+    RatioWs W;
+    ZK_TRY(g.s->reserve(ratio_ws_bytes(n, chunk, rows == 1)));
+    ZK_TRY(ratio_ws_take(g.s, n, chunk, rows == 1, &W));
+    ZK_TRY(ratio_rows_dev(g.s, st, d0, (const Fr*)P->sig, (const Fr*)d_l, (const Fr*)d_r, (const Fr*)d_o, in_stride, rows, (const Fr*)d_beta, (const Fr*)d_gamma, (Fr*)d_z,
+                          out_stride, W));
+    return slot_sync(g.s, st);
+}
+
+// fr.BatchInvert in place on n device elements: a zero stays a zero.  k_batch_inverse with its scratch from the slot's arena, at most RATIO_SCRATCH bytes at a time.
+int zk_bn254_fr_batch_invert_dev(void* d_a, size_t n, void* stream) {
+    if (!d_a) return set_err(ZK_ERR_ARG, "null pointer");
+    if (n == 0) return ZK_OK;
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    const size_t chunk = std::min(n, RATIO_SCRATCH / sizeof(Fr));
+    ZK_TRY(g.s->reserve(chunk * sizeof(Fr) + 256));
+    Fr* scr = (Fr*)g.s->alloc(chunk * sizeof(Fr));
+    if (!scr) return set_err(ZK_ERR_HIP, "batch inverse: workspace");
+    for (size_t first = 0; first < n; first += chunk) {
+        const size_t cnt = std::min(chunk, n - first), lanes = (cnt + BINV_K - 1) / BINV_K;
+        ZK_LAUNCH(g.s, st, "plonk_batch_inverse", k_batch_inverse, dim3(grid_of(lanes)), dim3(256), 0, (Fr*)d_a + first, cnt, scr);
+    }
+    return slot_sync(g.s, st);  // the scratch lives in the slot's arena
 }
 
 }  // extern "C"

@@ -54,6 +54,21 @@ class ProvingKey:
         """Build the SRS's Lagrange form over this key's domain (zk_bn254_plonk_pk_lagrange_srs): later proofs commit l, r, o from the wire values."""
         check(lib().zk_bn254_plonk_pk_lagrange_srs(self.handle))
 
+    @property
+    def domain_size(self) -> int:
+        """Domain[0].Cardinality"""
+        if self.vk is not None:
+            return int(self.vk["size"])
+        n = C.c_size_t(0)
+        check(lib().zk_bn254_plonk_pk_info(self.handle, C.byref(n), None, None, None))
+        return int(n.value)
+
+    def ratio_batch(self, l, r, o, beta, gamma, *, rows: int | None = None, in_stride: int | None = None, out_stride: int | None = None, out=None):
+        """ratio_copy_batch with this key's permutation, domain and twiddles (zk_bn254_plonk_ratio_batch_dev): round 2 of `rows` proofs against one key.
+        Host arrays ((rows, n, 4); beta, gamma (rows, 4)) go to the device and Z comes back as a new array; device buffers / pointers are used where they are
+        and `out` (made here when None) is returned.  Every shape / dtype / stride / count error is raised before the library is called."""
+        return _pk_ratio_batch(self, l, r, o, beta, gamma, rows=rows, in_stride=in_stride, out_stride=out_stride, out=out)
+
     def free(self):
         if self.handle.value:
             check(lib().zk_bn254_plonk_pk_free(self.handle))
@@ -122,3 +137,181 @@ def prove(pk: ProvingKey, solution, blinders, challenges=None) -> bytes:
         raise ValueError((lib().zk_last_error() or b"").decode())
     check(rc)
     return bytes(out)
+
+
+# ---- round 2 for many witnesses: iop.BuildRatioCopyConstraint with the row as a grid dimension (zk_bn254_iop_ratio_copy_batch[_dev], zk_bn254_plonk_ratio_batch_dev)
+_DEV = (int, _lib.DeviceBuffer)
+
+
+def _ptr(a) -> int:
+    return a if isinstance(a, int) else a.ptr
+
+
+def _host_rows(name, a, n=None):
+    """a C-contiguous (rows, n, 4) uint64 array, or TypeError / ValueError"""
+    if not (isinstance(a, np.ndarray) and a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"]):
+        raise TypeError("%s must be a C-contiguous uint64 numpy array (or a device buffer)" % name)
+    if a.ndim != 3 or a.shape[2] != 4 or (n is not None and a.shape[1] != n):
+        raise ValueError("%s has shape %s, not (rows, %s, 4)" % (name, a.shape, "n" if n is None else n))
+    return a
+
+
+def _host_challenges(name, a, rows):
+    if not (isinstance(a, np.ndarray) and a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"]):
+        raise TypeError("%s must be a C-contiguous uint64 numpy array" % name)
+    if a.shape != (rows, 4):
+        raise ValueError("%s has shape %s, not (%d, 4): one challenge per row" % (name, a.shape, rows))
+    return a
+
+
+def _power_of_two(n):
+    n = int(n)
+    if n < 1 or n & (n - 1) or n > 1 << 28:
+        raise ValueError("the domain size %d is not a power of two up to 2^28" % n)
+    return n
+
+
+def _host_perm(perm, n):
+    if not isinstance(perm, np.ndarray) or perm.dtype.kind not in "iu":
+        raise TypeError("perm must be an integer numpy array of 3 n positions")
+    if perm.shape != (3 * n,):
+        raise ValueError("perm has shape %s, not (%d,)" % (perm.shape, 3 * n))
+    if perm.size and (int(perm.min()) < 0 or int(perm.max()) >= 3 * n):
+        raise ValueError("perm holds a position outside [0, %d)" % (3 * n))
+    return np.ascontiguousarray(perm, dtype=np.uint32)
+
+
+def _dev_geometry(bufs, n, rows, in_stride, out_stride, out, extra=()):
+    """the checks of a call on device rows, before the library: bufs = (name, buffer) of l, r, o; extra = (name, buffer, bytes) of what else is read"""
+    if rows is None:
+        raise ValueError("rows is required with device-resident data")
+    rows = int(rows)
+    in_stride, out_stride = int(n if in_stride is None else in_stride), int(n if out_stride is None else out_stride)
+    if rows < 0:
+        raise ValueError("rows must not be negative")
+    if in_stride < n or out_stride < n:
+        raise ValueError("in_stride = %d / out_stride = %d is below the domain size %d" % (in_stride, out_stride, n))
+    span = lambda stride: ((rows - 1) * stride + n) * 32 if rows else 0
+    reads = [(name, b, span(in_stride)) for name, b in bufs] + list(extra)
+    for name, b, nbytes in reads + ([("out", out, span(out_stride))] if out is not None else []):
+        if not isinstance(b, _DEV):
+            raise TypeError("%s must be a device buffer or a device pointer, like l" % name)
+        if isinstance(b, _lib.DeviceBuffer) and nbytes > b.nbytes:
+            raise ValueError("%s: %d bytes do not fit the device buffer (%d bytes)" % (name, nbytes, b.nbytes))
+    if out is not None:
+        lo, hi = _ptr(out), _ptr(out) + span(out_stride)
+        for name, b, nbytes in reads:
+            if nbytes and _ptr(b) < hi and lo < _ptr(b) + nbytes:
+                raise ValueError("out overlaps %s" % name)
+    return rows, in_stride, out_stride
+
+
+def permutation_sigma(perm, n: int | None = None):
+    """3 n positions (gnark's pk.Permutation, L | R | O) -> a DeviceBuffer of the 3 n elements S1 | S2 | S3 in Lagrange form (zk_bn254_iop_sigma_dev): what
+    ratio_copy_batch takes as `perm` next to device rows.  perm: an integer numpy array, or a device buffer / pointer of uint32 together with n."""
+    if isinstance(perm, _DEV):
+        if n is None:
+            raise ValueError("n is required with a device-resident permutation")
+        n = _power_of_two(n)
+        if isinstance(perm, _lib.DeviceBuffer) and 3 * n * 4 > perm.nbytes:
+            raise ValueError("3 * %d positions do not fit the device buffer (%d bytes)" % (n, perm.nbytes))
+        src, keep = perm, None
+    else:
+        if not isinstance(perm, np.ndarray) or perm.ndim != 1 or perm.size % 3:
+            raise ValueError("perm must be a flat integer numpy array of 3 n positions")
+        n = _power_of_two(perm.size // 3)
+        src = keep = _lib.DeviceBuffer.from_numpy(_host_perm(perm, n))
+    out = _lib.DeviceBuffer(3 * n * 32)
+    try:
+        rc = lib().zk_bn254_iop_sigma_dev(C.c_void_p(_ptr(src)), C.c_uint32(n.bit_length() - 1), C.c_void_p(out.ptr), C.c_void_p(0))
+        if rc == _lib.ZK_ERR_ARG:
+            raise ValueError((lib().zk_last_error() or b"").decode())
+        check(rc)
+    except Exception:
+        out.free()
+        raise
+    finally:
+        if keep is not None:
+            keep.free()
+    return out
+
+
+def ratio_copy_batch(l, r, o, perm, beta, gamma, *, rows: int | None = None, in_stride: int | None = None, out_stride: int | None = None, n: int | None = None, out=None):
+    """iop.BuildRatioCopyConstraint for `rows` witnesses of one domain and one permutation, each row with its own beta and gamma: Z per row, Lagrange form,
+    regular order (include/zkmi.h says the rest).  Two forms, every shape / dtype / stride / count error raised before the library is called:
+      host    l, r, o: (rows, n, 4) uint64 arrays; perm: 3 n integer positions; beta, gamma: (rows, 4) -> a new (rows, n, 4) array
+      device  l, r, o, beta, gamma: device buffers / pointers; perm: S1 | S2 | S3 as permutation_sigma leaves it; rows and n are required, row v of the wires at
+              element v * in_stride, of Z at v * out_stride (both default n) of `out`, a device buffer that must not overlap an input (made here when None) -> out"""
+    if isinstance(l, _DEV):
+        if n is None:
+            raise ValueError("n is required with device-resident data")
+        n = _power_of_two(n)
+        cnt = 0 if rows is None else max(int(rows), 0)
+        rows, in_stride, out_stride = _dev_geometry((("l", l), ("r", r), ("o", o)), n, rows, in_stride, out_stride, out,
+                                                    (("perm", perm, 3 * n * 32), ("beta", beta, cnt * 32), ("gamma", gamma, cnt * 32)))
+        if out is None:
+            out = _lib.DeviceBuffer(max(((rows - 1) * out_stride + n) * 32 if rows else 0, 32))
+        check(lib().zk_bn254_iop_ratio_copy_batch_dev(C.c_void_p(_ptr(l)), C.c_void_p(_ptr(r)), C.c_void_p(_ptr(o)), C.c_size_t(in_stride), C.c_uint32(n.bit_length() - 1),
+                                                      C.c_size_t(rows), C.c_void_p(_ptr(perm)), C.c_void_p(_ptr(beta)), C.c_void_p(_ptr(gamma)), C.c_void_p(_ptr(out)),
+                                                      C.c_size_t(out_stride), C.c_void_p(0)))
+        return out
+    l = _host_rows("l", l)
+    cnt, size = l.shape[0], _power_of_two(l.shape[1])
+    if n is not None and int(n) != size:
+        raise ValueError("n = %d != %d elements per row" % (n, size))
+    r, o = _host_rows("r", r, size), _host_rows("o", o, size)
+    if r.shape[0] != cnt or o.shape[0] != cnt:
+        raise ValueError("l, r and o have %d, %d and %d rows" % (cnt, r.shape[0], o.shape[0]))
+    if rows is not None and int(rows) != cnt:
+        raise ValueError("rows = %d != %d rows of the arrays" % (rows, cnt))
+    for name, v in (("in_stride", in_stride), ("out_stride", out_stride)):
+        if v is not None and int(v) != size:
+            raise ValueError("the rows of a host array are contiguous: %s must be %d" % (name, size))
+    if out is not None:
+        raise ValueError("out belongs to the device form: the host form returns a new array")
+    p = _host_perm(perm, size)
+    beta, gamma = _host_challenges("beta", beta, cnt), _host_challenges("gamma", gamma, cnt)
+    z = np.zeros((cnt, size, 4), dtype=np.uint64)
+    check(lib().zk_bn254_iop_ratio_copy_batch(vp(l), vp(r), vp(o), C.c_uint32(size.bit_length() - 1), C.c_size_t(cnt), vp(p), vp(beta), vp(gamma), vp(z)))
+    return z
+
+
+def _pk_ratio_batch(self, l, r, o, beta, gamma, *, rows: int | None = None, in_stride: int | None = None, out_stride: int | None = None, out=None):
+    """ProvingKey.ratio_batch"""
+    n = self.domain_size
+    bufs = []
+    if isinstance(l, _DEV):
+        cnt = 0 if rows is None else max(int(rows), 0)
+        rows, in_stride, out_stride = _dev_geometry((("l", l), ("r", r), ("o", o)), n, rows, in_stride, out_stride, out, (("beta", beta, cnt * 32), ("gamma", gamma, cnt * 32)))
+        if out is None:
+            out = _lib.DeviceBuffer(max(((rows - 1) * out_stride + n) * 32 if rows else 0, 32))
+        host = None
+    else:
+        l, r, o = _host_rows("l", l, n), _host_rows("r", r, n), _host_rows("o", o, n)
+        cnt = l.shape[0]
+        if r.shape[0] != cnt or o.shape[0] != cnt:
+            raise ValueError("l, r and o have %d, %d and %d rows" % (cnt, r.shape[0], o.shape[0]))
+        if rows is not None and int(rows) != cnt:
+            raise ValueError("rows = %d != %d rows of the arrays" % (rows, cnt))
+        for name, v in (("in_stride", in_stride), ("out_stride", out_stride)):
+            if v is not None and int(v) != n:
+                raise ValueError("the rows of a host array are contiguous: %s must be %d" % (name, n))
+        if out is not None:
+            raise ValueError("out belongs to the device form: the host form returns a new array")
+        beta, gamma = _host_challenges("beta", beta, cnt), _host_challenges("gamma", gamma, cnt)
+        host = np.zeros((cnt, n, 4), dtype=np.uint64)
+        if cnt == 0:
+            return host
+        rows, in_stride, out_stride = cnt, n, n
+        bufs = [_lib.DeviceBuffer.from_numpy(v) for v in (l, r, o, beta, gamma)]
+        l, r, o, beta, gamma = bufs
+        out = _lib.DeviceBuffer(host.nbytes)
+        bufs.append(out)
+    try:
+        check(lib().zk_bn254_plonk_ratio_batch_dev(self.handle, C.c_void_p(_ptr(l)), C.c_void_p(_ptr(r)), C.c_void_p(_ptr(o)), C.c_size_t(in_stride), C.c_size_t(rows),
+                                                   C.c_void_p(_ptr(beta)), C.c_void_p(_ptr(gamma)), C.c_void_p(_ptr(out)), C.c_size_t(out_stride), C.c_void_p(0)))
+        return out if host is None else out.to_numpy(np.uint64, host.shape)
+    finally:
+        for b in bufs:
+            b.free()
+
