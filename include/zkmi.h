@@ -613,6 +613,40 @@ int zk_groth16_public_inputs(const char *raw_json, size_t raw_len, zk_fr *out, s
  * digits per scalar, i.e. mixed additions per scalar multiplication -- used by bench.py to turn launches into work. */
 int zk_bn254_msm_plan_info(size_t n, int window_tables, uint32_t *window_bits, uint32_t *digits);
 
+/* The scalar-side half of an MSM alone, for inspection / tests: signed-digit recoding, radix sort, bucket bounds, device-chosen task
+ * length, task plan and task records -- the production preparation itself, run through the same wrappers the provers call (plain;
+ * against a window table; a batch of up to three pointers; the rows of one matrix), on HOST scalars, with every intermediate copied
+ * back.  No bases are involved.  Nothing stays behind: the slot is released and the preparation's event destroyed on every path.
+ *   request   n scalars per vector; window_bits (0: the planner's choice; ignored in table mode) and scalars_mont as in zk_msm_cfg;
+ *             table != 0: one bucket set per vector against a table of width c whose rows are `stride` entries apart and hold the
+ *             windows row_first + k * row_step; `sets` vectors given by vec[0..sets) (by_rows == 0, sets <= 3; equal pointers stay
+ *             equal on the device) or as the rows vec[0] + v * row_stride of one matrix (by_rows != 0); drop_zero_digits as in the
+ *             provers (silently off where a workgroup's digits do not fit its stage: windows narrower than 8 bits).
+ *   result    the plan, `dropped` (1 when the run took the compacting recoding and its device-side pair counter, else 0), the pair count as the
+ *             device knows it (that counter when digits were dropped, else total), the
+ *             64-word control block ([0] split buckets, [1] largest bucket, [2] task length, [3] buckets above 8192 points, [4] giant
+ *             buckets found, [8..56) ids of those listed) and, where the pointer is not NULL, the arrays: keys / vals [total] (the
+ *             first device_total entries are meaningful), start / task_off [nb + 1], task_begin / len_keys / task_ids [max_tasks],
+ *             multi_list [nb] (the first ctl[0] entries are meaningful).
+ * With ALL array pointers NULL only the plan is filled in (host work: no device is needed, the scalars are not read): call once for
+ * the sizes, allocate, call again.  An empty plan (n == 0, or a table shard that owns no window) reports total == 0 and touches nothing. */
+typedef struct {
+    size_t n;
+    int window_bits, scalars_mont, table, drop_zero_digits;
+    uint32_t c, row_first, row_step, sets;
+    size_t stride;
+    int by_rows, reserved;
+    const zk_fr *vec[3];
+    size_t row_stride;
+} zk_msm_prep_request;
+typedef struct {
+    uint32_t c, W, Wd, Wrows, B, nb, key_bits, L, Lmin, m1, N1, dropped;
+    uint64_t total, max_tasks, device_total;
+    uint32_t ctl[64];
+    uint32_t *keys, *vals, *start, *task_off, *task_begin, *len_keys, *task_ids, *multi_list;
+} zk_msm_prep_result;
+int zk_bn254_msm_prep_inspect(const zk_msm_prep_request *req, zk_msm_prep_result *res);
+
 /* ---- felt-vector wire codec (the data format in front of the hot path) -------------------------------------------
  * The reference hands witness values to the Go side as hex( u32 BE count || count x 32 B BE canonical felts )
  * [REF src/gnark_backend_wrapper/serialize.rs:33-47,71-106; gnark_backend_ffi/internal/backend/helpers.go:24-33

@@ -32,6 +32,21 @@ class MsmCfg(C.Structure):
     _fields_ = [("nb_tasks", C.c_int), ("scalars_mont", C.c_int), ("window_bits", C.c_int), ("device_mask", C.c_int)]
 
 
+class MsmPrepRequest(C.Structure):
+    _fields_ = [("n", C.c_size_t), ("window_bits", C.c_int), ("scalars_mont", C.c_int), ("table", C.c_int), ("drop_zero_digits", C.c_int),
+                ("c", C.c_uint32), ("row_first", C.c_uint32), ("row_step", C.c_uint32), ("sets", C.c_uint32), ("stride", C.c_size_t),
+                ("by_rows", C.c_int), ("reserved", C.c_int), ("vec", C.c_void_p * 3), ("row_stride", C.c_size_t)]
+
+
+MSM_PREP_PLAN = ("c", "W", "Wd", "Wrows", "B", "nb", "key_bits", "L", "Lmin", "m1", "N1")
+MSM_PREP_ARRAYS = ("keys", "vals", "start", "task_off", "task_begin", "len_keys", "task_ids", "multi_list")
+
+
+class MsmPrepResult(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in MSM_PREP_PLAN + ("dropped",)] + [("total", C.c_uint64), ("max_tasks", C.c_uint64), ("device_total", C.c_uint64),
+                                                                         ("ctl", C.c_uint32 * 64)] + [(k, C.c_void_p) for k in MSM_PREP_ARRAYS]
+
+
 class Groth16PK(C.Structure):
     _fields_ = [("log_domain", C.c_uint32), ("n_wires", C.c_size_t), ("n_public", C.c_size_t),
                 ("g1_alpha", C.c_void_p), ("g1_beta", C.c_void_p), ("g1_delta", C.c_void_p),
@@ -70,7 +85,7 @@ SYMBOLS = [
     "zk_device_count", "zk_init", "zk_last_error", "zk_version",
     "zk_bn254_g1_msm", "zk_bn254_g2_msm", "zk_bn254_g1_msm_dev", "zk_bn254_g2_msm_dev",
     "zk_bn254_g1_msm_partial_dev", "zk_bn254_g2_msm_partial_dev", "zk_bn254_g1_sum_xyzz", "zk_bn254_g2_sum_xyzz",
-    "zk_bn254_msm_plan_info", "zk_bn254_bases_register", "zk_bn254_bases_register_dev", "zk_bn254_bases_register_cfg", "zk_bn254_bases_build_table", "zk_bn254_bases_lagrange", "zk_bn254_bases_free", "zk_bn254_msm_bases", "zk_bn254_msm_bases_batch", "zk_bn254_msm_bases_batch_dev", "zk_bn254_msm_bases_dev", "zk_bn254_scalars_register", "zk_bn254_scalars_free", "zk_bn254_msm_bases_prepared",
+    "zk_bn254_msm_plan_info", "zk_bn254_msm_prep_inspect", "zk_bn254_bases_register", "zk_bn254_bases_register_dev", "zk_bn254_bases_register_cfg", "zk_bn254_bases_build_table", "zk_bn254_bases_lagrange", "zk_bn254_bases_free", "zk_bn254_msm_bases", "zk_bn254_msm_bases_batch", "zk_bn254_msm_bases_batch_dev", "zk_bn254_msm_bases_dev", "zk_bn254_scalars_register", "zk_bn254_scalars_free", "zk_bn254_msm_bases_prepared",
     "zk_bn254_ntt", "zk_bn254_ntt_dev", "zk_bn254_bit_reverse", "zk_bn254_bit_reverse_dev",
     "zk_bn254_ntt_batch", "zk_bn254_ntt_batch_dev", "zk_bn254_groth16_compute_h_batch", "zk_bn254_groth16_compute_h_batch_dev",
     "zk_bn254_groth16_compute_h", "zk_bn254_groth16_compute_h_dev", "zk_bn254_groth16_h_shard_dev", "zk_bn254_ntt_shard_dev",

@@ -100,6 +100,58 @@ def g2_sum_partials(partials) -> np.ndarray:
     return out
 
 
+def msm_prep_inspect(vectors, n: int | None = None, window_bits: int = 0, scalars_mont: bool = False, table_c: int = 0, stride: int | None = None,
+                     row_first: int = 0, row_step: int = 1, rows: int = 0, row_stride: int | None = None, drop_zero_digits: bool = False,
+                     plan_only: bool = False, arrays=None) -> dict:
+    """The scalar-side half of an MSM alone (zk_bn254_msm_prep_inspect; for tests): the plan and, unless plan_only (host work, no device), the pair count as the
+    device knows it, the control block and every intermediate array of the production preparation.
+    vectors: one (n, 4) array (plain method, or one vector against a table of width table_c), a list of up to three of them (a batch by pointers; the same
+    array object twice is the same device vector twice), or -- with rows > 0 -- one (rows, row_stride, 4) matrix whose rows' first n elements are the vectors.
+    arrays: names of the arrays to copy back (default: all of _lib.MSM_PREP_ARRAYS; the others come back empty)."""
+    req = _lib.MsmPrepRequest()
+    if rows:
+        mat = _as_u64(vectors, 4)
+        row_stride = row_stride if row_stride is not None else mat.shape[0] // rows
+        if n is None:
+            n = row_stride
+        if mat.shape[0] < (rows - 1) * row_stride + n:
+            raise ValueError("the matrix is shorter than rows * row_stride")
+        keep, sets = [mat], rows
+    else:
+        keep, seen = [], {}
+        for v in (vectors if isinstance(vectors, (list, tuple)) else [vectors]):
+            if id(v) not in seen:
+                seen[id(v)] = _as_u64(v, 4)
+            keep.append(seen[id(v)])
+        sets = len(keep)
+        if n is None:
+            n = keep[0].shape[0]
+        if any(k.shape[0] < n for k in keep):
+            raise ValueError("a scalar vector is shorter than n")
+    req.n, req.window_bits, req.scalars_mont, req.table, req.drop_zero_digits = n, window_bits, int(scalars_mont), int(table_c != 0), int(drop_zero_digits)
+    req.c, req.row_first, req.row_step, req.sets, req.stride = table_c, row_first, row_step, sets, (stride if stride is not None else n)
+    req.by_rows, req.row_stride = int(rows > 0), (row_stride or 0)
+    for i, k in enumerate(keep[:3]):
+        req.vec[i] = k.ctypes.data
+    res = _lib.MsmPrepResult()
+    check(lib().zk_bn254_msm_prep_inspect(C.byref(req), C.byref(res)))
+    plan = lambda: dict({k: int(getattr(res, k)) for k in _lib.MSM_PREP_PLAN}, total=int(res.total), max_tasks=int(res.max_tasks))  # noqa: E731
+    out = plan()
+    if plan_only or out["total"] == 0:
+        out.update(device_total=0, dropped=False, ctl=np.zeros(64, np.uint32), **{k: np.zeros(0, np.uint32) for k in _lib.MSM_PREP_ARRAYS})
+        return out
+    sizes = dict(keys=out["total"], vals=out["total"], start=out["nb"] + 1, task_off=out["nb"] + 1, task_begin=out["max_tasks"], len_keys=out["max_tasks"],
+                 task_ids=out["max_tasks"], multi_list=out["nb"])
+    wanted = _lib.MSM_PREP_ARRAYS if arrays is None else tuple(arrays)
+    arrays = {k: np.zeros(sizes[k] if k in wanted else 0, np.uint32) for k in _lib.MSM_PREP_ARRAYS}
+    for k in wanted:
+        setattr(res, k, arrays[k].ctypes.data)
+    check(lib().zk_bn254_msm_prep_inspect(C.byref(req), C.byref(res)))
+    assert plan() == out
+    out.update(device_total=int(res.device_total), dropped=bool(res.dropped), ctl=np.array(res.ctl[:], dtype=np.uint32), **arrays)
+    return out
+
+
 class ResidentBases:
     """pk / SRS bases kept in HBM across calls (zk_bn254_bases_register)."""
 

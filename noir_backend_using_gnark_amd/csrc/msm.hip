@@ -1191,6 +1191,8 @@ static int msm_prepare(Slot* s, hipStream_t st, const MsmPlan& P, const Fr* d_sc
     ZK_LAUNCH(s, st, "msm_task_scatter", k_task_scatter, dim3(tgrid), dim3(256), 0, (const uint32_t*)lkey0, (uint32_t)max_tasks, bshift, nbins, hist,
               lkey1, tid1);
     out->vals = vb.current();
+    out->keys = keys;
+    out->d_total = d_total;
     out->start = start;
     out->task_off = task_off;
     out->task_begin = task_begin;
@@ -1820,6 +1822,86 @@ int zk_bn254_msm_plan_info(size_t n, int window_tables, uint32_t* window_bits, u
     *window_bits = c;
     *digits = (255 + c - 1) / c;
     return ZK_OK;
+}
+
+// the scalar-side half alone, for inspection / tests (include/zkmi.h): the production msm_prepare through the wrappers the provers call, everything copied back
+static int msm_prep_inspect_run(Slot* s, const zk_msm_prep_request* q, const zk_msm_cfg* cfg, const MsmTable* tab, const MsmPlan& P, MsmPrep* prep,
+                                zk_msm_prep_result* r) {
+    hipStream_t st = s->stream;
+    const size_t n = q->n;
+    const unsigned sets = tab ? q->sets : 1;
+    const size_t elems = q->by_rows ? (size_t)(sets - 1) * q->row_stride + n : n;  // per uploaded block
+    ZK_TRY(s->reserve((q->by_rows ? 1 : sets) * (elems * 32 + 256) + P.need_prep + msm_compact_need(n, sets) + 4096));
+    const void* d_vec[3] = {nullptr, nullptr, nullptr};
+    for (unsigned v = 0; v < (q->by_rows ? 1u : sets); v++) {
+        for (unsigned u = 0; u < v; u++)
+            if (q->vec[u] == q->vec[v]) d_vec[v] = d_vec[u];  // the same host vector twice: the same device vector twice
+        if (d_vec[v]) continue;
+        void* d = s->alloc(elems * 32 + 16);
+        if (!d) return set_err(ZK_ERR_HIP, "MSM inspection: scalar buffer was not reserved");
+        ZK_HIP(hipMemcpyAsync(d, q->vec[v], elems * 32, hipMemcpyHostToDevice, st));
+        d_vec[v] = d;
+    }
+    const bool drop = q->drop_zero_digits != 0;
+    if (!tab) ZK_TRY(msm_prepare_scalars(s, st, d_vec[0], n, cfg, prep, drop));
+    else if (q->by_rows) ZK_TRY(msm_prepare_scalars_table_rows(s, st, d_vec[0], q->row_stride, sets, n, cfg, *tab, prep, drop));
+    else if (sets > 1) ZK_TRY(msm_prepare_scalars_table_batch(s, st, d_vec, sets, n, cfg, *tab, prep, drop));
+    else ZK_TRY(msm_prepare_scalars_table(s, st, d_vec[0], n, cfg, *tab, prep, drop));
+    if (prep->empty) return set_err(ZK_ERR_ARG, "MSM inspection: the preparation is empty where its plan is not");
+    ZK_HIP(hipStreamSynchronize(st));
+    auto back = [&](uint32_t* dst, const uint32_t* src, size_t count) -> int {
+        if (dst && count) ZK_HIP(hipMemcpy(dst, src, count * 4, hipMemcpyDeviceToHost));
+        return ZK_OK;
+    };
+    uint32_t dev_total = (uint32_t)P.total;
+    if (prep->d_total) ZK_HIP(hipMemcpy(&dev_total, prep->d_total, 4, hipMemcpyDeviceToHost));
+    r->device_total = dev_total;
+    r->dropped = prep->d_total ? 1u : 0u;
+    ZK_HIP(hipMemcpy(r->ctl, prep->num_multi, sizeof r->ctl, hipMemcpyDeviceToHost));
+    ZK_TRY(back(r->keys, prep->keys, P.total));
+    ZK_TRY(back(r->vals, prep->vals, P.total));
+    ZK_TRY(back(r->start, prep->start, (size_t)P.nb + 1));
+    ZK_TRY(back(r->task_off, prep->task_off, (size_t)P.nb + 1));
+    ZK_TRY(back(r->task_begin, prep->task_begin, P.max_tasks));
+    ZK_TRY(back(r->len_keys, prep->lkeys, P.max_tasks));
+    ZK_TRY(back(r->task_ids, prep->tids, P.max_tasks));
+    ZK_TRY(back(r->multi_list, prep->multi_list, P.nb));
+    return ZK_OK;
+}
+int zk_bn254_msm_prep_inspect(const zk_msm_prep_request* q, zk_msm_prep_result* r) {
+    if (!q || !r) return set_err(ZK_ERR_ARG, "null pointer");
+    zk_msm_cfg cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.scalars_mont = q->scalars_mont;
+    cfg.window_bits = q->window_bits;
+    MsmTable tab;
+    if (q->table) {
+        if (q->sets < 1 || (!q->by_rows && q->sets > 3)) return set_err(ZK_ERR_ARG, "MSM inspection: one to three vectors by pointer, any number by rows");
+        if (q->stride < q->n || (q->by_rows && q->sets > 1 && q->row_stride < q->n)) return set_err(ZK_ERR_ARG, "MSM inspection: a stride shorter than the vectors");
+        tab.c = q->c;
+        tab.stride = q->stride;
+        tab.row_first = q->row_first;
+        tab.row_step = q->row_step ? q->row_step : 1;
+    } else if (q->sets > 1 || q->by_rows) {
+        return set_err(ZK_ERR_ARG, "MSM inspection: several vectors need table mode");
+    }
+    MsmPlan P;
+    ZK_TRY(msm_plan<Fp>(q->n, &cfg, nullptr, &P, q->table ? &tab : nullptr, q->table ? q->sets : 1));
+    r->c = P.c; r->W = P.W; r->Wd = P.Wd; r->Wrows = P.Wrows; r->B = P.B; r->nb = P.nb; r->key_bits = P.key_bits; r->L = P.L; r->Lmin = P.Lmin;
+    r->m1 = P.m1; r->N1 = P.N1; r->dropped = 0;
+    r->total = P.total; r->max_tasks = P.max_tasks; r->device_total = 0;
+    memset(r->ctl, 0, sizeof r->ctl);
+    const bool sizes_only = !r->keys && !r->vals && !r->start && !r->task_off && !r->task_begin && !r->len_keys && !r->task_ids && !r->multi_list;
+    if (sizes_only || P.total == 0) return ZK_OK;
+    for (unsigned v = 0; v < (q->by_rows ? 1u : (q->table ? q->sets : 1u)); v++)
+        if (!q->vec[v]) return set_err(ZK_ERR_ARG, "null pointer");
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    MsmPrep prep;
+    int rc = msm_prep_inspect_run(g.s, q, &cfg, q->table ? &tab : nullptr, P, &prep, r);
+    if (rc != ZK_OK) (void)hipStreamSynchronize(g.s->stream);  // nothing of this call is in flight when the slot goes back
+    msm_prep_release(&prep);
+    return rc;
 }
 
 int zk_bn254_g1_msm(const zk_g1_affine* points, size_t n_points, const zk_fr* scalars, size_t n_scalars, const zk_msm_cfg* cfg, zk_g1_affine* out) {

@@ -55,6 +55,8 @@ struct MsmPrep {
     bool empty = true;
     const uint32_t *vals = nullptr, *start = nullptr, *task_off = nullptr, *task_begin = nullptr, *lkeys = nullptr, *tids = nullptr,
                    *multi_list = nullptr, *num_multi = nullptr;
+    const uint32_t *keys = nullptr;     // the sorted bucket keys beside `vals` (inspection only: nothing after the bucket bounds reads them)
+    const uint32_t *d_total = nullptr;  // non-null: the zero digits were dropped and this is the device's pair count (inspection only)
     hipEvent_t ready = nullptr;  // recorded on the preparing stream
 };
 

@@ -194,25 +194,30 @@ def msm_naive(F, points, scalars):
     return acc
 
 
+def pippenger_digits(s: int, c: int) -> list:
+    """gnark-crypto's partitionScalars recoding of one scalar: ceil(255 / c) + 1 signed c-bit digits in [-2^(c-1), 2^(c-1)] with sum_w d_w 2^(c w) = s mod r"""
+    nwin = (255 + c - 1) // c + 0
+    half = 1 << (c - 1)
+    s %= R
+    ds, carry = [], 0
+    for w in range(nwin + 1):
+        d = ((s >> (w * c)) & ((1 << c) - 1)) + carry
+        carry = 0
+        if d > half:  # gnark: "if digit > max { digit -= 1<<c; carry = 1 }"
+            d -= 1 << c
+            carry = 1
+        ds.append(d)
+    assert carry == 0
+    return ds
+
+
 def msm_pippenger(F, points, scalars, c: int = 4):
     """Bucket method in the shape gnark-crypto uses (signed c-bit digits, 2^(c-1) buckets per window,
     running-sum reduce, Horner combine).  Affine arithmetic; used to pin the C oracle's digit recoding."""
     assert len(points) == len(scalars)
     nwin = (255 + c - 1) // c + 0
     half = 1 << (c - 1)
-    digits = []
-    for s in scalars:
-        s %= R
-        ds, carry = [], 0
-        for w in range(nwin + 1):
-            d = ((s >> (w * c)) & ((1 << c) - 1)) + carry
-            carry = 0
-            if d > half:  # gnark: "if digit > max { digit -= 1<<c; carry = 1 }"
-                d -= 1 << c
-                carry = 1
-            ds.append(d)
-        assert carry == 0
-        digits.append(ds)
+    digits = [pippenger_digits(s, c) for s in scalars]
     total = None
     for w in range(nwin, -1, -1):
         for _ in range(c):

@@ -1,5 +1,7 @@
 // Stand-alone check and timing of the hand-written radix sort (csrc/radix.hpp) against std::stable_sort, outside the library:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Inoir_backend_using_gnark_amd/csrc tools/rs_test.hip -o tools/rs_test && tools/rs_test
+// It is the timing tool of the sort now: correctness lives in the suite (tests/test_gpu_msm_prep.py sorts through the production preparation, with the
+// device-side length and the four-pass plans this program predates, against numpy's stable sort).
 // Sizes include the MSM's own (13.6 M pairs, 19-bit keys), ragged tails, every pass count (1..3), constant keys and a heavy skew (half the keys equal).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
