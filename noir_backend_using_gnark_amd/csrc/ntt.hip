@@ -225,10 +225,10 @@ __device__ __forceinline__ void lds_store9(uint4* lo, uint4* hi, uint32_t* top, 
 //   2  forward half of k_ntt_pass29_if: A.tw2, no tables, canonical image if A.canonical
 //   3  k_ntt_pass29_if's third vector, a plain FFTInverse ending: A.tw, * A.post_const, canonical image
 // SUB (compile-time too: its extra live values would cost every other pass a wave of occupancy) adds computeH's closing step.
-// ROWS (the row-batched kernels below): `pre` and `sub` may be per-row operands, found pre_off / sub_off elements further on (0 where all rows share the table).
-template <int G, bool DIF, unsigned THREADS, bool SUB, int MODE, bool UNIT, bool ROWS = false>
+// op_off: `pre` and `sub` may be operands of the workgroup's row, found op_off elements further on (0 where every row shares the table).
+template <int G, bool DIF, unsigned THREADS, bool SUB, int MODE, bool UNIT>
 __device__ __forceinline__ void ntt_group29(const PassArgs& A, uint4* lo, uint4* hi, uint32_t* top, size_t base, unsigned E, unsigned s0,
-                                            bool load_packed, bool apply_pre, bool apply_post, bool store_packed, size_t pre_off = 0, size_t sub_off = 0) {
+                                            bool load_packed, bool apply_pre, bool apply_post, bool store_packed, size_t op_off) {
     constexpr unsigned NE = 1u << G;
     const unsigned L = 1u << A.logL;
     const unsigned ql = DIF ? (A.k - s0 - G) : s0;
@@ -240,7 +240,7 @@ __device__ __forceinline__ void ntt_group29(const PassArgs& A, uint4* lo, uint4*
         for (unsigned e = 0; e < NE; e++) {
             const unsigned t = ((mid0 | (e << ql)) << A.logL) + l;
             x[e] = load_packed ? u29_unpack(lds_load(lo, hi, t)) : lds_load9(lo, hi, top, t);
-            if (MODE == 0 && apply_pre && A.pre) x[e] = u29r_mul(x[e], u29r_load5(gload_fr(A.pre + (ROWS ? pre_off : 0) + base + ((size_t)(mid0 | (e << ql)) << A.bit_lo) + l)));
+            if (MODE == 0 && apply_pre && A.pre) x[e] = u29r_mul(x[e], u29r_load5(gload_fr(A.pre + op_off + base + ((size_t)(mid0 | (e << ql)) << A.bit_lo) + l)));
         }
 #pragma unroll
         for (int sl = 0; sl < G; sl++) {
@@ -290,7 +290,7 @@ __device__ __forceinline__ void ntt_group29(const PassArgs& A, uint4* lo, uint4*
                 if ((MODE == 0 || MODE == 1) && A.post) x[e] = u29r_mul(x[e], u29r_load5(gload_fr(A.post + base + ((size_t)(mid0 | (e << ql)) << A.bit_lo) + l)));
                 else if (MODE == 3 || (MODE == 0 && A.has_post_const)) x[e] = u29r_mul(x[e], u29r_load5(A.post_const));
                 if (SUB) {  // x < 2 r after the product above; sub[i] canonical: the difference stays below 6 r, a legal multiplicand (tools/u29_ntt_model.py)
-                    const U29 c = u29_unpack(gload_fr(A.sub + (ROWS ? sub_off : 0) + base + ((size_t)(mid0 | (e << ql)) << A.bit_lo) + l));
+                    const U29 c = u29_unpack(gload_fr(A.sub + op_off + base + ((size_t)(mid0 | (e << ql)) << A.bit_lo) + l));
                     x[e] = u29r_mul(u29r_sub<4>(x[e], c), u29r_load5(A.post_const));
                 }
             }
@@ -301,22 +301,22 @@ __device__ __forceinline__ void ntt_group29(const PassArgs& A, uint4* lo, uint4*
 }
 
 // all k stages of a pass, GMAX at a time.  packed_in / packed_out: the tile sits in LDS as 8 packed words before / after.
-template <int GMAX, unsigned THREADS, bool DIF, bool SUB, int MODE, bool ROWS = false>
+template <int GMAX, unsigned THREADS, bool DIF, bool SUB, int MODE>
 __device__ __forceinline__ void ntt_stages29(const PassArgs& A, uint4* lo, uint4* hi, uint32_t* top, size_t base, unsigned E, bool packed_in, bool packed_out,
-                                             size_t pre_off = 0, size_t sub_off = 0) {
+                                             size_t op_off) {
     for (unsigned s0 = 0; s0 < A.k;) {
         const unsigned G = (A.k - s0 >= (unsigned)GMAX) ? (unsigned)GMAX : (A.k - s0);
         const bool first = (s0 == 0), last = (s0 + G == A.k);
         const bool lp = first && packed_in, sp = last && packed_out;
         const bool ug = A.unit_skip && A.bit_lo == 0 && (DIF ? last : first);  // the group that holds index bit 0 (uniform)
         if (ug) {
-            if (GMAX >= 3 && G == 3) ntt_group29<(GMAX >= 3 ? 3 : 1), DIF, THREADS, SUB, MODE, true, ROWS>(A, lo, hi, top, base, E, s0, lp, first, last, sp, pre_off, sub_off);
-            else if (G == 2) ntt_group29<2, DIF, THREADS, SUB, MODE, true, ROWS>(A, lo, hi, top, base, E, s0, lp, first, last, sp, pre_off, sub_off);
-            else ntt_group29<1, DIF, THREADS, SUB, MODE, true, ROWS>(A, lo, hi, top, base, E, s0, lp, first, last, sp, pre_off, sub_off);
+            if (GMAX >= 3 && G == 3) ntt_group29<(GMAX >= 3 ? 3 : 1), DIF, THREADS, SUB, MODE, true>(A, lo, hi, top, base, E, s0, lp, first, last, sp, op_off);
+            else if (G == 2) ntt_group29<2, DIF, THREADS, SUB, MODE, true>(A, lo, hi, top, base, E, s0, lp, first, last, sp, op_off);
+            else ntt_group29<1, DIF, THREADS, SUB, MODE, true>(A, lo, hi, top, base, E, s0, lp, first, last, sp, op_off);
         } else {
-            if (GMAX >= 3 && G == 3) ntt_group29<(GMAX >= 3 ? 3 : 1), DIF, THREADS, SUB, MODE, false, ROWS>(A, lo, hi, top, base, E, s0, lp, first, last, sp, pre_off, sub_off);
-            else if (G == 2) ntt_group29<2, DIF, THREADS, SUB, MODE, false, ROWS>(A, lo, hi, top, base, E, s0, lp, first, last, sp, pre_off, sub_off);
-            else ntt_group29<1, DIF, THREADS, SUB, MODE, false, ROWS>(A, lo, hi, top, base, E, s0, lp, first, last, sp, pre_off, sub_off);
+            if (GMAX >= 3 && G == 3) ntt_group29<(GMAX >= 3 ? 3 : 1), DIF, THREADS, SUB, MODE, false>(A, lo, hi, top, base, E, s0, lp, first, last, sp, op_off);
+            else if (G == 2) ntt_group29<2, DIF, THREADS, SUB, MODE, false>(A, lo, hi, top, base, E, s0, lp, first, last, sp, op_off);
+            else ntt_group29<1, DIF, THREADS, SUB, MODE, false>(A, lo, hi, top, base, E, s0, lp, first, last, sp, op_off);
         }
         s0 += G;
         __syncthreads();
@@ -329,10 +329,21 @@ __device__ __forceinline__ uintptr_t pick3(uintptr_t v0, uintptr_t v1, uintptr_t
     const uintptr_t m1 = (uintptr_t)0 - (uintptr_t)(blockIdx.y == 1), m2 = (uintptr_t)0 - (uintptr_t)(blockIdx.y == 2);
     return (v0 & ~(m1 | m2)) | (v1 & m1) | (v2 & m2);
 }
-__device__ __forceinline__ Fr* pass_data(const PassArgs& A) { return reinterpret_cast<Fr*>(pick3((uintptr_t)A.data, (uintptr_t)A.data2, (uintptr_t)A.data3)); }
-__device__ __forceinline__ const Fr* pass_src(const PassArgs& A, const Fr* data) {
+
+// One launch takes the pass over MANY vectors of one domain: blockIdx.z is the row (a single vector is rows = 1), blockIdx.y the vector a / b / c of computeH.
+// What belongs to a row moves by row * stride elements (stride >= N): data / data2 / data3, src / src2 / src3, and `pre` / `sub` where they are operands of the
+// row (computeH's closing transform: pre = b, sub = c; op_stride = 0 where every row shares the table).  Twiddles, a coset table in `post`, tw2: one per domain.
+// One workgroup handles one tile of one row, so a domain below 2^11 leaves lanes of its 512 idle.
+struct RowArgs {
+    size_t stride, op_stride;  // in Fr elements
+};
+// the row's byte offset joins the vector's address before tile_copy_in / tile_copy_out restate its address space: resolved once per workgroup, in scalar registers
+__device__ __forceinline__ Fr* row_data(const PassArgs& A, size_t off) {
+    return reinterpret_cast<Fr*>(pick3((uintptr_t)A.data, (uintptr_t)A.data2, (uintptr_t)A.data3) + off * sizeof(Fr));
+}
+__device__ __forceinline__ const Fr* row_src(const PassArgs& A, const Fr* data, size_t off) {
     const uintptr_t src = pick3((uintptr_t)A.src, (uintptr_t)A.src2, (uintptr_t)A.src3);
-    return src ? reinterpret_cast<const Fr*>(src) : data;
+    return src ? reinterpret_cast<const Fr*>(src + off * sizeof(Fr)) : data;
 }
 template <unsigned THREADS>
 __device__ __forceinline__ void tile_copy_in(const Fr* src, unsigned logL, unsigned bit_lo, uint4* lo, uint4* hi, size_t base, unsigned E) {
@@ -369,76 +380,12 @@ __device__ __forceinline__ void tile_copy_out(Fr* dst, unsigned logL, unsigned b
 }
 
 // 512 lanes: two workgroups per CU (4 waves per SIMD, <= 128 VGPRs); 256 lanes (radix-8 groups, A/B variant): two waves per SIMD.  The register counts are
-// what -Rpass-analysis=kernel-resource-usage shows (123 / 119 for the 512-lane kernels); asking for them with __launch_bounds__(512, 4) gives the same
+// what -Rpass-analysis=kernel-resource-usage shows (512 lanes: 121, 125 with SUB, 107 for k_ntt_pass29_if); asking for them with __launch_bounds__(512, 4) gives the same
 // counts and a schedule that is 1.5 % slower on a 2^26-point transform (measured), so the bound stays implicit -- check the remark when touching the kernels.
 #define ZK_NTT_BOUNDS(THREADS) __launch_bounds__(THREADS)
 
 template <int GMAX, unsigned THREADS, bool SUB = false>
-__global__ ZK_NTT_BOUNDS(THREADS) void k_ntt_pass29(PassArgs A) {
-    prio_mid();
-    extern __shared__ uint4 lds[];
-    const unsigned E = 1u << (A.k + A.logL);
-    uint4* lo = lds;
-    uint4* hi = lds + E;
-    uint32_t* top = reinterpret_cast<uint32_t*>(lds + 2 * E);
-    const unsigned lo_blks = (1u << A.bit_lo) >> A.logL;  // >= 1
-    const size_t tile = blockIdx.x;
-    const size_t hi_idx = tile / lo_blks;
-    const unsigned lo_blk = (unsigned)(tile % lo_blks);
-    const size_t base = (hi_idx << (A.bit_lo + A.k)) + ((size_t)lo_blk << A.logL);
-    Fr* const data = pass_data(A);
-    tile_copy_in<THREADS>(pass_src(A, data), A.logL, A.bit_lo, lo, hi, base, E);
-    __syncthreads();
-    if (A.dif) ntt_stages29<GMAX, THREADS, true, SUB, 0>(A, lo, hi, top, base, E, true, true);
-    else ntt_stages29<GMAX, THREADS, false, SUB, 0>(A, lo, hi, top, base, E, true, true);
-    tile_copy_out<THREADS>(data, A.logL, A.bit_lo, lo, hi, base, E);
-}
-
-// computeH runs FFTInverse(DIF) immediately followed by FFT(DIT, coset) on the same vector: the inverse transform ENDS with the
-// contiguous pass over the low index bits and the forward transform BEGINS with it, on the same tiles -- so the two passes are one
-// kernel: load tile, k DIF stages (A.tw), * A.post (1/N * g^bitrev(i)), k DIT stages (A.tw2), store.  One HBM round trip saved
-// per vector.
-template <int GMAX, unsigned THREADS>
-__global__ ZK_NTT_BOUNDS(THREADS) void k_ntt_pass29_if(PassArgs A) {
-    prio_mid();
-    extern __shared__ uint4 lds[];
-    const unsigned E = 1u << (A.k + A.logL);
-    uint4* lo = lds;
-    uint4* hi = lds + E;
-    uint32_t* top = reinterpret_cast<uint32_t*>(lds + 2 * E);
-    const size_t base = (size_t)blockIdx.x << A.k;  // contiguous tiles only (bit_lo = 0, logL = 0)
-    Fr* const data = pass_data(A);
-    tile_copy_in<THREADS>(pass_src(A, data), 0, 0, lo, hi, base, E);
-    __syncthreads();
-    if (blockIdx.y == 2) {  // the third vector: a plain FFTInverse ending (* post_const, canonical image)
-        ntt_stages29<GMAX, THREADS, true, false, 3>(A, lo, hi, top, base, E, true, true);
-    } else {
-        ntt_stages29<GMAX, THREADS, true, false, 1>(A, lo, hi, top, base, E, true, false);   // inverse half; its post table is applied, limbs stay unpacked
-        ntt_stages29<GMAX, THREADS, false, false, 2>(A, lo, hi, top, base, E, false, true);  // forward half
-    }
-    tile_copy_out<THREADS>(data, 0, 0, lo, hi, base, E);
-}
-
-// ------------------------------------------------------------------------------------------------ row-batched passes
-// The same pass on MANY vectors of one domain in one launch: blockIdx.z is the row, blockIdx.y keeps its meaning (vector a / b / c of computeH).  What belongs
-// to a row moves by row * stride elements (stride >= N): data / data2 / data3, src / src2 / src3, and `pre` / `sub` where they are per-row operands (computeH's
-// closing transform: pre = b, sub = c; pre_stride / sub_stride = 0 where every row shares the table).  Twiddles, a coset table in `post`, tw2: one per domain.
-// One workgroup still handles one tile of one row, so a domain below 2^11 leaves lanes of its 512 idle exactly as in the single-vector kernels.
-// The existing kernels are untouched: ROWS is a template parameter of the stage helpers and their instantiations with ROWS = false compile to what they did.
-struct RowArgs {
-    size_t stride, pre_stride, sub_stride;  // in Fr elements
-};
-// the row's byte offset joins the vector's address before tile_copy_in / tile_copy_out restate its address space: resolved once per workgroup, in scalar registers
-__device__ __forceinline__ Fr* row_data(const PassArgs& A, size_t off) {
-    return reinterpret_cast<Fr*>(pick3((uintptr_t)A.data, (uintptr_t)A.data2, (uintptr_t)A.data3) + off * sizeof(Fr));
-}
-__device__ __forceinline__ const Fr* row_src(const PassArgs& A, const Fr* data, size_t off) {
-    const uintptr_t src = pick3((uintptr_t)A.src, (uintptr_t)A.src2, (uintptr_t)A.src3);
-    return src ? reinterpret_cast<const Fr*>(src + off * sizeof(Fr)) : data;
-}
-
-template <int GMAX, unsigned THREADS, bool SUB = false>
-__global__ ZK_NTT_BOUNDS(THREADS) void k_ntt_pass29_rows(PassArgs A, RowArgs R) {
+__global__ ZK_NTT_BOUNDS(THREADS) void k_ntt_pass29(PassArgs A, RowArgs R) {
     prio_mid();
     extern __shared__ uint4 lds[];
     const unsigned E = 1u << (A.k + A.logL);
@@ -454,14 +401,17 @@ __global__ ZK_NTT_BOUNDS(THREADS) void k_ntt_pass29_rows(PassArgs A, RowArgs R) 
     Fr* const data = row_data(A, row * R.stride);
     tile_copy_in<THREADS>(row_src(A, data, row * R.stride), A.logL, A.bit_lo, lo, hi, base, E);
     __syncthreads();
-    if (A.dif) ntt_stages29<GMAX, THREADS, true, SUB, 0, true>(A, lo, hi, top, base, E, true, true, row * R.pre_stride, row * R.sub_stride);
-    else ntt_stages29<GMAX, THREADS, false, SUB, 0, true>(A, lo, hi, top, base, E, true, true, row * R.pre_stride, row * R.sub_stride);
+    if (A.dif) ntt_stages29<GMAX, THREADS, true, SUB, 0>(A, lo, hi, top, base, E, true, true, row * R.op_stride);
+    else ntt_stages29<GMAX, THREADS, false, SUB, 0>(A, lo, hi, top, base, E, true, true, row * R.op_stride);
     tile_copy_out<THREADS>(data, A.logL, A.bit_lo, lo, hi, base, E);
 }
 
-// k_ntt_pass29_if with the row as blockIdx.z (its `post` is the coset table of the domain: shared)
+// computeH runs FFTInverse(DIF) immediately followed by FFT(DIT, coset) on the same vector: the inverse transform ENDS with the
+// contiguous pass over the low index bits and the forward transform BEGINS with it, on the same tiles -- so the two passes are one
+// kernel: load tile, k DIF stages (A.tw), * A.post (1/N * g^bitrev(i): the domain's table, shared by the rows), k DIT stages (A.tw2), store.
+// One HBM round trip saved per vector.
 template <int GMAX, unsigned THREADS>
-__global__ ZK_NTT_BOUNDS(THREADS) void k_ntt_pass29_if_rows(PassArgs A, RowArgs R) {
+__global__ ZK_NTT_BOUNDS(THREADS) void k_ntt_pass29_if(PassArgs A, RowArgs R) {
     prio_mid();
     extern __shared__ uint4 lds[];
     const unsigned E = 1u << (A.k + A.logL);
@@ -473,11 +423,11 @@ __global__ ZK_NTT_BOUNDS(THREADS) void k_ntt_pass29_if_rows(PassArgs A, RowArgs 
     Fr* const data = row_data(A, off);
     tile_copy_in<THREADS>(row_src(A, data, off), 0, 0, lo, hi, base, E);
     __syncthreads();
-    if (blockIdx.y == 2) {
-        ntt_stages29<GMAX, THREADS, true, false, 3>(A, lo, hi, top, base, E, true, true);
+    if (blockIdx.y == 2) {  // the third vector: a plain FFTInverse ending (* post_const, canonical image)
+        ntt_stages29<GMAX, THREADS, true, false, 3>(A, lo, hi, top, base, E, true, true, 0);
     } else {
-        ntt_stages29<GMAX, THREADS, true, false, 1>(A, lo, hi, top, base, E, true, false);
-        ntt_stages29<GMAX, THREADS, false, false, 2>(A, lo, hi, top, base, E, false, true);
+        ntt_stages29<GMAX, THREADS, true, false, 1>(A, lo, hi, top, base, E, true, false, 0);   // inverse half; its post table is applied, limbs stay unpacked
+        ntt_stages29<GMAX, THREADS, false, false, 2>(A, lo, hi, top, base, E, false, true, 0);  // forward half
     }
     tile_copy_out<THREADS>(data, 0, 0, lo, hi, base, E);
 }
@@ -489,7 +439,7 @@ __global__ void k_scale_table_rows(Fr* a, size_t stride, const Fr* t, size_t row
     if (i < rows) a[i * stride] = a[i * stride] * gload_fr(t);
 }
 
-// a[i] *= t[i]  (used when a transform has no stage to fold a scaling into: N == 1)
+// a[i] *= t[i]  (the coset factor a sharded transform applies outside its block transform)
 __global__ void k_scale_table(Fr* a, const Fr* t, size_t n) {
     prio_mid();
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -620,54 +570,100 @@ static std::vector<PassPlan> plan_passes(unsigned logn) {
 
 static const uint32_t g_tw_and = (uint32_t)ZK_EXP("ZKMI_NTT_TWMASK", 0xffffffffL);
 static const uint32_t g_unit_skip = ZK_EXP("ZKMI_NTT_UNIT", 1) != 0;
-static int launch_pass(Slot* s, hipStream_t st, const PassArgs& A_, bool sat) {
-    PassArgs A = A_;
-    A.tw_and = g_tw_and;
-    A.unit_skip = g_unit_skip;
-    unsigned E = 1u << (A.k + A.logL);
-    size_t tiles = ((size_t)1 << A.logn) / E;
-    const char* name = A.logL ? "ntt_pass_strided" : "ntt_pass_contig";
-    const unsigned ny = sat ? 1 : 1 + (A.data2 ? 1 : 0) + (A.data2 && A.data3 ? 1 : 0);
-    if (sat) ZK_LAUNCH(s, st, name, k_ntt_pass, dim3((unsigned)tiles), dim3(NTT_THREADS), (size_t)E * 32, A);
-    else if (A.sub && g_ntt_g2) ZK_LAUNCH(s, st, name, (k_ntt_pass29<2, 512, true>), dim3((unsigned)tiles, ny), dim3(512), (size_t)E * 36, A);
-    else if (A.sub) ZK_LAUNCH(s, st, name, (k_ntt_pass29<3, 256, true>), dim3((unsigned)tiles, ny), dim3(NTT_THREADS), (size_t)E * 36, A);
-    else if (g_ntt_g2) ZK_LAUNCH(s, st, name, (k_ntt_pass29<2, 512>), dim3((unsigned)tiles, ny), dim3(512), (size_t)E * 36, A);
-    else ZK_LAUNCH(s, st, name, (k_ntt_pass29<3, 256>), dim3((unsigned)tiles, ny), dim3(NTT_THREADS), (size_t)E * 36, A);
+
+// Every transform below takes `rows` vectors of one domain, `stride` elements apart (one vector: rows = 1, stride unused), in the launches of ONE vector:
+// gridDim.z = rows, up to the 65535 a grid's z extent holds; more rows are taken in several launches, never folded into x.
+static constexpr size_t ROWS_PER_LAUNCH = 65535;
+
+// rows of `width` bytes: one plain copy where both sides are contiguous, else a pitched one
+static int copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, hipMemcpyKind kind, hipStream_t st) {
+    if (!width || !rows) return ZK_OK;
+    if (rows == 1 || (dpitch == width && spitch == width)) ZK_HIP(hipMemcpyAsync(dst, src, width * rows, kind, st));
+    else ZK_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, kind, st));
     return ZK_OK;
 }
 
-// Runs the log2(N) stages of one transform as a sequence of tile passes.
-static int run_passes(Slot* s, hipStream_t st, Fr* data, const Domain* dom, int inverse, int dif, const Fr* pre, const Fr* post,
-                      const Fr* post_const, const Fr* src = nullptr, const Fr* sub = nullptr) {
+// One pass: k_ntt_pass29_if where A.tw2 is set, else k_ntt_pass29 (or, sat, the saturated k_ntt_pass: one row only).  A launch over one row carries the name the
+// benchmark's roofline prices as one vector per launch; a launch over more rows the `_rows` name.
+static int launch_pass(Slot* s, hipStream_t st, const PassArgs& A_, const RowArgs& R, size_t rows, bool sat) {
+    static const char* const names[2][3] = {{"ntt_pass_contig", "ntt_pass_strided", "ntt_pass_contig_if"},
+                                            {"ntt_pass_contig_rows", "ntt_pass_strided_rows", "ntt_pass_contig_if_rows"}};
+    const unsigned E = 1u << (A_.k + A_.logL);
+    const unsigned tiles = (unsigned)(((size_t)1 << A_.logn) / E);
+    const unsigned ny = sat ? 1 : 1 + (A_.data2 ? 1 : 0) + (A_.data2 && A_.data3 ? 1 : 0);
+    for (size_t r0 = 0; r0 < rows; r0 += ROWS_PER_LAUNCH) {
+        const unsigned nz = (unsigned)std::min(rows - r0, ROWS_PER_LAUNCH);
+        const char* name = names[nz > 1][A_.tw2 ? 2 : (A_.logL ? 1 : 0)];
+        PassArgs A = A_;
+        A.tw_and = g_tw_and;
+        A.unit_skip = g_unit_skip;
+        const size_t d = r0 * R.stride, o = r0 * R.op_stride;
+        A.data += d;
+        if (A.data2) A.data2 += d;
+        if (A.data3) A.data3 += d;
+        if (A.src) A.src += d;
+        if (A.src2) A.src2 += d;
+        if (A.src3) A.src3 += d;
+        if (A.pre) A.pre += o;
+        if (A.sub) A.sub += o;
+        const dim3 grid(tiles, ny, nz);
+        if (sat) ZK_LAUNCH(s, st, name, k_ntt_pass, dim3(tiles), dim3(NTT_THREADS), (size_t)E * 32, A);
+        else if (A.tw2 && g_ntt_g2) ZK_LAUNCH(s, st, name, (k_ntt_pass29_if<2, 512>), grid, dim3(512), (size_t)E * 36, A, R);
+        else if (A.tw2) ZK_LAUNCH(s, st, name, (k_ntt_pass29_if<3, 256>), grid, dim3(NTT_THREADS), (size_t)E * 36, A, R);
+        else if (A.sub && g_ntt_g2) ZK_LAUNCH(s, st, name, (k_ntt_pass29<2, 512, true>), grid, dim3(512), (size_t)E * 36, A, R);
+        else if (A.sub) ZK_LAUNCH(s, st, name, (k_ntt_pass29<3, 256, true>), grid, dim3(NTT_THREADS), (size_t)E * 36, A, R);
+        else if (g_ntt_g2) ZK_LAUNCH(s, st, name, (k_ntt_pass29<2, 512>), grid, dim3(512), (size_t)E * 36, A, R);
+        else ZK_LAUNCH(s, st, name, (k_ntt_pass29<3, 256>), grid, dim3(NTT_THREADS), (size_t)E * 36, A, R);
+    }
+    return ZK_OK;
+}
+
+// Runs the log2(N) stages of one transform (of each row) as a sequence of tile passes.
+static int run_passes(Slot* s, hipStream_t st, Fr* data, size_t stride, size_t rows, const Domain* dom, int inverse, int dif, const Fr* pre, const Fr* post,
+                      const Fr* post_const, const Fr* src = nullptr, const Fr* sub = nullptr, bool row_ops = false) {
+    // src (optional): the rows of the input live there, `stride` apart like the data, and stay untouched -- the first pass reads them and writes `data`
     // sub (29-bit-limb passes only, with `post` AND `post_const`): the last stage leaves (x * post[i] - sub[i]) * post_const
+    // row_ops: `pre` and `sub` are operands of each row, `stride` apart like the data (else one table for every row)
     const unsigned logn = dom->logn;
     const bool sat = g_ntt_saturated;
-    const Fr* tw = sat ? (inverse ? dom->tw_inv : dom->tw) : (inverse ? dom->tw29_inv : dom->tw29);
-    if (logn == 0) {
-        if (src && src != data) ZK_HIP(hipMemcpyAsync(data, src, sizeof(Fr), hipMemcpyDeviceToDevice, st));
-        if (pre) ZK_LAUNCH(s, st, "ntt_scale", k_scale_table, dim3(1), dim3(64), 0, data, pre, (size_t)1);
-        if (post) ZK_LAUNCH(s, st, "ntt_scale", k_scale_table, dim3(1), dim3(64), 0, data, post, (size_t)1);
-        return ZK_OK;  // 1/N = 1
+    if (sat && rows > 1) {  // the saturated kernels (A/B switch) have no row form: row by row
+        const size_t op = row_ops ? stride : 0;
+        for (size_t i = 0; i < rows; i++)
+            ZK_TRY(run_passes(s, st, data + i * stride, 0, 1, dom, inverse, dif, pre ? pre + i * op : nullptr, post, post_const, src ? src + i * stride : nullptr,
+                              sub ? sub + i * op : nullptr));
+        return ZK_OK;
     }
-    if (sat && src && src != data) {  // the saturated kernels (A/B switch) work in place only
-        ZK_HIP(hipMemcpyAsync(data, src, sizeof(Fr) << logn, hipMemcpyDeviceToDevice, st));
+    if (src == data) src = nullptr;
+    if (logn == 0) {  // rows of one element: a transform of one point is its scaling (1/N = 1)
+        if ((row_ops && pre) || sub) return set_err(ZK_ERR_ARG, "per-row operands need a domain of at least two points");
+        if (src) ZK_TRY(copy_rows(data, stride * sizeof(Fr), src, stride * sizeof(Fr), sizeof(Fr), rows, hipMemcpyDeviceToDevice, st));
+        const unsigned grid = (unsigned)((rows + 255) / 256);
+        const char* name = rows > 1 ? "ntt_scale_rows" : "ntt_scale";
+        if (pre) ZK_LAUNCH(s, st, name, k_scale_table_rows, dim3(grid), dim3(256), 0, data, stride, pre, rows);
+        if (post) ZK_LAUNCH(s, st, name, k_scale_table_rows, dim3(grid), dim3(256), 0, data, stride, post, rows);
+        return ZK_OK;
+    }
+    if (sat && src) {  // the saturated kernels work in place only
+        ZK_TRY(copy_rows(data, stride * sizeof(Fr), src, stride * sizeof(Fr), sizeof(Fr) << logn, rows, hipMemcpyDeviceToDevice, st));
         src = nullptr;
     }
+    const Fr* tw = sat ? (inverse ? dom->tw_inv : dom->tw) : (inverse ? dom->tw29_inv : dom->tw29);
+    const RowArgs R = {stride, row_ops ? stride : 0};
     std::vector<PassPlan> passes = plan_passes(logn);
-    size_t npass = passes.size();
+    const size_t npass = passes.size();
     for (size_t idx = 0; idx < npass; idx++) {
         // DIF walks the bits from the top, DIT from the bottom
         const PassPlan& p = dif ? passes[npass - 1 - idx] : passes[idx];
         PassArgs A;
         A.data2 = nullptr; A.src2 = nullptr; A.data3 = nullptr; A.src3 = nullptr;
-        A.data = data; A.tw = tw; A.tw2 = nullptr; A.src = (idx == 0 && src && src != data) ? src : nullptr; A.logn = logn; A.bit_lo = p.bit_lo; A.k = p.k; A.logL = p.logL; A.dif = dif;
+        A.data = data; A.tw = tw; A.tw2 = nullptr; A.src = (idx == 0) ? src : nullptr; A.logn = logn; A.bit_lo = p.bit_lo; A.k = p.k; A.logL = p.logL; A.dif = dif;
         A.pre = (idx == 0) ? pre : nullptr;
         A.post = (idx + 1 == npass) ? post : nullptr;
         A.has_post_const = (idx + 1 == npass && post_const && !post) ? 1 : 0;
         A.sub = (idx + 1 == npass && !sat) ? sub : nullptr;
         if (A.has_post_const || A.sub) A.post_const = *post_const; else A.post_const = Fr::zero();
         A.canonical = (idx + 1 == npass) ? 1 : 0;
-        ZK_TRY(launch_pass(s, st, A, sat));
+        ZK_TRY(launch_pass(s, st, A, R, rows, sat));
     }
     return ZK_OK;
 }
@@ -675,53 +671,56 @@ static int run_passes(Slot* s, hipStream_t st, Fr* data, const Domain* dom, int 
 // FFTInverse(DIF) with `mid` applied at its end (1/N and whatever scaling follows), then FFT(DIT): as run_passes twice, but the two
 // contiguous passes in the middle are ONE kernel (k_ntt_pass29_if).
 static const bool g_ntt_fuse_if = (ZK_EXP("ZKMI_NTT_FUSE", 1) != 0);  // A/B switch
-static int run_inverse_forward(Slot* s, hipStream_t st, Fr* data, const Domain* dom, const Fr* mid, const Fr* src = nullptr, Fr* data2 = nullptr,
-                               const Fr* src2 = nullptr, Fr* data3 = nullptr, const Fr* src3 = nullptr, const Fr* end3 = nullptr) {
+static int run_inverse_forward(Slot* s, hipStream_t st, Fr* data, size_t stride, size_t rows, const Domain* dom, const Fr* mid, const Fr* src = nullptr,
+                               Fr* data2 = nullptr, const Fr* src2 = nullptr, Fr* data3 = nullptr, const Fr* src3 = nullptr, const Fr* end3 = nullptr) {
     // src (optional): the input lives there and stays untouched -- the first pass reads it and writes `data`
     // data2 / src2 (optional): a second vector taken through the same passes by the same launches (gridDim.y = 2)
     // data3 / src3 / end3 (optional, with data2): a third vector that only takes the INVERSE transform, closed by the constant *end3 (computeH's c), in the
     // launches of the inverse half (gridDim.y = 3)
+    // rows of data2 / data3 / src* lie `stride` apart like those of `data`
     const unsigned logn = dom->logn;
     if (g_ntt_saturated || !g_ntt_fuse_if || logn == 0) {
-        if (data2) {  // the unfused A/B variants take the vectors one after the other
-            ZK_TRY(run_inverse_forward(s, st, data, dom, mid, src));
-            ZK_TRY(run_inverse_forward(s, st, data2, dom, mid, src2));
-            return data3 ? run_passes(s, st, data3, dom, 1, 1, nullptr, nullptr, end3, src3) : ZK_OK;
+        if (rows > 1) {  // the unfused A/B variants have no row form: row by row
+            for (size_t i = 0; i < rows; i++) {
+                const size_t d = i * stride;
+                ZK_TRY(run_inverse_forward(s, st, data + d, 0, 1, dom, mid, src ? src + d : nullptr, data2 ? data2 + d : nullptr, src2 ? src2 + d : nullptr,
+                                           data3 ? data3 + d : nullptr, src3 ? src3 + d : nullptr, end3));
+            }
+            return ZK_OK;
+        }
+        if (data2) {  // and take the vectors one after the other
+            ZK_TRY(run_inverse_forward(s, st, data, 0, 1, dom, mid, src));
+            ZK_TRY(run_inverse_forward(s, st, data2, 0, 1, dom, mid, src2));
+            return data3 ? run_passes(s, st, data3, 0, 1, dom, 1, 1, nullptr, nullptr, end3, src3) : ZK_OK;
         }
         if (src && src != data) ZK_HIP(hipMemcpyAsync(data, src, sizeof(Fr) << logn, hipMemcpyDeviceToDevice, st));
-        ZK_TRY(run_passes(s, st, data, dom, 1, 1, nullptr, mid, nullptr));
-        return run_passes(s, st, data, dom, 0, 0, nullptr, nullptr, nullptr);
+        ZK_TRY(run_passes(s, st, data, 0, 1, dom, 1, 1, nullptr, mid, nullptr));
+        return run_passes(s, st, data, 0, 1, dom, 0, 0, nullptr, nullptr, nullptr);
     }
+    const RowArgs R = {stride, 0};
     std::vector<PassPlan> passes = plan_passes(logn);
     const size_t npass = passes.size();
     PassArgs A;
     A.data = data; A.logn = logn; A.pre = nullptr; A.post = nullptr; A.has_post_const = 0; A.post_const = Fr::zero(); A.tw2 = nullptr;
     A.sub = nullptr;
-    A.tw_and = g_tw_and;
-    A.unit_skip = g_unit_skip;
     A.src = (src && src != data) ? src : nullptr;  // consumed by whichever pass runs first
     A.data2 = data2;
     A.src2 = (data2 && src2 && src2 != data2) ? src2 : nullptr;
     A.data3 = data2 ? data3 : nullptr;
     A.src3 = (A.data3 && src3 && src3 != data3) ? src3 : nullptr;
     if (A.data3) A.post_const = *end3;
-    const unsigned ny = 1 + (data2 ? 1 : 0) + (A.data3 ? 1 : 0);
     for (size_t idx = npass - 1; idx >= 1; idx--) {  // strided passes of the inverse transform, top bits first
         const PassPlan& p = passes[idx];
         A.tw = dom->tw29_inv; A.bit_lo = p.bit_lo; A.k = p.k; A.logL = p.logL; A.dif = 1; A.canonical = 0;
-        ZK_TRY(launch_pass(s, st, A, false));
+        ZK_TRY(launch_pass(s, st, A, R, rows, false));
         A.src = nullptr;
         A.src2 = nullptr;
         A.src3 = nullptr;
     }
-    {
-        const PassPlan& p = passes[0];
-        A.tw = dom->tw29_inv; A.tw2 = dom->tw29; A.bit_lo = 0; A.k = p.k; A.logL = 0; A.dif = 1; A.post = mid;
+    {  // the contiguous passes of both transforms: one launch
+        A.tw = dom->tw29_inv; A.tw2 = dom->tw29; A.bit_lo = 0; A.k = passes[0].k; A.logL = 0; A.dif = 1; A.post = mid;
         A.canonical = (npass == 1) ? 1 : 0;
-        unsigned E = 1u << p.k;
-        size_t tiles = ((size_t)1 << logn) / E;
-        if (g_ntt_g2) ZK_LAUNCH(s, st, "ntt_pass_contig_if", (k_ntt_pass29_if<2, 512>), dim3((unsigned)tiles, ny), dim3(512), (size_t)E * 36, A);
-        else ZK_LAUNCH(s, st, "ntt_pass_contig_if", (k_ntt_pass29_if<3, 256>), dim3((unsigned)tiles, ny), dim3(NTT_THREADS), (size_t)E * 36, A);
+        ZK_TRY(launch_pass(s, st, A, R, rows, false));
         A.post = nullptr;
         A.tw2 = nullptr;
         A.src = nullptr;
@@ -732,141 +731,7 @@ static int run_inverse_forward(Slot* s, hipStream_t st, Fr* data, const Domain* 
     for (size_t idx = 1; idx < npass; idx++) {  // strided passes of the forward transform, low bits first
         const PassPlan& p = passes[idx];
         A.tw = dom->tw29; A.bit_lo = p.bit_lo; A.k = p.k; A.logL = p.logL; A.dif = 0; A.canonical = (idx + 1 == npass) ? 1 : 0;
-        ZK_TRY(launch_pass(s, st, A, false));
-    }
-    return ZK_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ row-batched launchers
-// Twins of launch_pass / run_passes / run_inverse_forward over `rows` vectors `stride` elements apart: the SAME number of launches as for one vector whatever the
-// row count (gridDim.z = rows), up to the 65535 a grid's z extent holds; more rows are taken in several launches, never folded into x.
-static constexpr size_t ROWS_PER_LAUNCH = 65535;
-
-static void advance_rows(PassArgs& A, const RowArgs& R, size_t r0) {
-    const size_t d = r0 * R.stride;
-    A.data += d;
-    if (A.data2) A.data2 += d;
-    if (A.data3) A.data3 += d;
-    if (A.src) A.src += d;
-    if (A.src2) A.src2 += d;
-    if (A.src3) A.src3 += d;
-    if (A.pre) A.pre += r0 * R.pre_stride;
-    if (A.sub) A.sub += r0 * R.sub_stride;
-}
-
-static int launch_pass_rows(Slot* s, hipStream_t st, const PassArgs& A_, const RowArgs& R, size_t rows) {
-    const unsigned E = 1u << (A_.k + A_.logL);
-    const unsigned tiles = (unsigned)(((size_t)1 << A_.logn) / E);
-    const char* name = A_.logL ? "ntt_pass_strided_rows" : "ntt_pass_contig_rows";
-    const unsigned ny = 1 + (A_.data2 ? 1 : 0) + (A_.data2 && A_.data3 ? 1 : 0);
-    for (size_t r0 = 0; r0 < rows; r0 += ROWS_PER_LAUNCH) {
-        const unsigned nz = (unsigned)std::min(rows - r0, ROWS_PER_LAUNCH);
-        PassArgs A = A_;
-        A.tw_and = g_tw_and;
-        A.unit_skip = g_unit_skip;
-        advance_rows(A, R, r0);
-        if (A.sub && g_ntt_g2) ZK_LAUNCH(s, st, name, (k_ntt_pass29_rows<2, 512, true>), dim3(tiles, ny, nz), dim3(512), (size_t)E * 36, A, R);
-        else if (A.sub) ZK_LAUNCH(s, st, name, (k_ntt_pass29_rows<3, 256, true>), dim3(tiles, ny, nz), dim3(NTT_THREADS), (size_t)E * 36, A, R);
-        else if (g_ntt_g2) ZK_LAUNCH(s, st, name, (k_ntt_pass29_rows<2, 512>), dim3(tiles, ny, nz), dim3(512), (size_t)E * 36, A, R);
-        else ZK_LAUNCH(s, st, name, (k_ntt_pass29_rows<3, 256>), dim3(tiles, ny, nz), dim3(NTT_THREADS), (size_t)E * 36, A, R);
-    }
-    return ZK_OK;
-}
-
-// run_passes on `rows` vectors.  pre_stride / sub_stride: 0 = `pre` / `sub` is one table for every row, else the distance between the rows' operands.
-static int run_passes_rows(Slot* s, hipStream_t st, Fr* data, size_t stride, size_t rows, const Domain* dom, int inverse, int dif, const Fr* pre, size_t pre_stride,
-                           const Fr* post, const Fr* post_const, const Fr* sub = nullptr, size_t sub_stride = 0) {
-    const unsigned logn = dom->logn;
-    if (g_ntt_saturated) {  // the saturated kernels (A/B switch) have no row form: row by row
-        for (size_t i = 0; i < rows; i++)
-            ZK_TRY(run_passes(s, st, data + i * stride, dom, inverse, dif, pre ? pre + i * pre_stride : nullptr, post, post_const, nullptr, sub ? sub + i * sub_stride : nullptr));
-        return ZK_OK;
-    }
-    if (logn == 0) {  // rows of one element: a transform of one point is its scaling (1/N = 1)
-        if (pre_stride || sub) return set_err(ZK_ERR_ARG, "per-row operands need a domain of at least two points");
-        const unsigned grid = (unsigned)((rows + 255) / 256);
-        if (pre) ZK_LAUNCH(s, st, "ntt_scale_rows", k_scale_table_rows, dim3(grid), dim3(256), 0, data, stride, pre, rows);
-        if (post) ZK_LAUNCH(s, st, "ntt_scale_rows", k_scale_table_rows, dim3(grid), dim3(256), 0, data, stride, post, rows);
-        return ZK_OK;
-    }
-    const Fr* tw = inverse ? dom->tw29_inv : dom->tw29;
-    const RowArgs R = {stride, pre_stride, sub_stride};
-    std::vector<PassPlan> passes = plan_passes(logn);
-    const size_t npass = passes.size();
-    for (size_t idx = 0; idx < npass; idx++) {
-        const PassPlan& p = dif ? passes[npass - 1 - idx] : passes[idx];
-        PassArgs A;
-        A.data2 = nullptr; A.src2 = nullptr; A.data3 = nullptr; A.src3 = nullptr; A.src = nullptr;
-        A.data = data; A.tw = tw; A.tw2 = nullptr; A.logn = logn; A.bit_lo = p.bit_lo; A.k = p.k; A.logL = p.logL; A.dif = dif;
-        A.pre = (idx == 0) ? pre : nullptr;
-        A.post = (idx + 1 == npass) ? post : nullptr;
-        A.has_post_const = (idx + 1 == npass && post_const && !post) ? 1 : 0;
-        A.sub = (idx + 1 == npass) ? sub : nullptr;
-        if (A.has_post_const || A.sub) A.post_const = *post_const; else A.post_const = Fr::zero();
-        A.canonical = (idx + 1 == npass) ? 1 : 0;
-        ZK_TRY(launch_pass_rows(s, st, A, R, rows));
-    }
-    return ZK_OK;
-}
-
-// run_inverse_forward on `rows` vectors (and their second / third vectors data2 / data3, the same distance apart): in place
-static int run_inverse_forward_rows(Slot* s, hipStream_t st, Fr* data, size_t stride, size_t rows, const Domain* dom, const Fr* mid, Fr* data2 = nullptr,
-                                    Fr* data3 = nullptr, const Fr* end3 = nullptr, const Fr* const* src = nullptr) {
-    // src (optional): the rows of the three inputs live in src[0..2], `stride` apart like the data, and stay untouched -- the first pass reads them
-    const unsigned logn = dom->logn;
-    if (g_ntt_saturated || !g_ntt_fuse_if || logn == 0) {  // the unfused A/B variants: row by row
-        for (size_t i = 0; i < rows; i++)
-            ZK_TRY(run_inverse_forward(s, st, data + i * stride, dom, mid, src ? src[0] + i * stride : nullptr, data2 ? data2 + i * stride : nullptr,
-                                       src ? src[1] + i * stride : nullptr, data3 ? data3 + i * stride : nullptr, src ? src[2] + i * stride : nullptr, end3));
-        return ZK_OK;
-    }
-    const RowArgs R = {stride, 0, 0};
-    std::vector<PassPlan> passes = plan_passes(logn);
-    const size_t npass = passes.size();
-    PassArgs A;
-    A.data = data; A.logn = logn; A.pre = nullptr; A.post = nullptr; A.has_post_const = 0; A.post_const = Fr::zero(); A.tw2 = nullptr;
-    A.sub = nullptr;
-    A.data2 = data2;
-    A.data3 = data2 ? data3 : nullptr;
-    A.src = (src && src[0] != data) ? src[0] : nullptr;  // consumed by whichever pass runs first
-    A.src2 = (src && data2 && src[1] != data2) ? src[1] : nullptr;
-    A.src3 = (src && A.data3 && src[2] != data3) ? src[2] : nullptr;
-    if (A.data3) A.post_const = *end3;
-    const unsigned ny = 1 + (data2 ? 1 : 0) + (A.data3 ? 1 : 0);
-    for (size_t idx = npass - 1; idx >= 1; idx--) {  // strided passes of the inverse transform, top bits first
-        const PassPlan& p = passes[idx];
-        A.tw = dom->tw29_inv; A.bit_lo = p.bit_lo; A.k = p.k; A.logL = p.logL; A.dif = 1; A.canonical = 0;
-        ZK_TRY(launch_pass_rows(s, st, A, R, rows));
-        A.src = nullptr;
-        A.src2 = nullptr;
-        A.src3 = nullptr;
-    }
-    {
-        const PassPlan& p = passes[0];
-        A.tw = dom->tw29_inv; A.tw2 = dom->tw29; A.bit_lo = 0; A.k = p.k; A.logL = 0; A.dif = 1; A.post = mid;
-        A.canonical = (npass == 1) ? 1 : 0;
-        A.tw_and = g_tw_and;
-        A.unit_skip = g_unit_skip;
-        const unsigned E = 1u << p.k;
-        const unsigned tiles = (unsigned)(((size_t)1 << logn) / E);
-        for (size_t r0 = 0; r0 < rows; r0 += ROWS_PER_LAUNCH) {
-            const unsigned nz = (unsigned)std::min(rows - r0, ROWS_PER_LAUNCH);
-            PassArgs B = A;
-            advance_rows(B, R, r0);
-            if (g_ntt_g2) ZK_LAUNCH(s, st, "ntt_pass_contig_if_rows", (k_ntt_pass29_if_rows<2, 512>), dim3(tiles, ny, nz), dim3(512), (size_t)E * 36, B, R);
-            else ZK_LAUNCH(s, st, "ntt_pass_contig_if_rows", (k_ntt_pass29_if_rows<3, 256>), dim3(tiles, ny, nz), dim3(NTT_THREADS), (size_t)E * 36, B, R);
-        }
-        A.post = nullptr;
-        A.tw2 = nullptr;
-        A.src = nullptr;
-        A.src2 = nullptr;
-        A.data3 = nullptr;  // c is done
-        A.src3 = nullptr;
-    }
-    for (size_t idx = 1; idx < npass; idx++) {  // strided passes of the forward transform, low bits first
-        const PassPlan& p = passes[idx];
-        A.tw = dom->tw29; A.bit_lo = p.bit_lo; A.k = p.k; A.logL = p.logL; A.dif = 0; A.canonical = (idx + 1 == npass) ? 1 : 0;
-        ZK_TRY(launch_pass_rows(s, st, A, R, rows));
+        ZK_TRY(launch_pass(s, st, A, R, rows, false));
     }
     return ZK_OK;
 }
@@ -884,40 +749,12 @@ static int ensure_lds_attr() {
         ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29<2, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
         ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_if<3, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
         ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_if<2, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
-        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_rows<3, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
-        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_rows<2, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
-        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_rows<3, 256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
-        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_rows<2, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
-        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_if_rows<3, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
-        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_if_rows<2, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
         g_lds_attr_set |= bit;
     }
     return ZK_OK;
 }
 
-// (*Domain).FFT / FFTInverse on device memory
-int ntt_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn, int inverse, int decimation, int coset) {
-    ZK_TRY(ensure_lds_attr());
-    unsigned need = inverse ? DOM_TW_INV : DOM_TW;
-    if (coset) {
-        if (!inverse) need |= (decimation == ZK_DIT) ? DOM_COSET_REV : DOM_COSET;
-        else need |= (decimation == ZK_DIT) ? DOM_COSET_INV_N : DOM_COSET_INV_N_REV;
-    }
-    Domain* d;
-    ZK_TRY(get_domain(s, st, logn, need, &d));
-    int dif = (decimation == ZK_DIF);
-    if (!inverse) {
-        // FFT: coset scaling first -- DIF by CosetTable[i], DIT (bit-reversed memory order) by CosetTableReversed[i]
-        const Fr* pre = coset ? (dif ? d->coset_tab : d->coset_rev) : nullptr;
-        return run_passes(s, st, d_a, d, 0, dif, pre, nullptr, nullptr);
-    }
-    // FFTInverse: TwiddlesInv, then * CardinalityInv (and CosetTableInv[i] for DIT / CosetTableInvReversed[i] for DIF)
-    const Fr* post = coset ? (dif ? d->coset_inv_n_rev : d->coset_inv_n) : nullptr;
-    Fr cinv = to_dev(d->card_inv);
-    return run_passes(s, st, d_a, d, 1, dif, nullptr, post, &cinv);
-}
-
-// ntt_dev on `rows` vectors, row i at d_a + i * row_stride (row_stride >= 2^logn): one launch per pass for all of them
+// (*Domain).FFT / FFTInverse on device memory: `rows` vectors, row i at d_a + i * row_stride (row_stride >= 2^logn), one launch per pass for all of them
 int ntt_rows_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn, size_t rows, size_t row_stride, int inverse, int decimation, int coset) {
     if (rows == 0) return ZK_OK;
     ZK_TRY(ensure_lds_attr());
@@ -930,13 +767,17 @@ int ntt_rows_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn, size_t rows, s
     ZK_TRY(get_domain(s, st, logn, need, &d));
     const int dif = (decimation == ZK_DIF);
     if (!inverse) {
+        // FFT: coset scaling first -- DIF by CosetTable[i], DIT (bit-reversed memory order) by CosetTableReversed[i]
         const Fr* pre = coset ? (dif ? d->coset_tab : d->coset_rev) : nullptr;
-        return run_passes_rows(s, st, d_a, row_stride, rows, d, 0, dif, pre, 0, nullptr, nullptr);
+        return run_passes(s, st, d_a, row_stride, rows, d, 0, dif, pre, nullptr, nullptr);
     }
+    // FFTInverse: TwiddlesInv, then * CardinalityInv (and CosetTableInv[i] for DIT / CosetTableInvReversed[i] for DIF)
     const Fr* post = coset ? (dif ? d->coset_inv_n_rev : d->coset_inv_n) : nullptr;
     const Fr cinv = to_dev(d->card_inv);
-    return run_passes_rows(s, st, d_a, row_stride, rows, d, 1, dif, nullptr, 0, post, &cinv);
+    return run_passes(s, st, d_a, row_stride, rows, d, 1, dif, nullptr, post, &cinv);
 }
+
+int ntt_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn, int inverse, int decimation, int coset) { return ntt_rows_dev(s, st, d_a, logn, 1, 0, inverse, decimation, coset); }
 
 int bit_reverse_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn) {
     size_t n = (size_t)1 << logn;
@@ -948,6 +789,8 @@ int bit_reverse_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn) {
 static const bool skip_c = (ZK_EXP("ZKMI_H_SKIP_C", 1) != 0);
 static const bool h_batch = ZK_EXP("ZKMI_H_BATCH", 1) == 1;
 static const bool fuse_pw = ZK_EXP("ZKMI_H_FUSE_PW", 1) == 1;
+// the production schedule, which has a row form (compute_h_rows_inplace); everything else takes one triple at a time (compute_h_inplace)
+static bool h_production(unsigned logN) { return skip_c && h_batch && fuse_pw && !g_ntt_saturated && logN > 0; }
 
 // gnark v0.8.0 computeH on device buffers a (in/out, N), b, c (scratch, N); result left in a, bit-reversed order.
 //   3 x FFTInverse(DIF) ; 3 x FFT(DIT, coset) ; a = (a*b - c) / (g^N - 1) ; FFTInverse(a, DIF, coset)
@@ -958,33 +801,28 @@ int compute_h_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned log
     // side (optional): two more streams -- the transforms of b and c run on them, concurrently with a's on `st` (whatever produced the inputs must
     // be ordered before `st`): every pass is load -> butterflies -> store in lock-step over the whole machine at sizes that fit one round of
     // workgroups, so three transforms in flight put one array's loads / stores under another's butterflies.
+    if (!side && h_production(logN)) return compute_h_rows_inplace(s, st, a, b, c, logN, 1, 0, src);
     ZK_TRY(ensure_lds_attr());
     Domain* d;
     ZK_TRY(get_domain(s, st, logN, DOM_TW | DOM_TW_INV | DOM_COSET_REV_N | DOM_COSET_INV_N_REV, &d));
     size_t N = (size_t)1 << logN;
     Fr* vs[3] = {a, b, c};
-    // By linearity (exact field arithmetic, so bit for bit for ANY input): FFTInverse(coset)((a'b' - c') den) = den (FFTInverse(coset)(a'b') - FFTInverse(c)),
-    // where c' = FFT(coset)(FFTInverse(c)) -- the coset transform of c and its way back cancel.  c therefore only needs its first FFTInverse(DIF)
-    // (coefficients, bit-reversed like the result): six transforms instead of gnark's seven.  ZKMI_H_SKIP_C=0 restores the literal sequence.
+    // ZKMI_H_SKIP_C=1 without the whole production schedule: c stays in coefficient form (see compute_h_rows_inplace).  ZKMI_H_SKIP_C=0: the literal sequence.
     if (skip_c && !side && logN > 0) {
         const Fr cinv = to_dev(d->card_inv);
-        // a, b (and c for the inverse half) go through their passes in the SAME launches (gridDim.y = vector): at 2^20 a pass is ONE round of workgroups moving
-        // in lock-step (load, butterflies, store); with two or three rounds per launch one round's loads and stores run under another's butterflies, and seven
-        // launches disappear.  ZKMI_H_BATCH=0 (A/B switch): one vector per launch.
-        if (h_batch) {
-            ZK_TRY(run_inverse_forward(s, st, a, d, d->coset_rev_n, src ? src[0] : nullptr, b, src ? src[1] : nullptr, c, src ? src[2] : nullptr, &cinv));
+        if (h_batch) {  // ZKMI_H_BATCH=0 (A/B switch): one vector per launch
+            ZK_TRY(run_inverse_forward(s, st, a, 0, 1, d, d->coset_rev_n, src ? src[0] : nullptr, b, src ? src[1] : nullptr, c, src ? src[2] : nullptr, &cinv));
         } else {
-            for (int i = 0; i < 2; i++) ZK_TRY(run_inverse_forward(s, st, vs[i], d, d->coset_rev_n, src ? src[i] : nullptr));
-            ZK_TRY(run_passes(s, st, c, d, 1, 1, nullptr, nullptr, &cinv, src ? src[2] : nullptr));
+            for (int i = 0; i < 2; i++) ZK_TRY(run_inverse_forward(s, st, vs[i], 0, 1, d, d->coset_rev_n, src ? src[i] : nullptr));
+            ZK_TRY(run_passes(s, st, c, 0, 1, d, 1, 1, nullptr, nullptr, &cinv, src ? src[2] : nullptr));
         }
         HFr gN = d->coset;
         for (unsigned i = 0; i < logN; i++) gN = gN.sqr();
         const Fr den = to_dev((gN - HFr::one()).inv());
-        // the product a*b rides on the loads of the closing transform's first stage (`pre` = b) and (x - c) * den on the stores of its last one (`sub` = c)
-        // instead of two element-wise kernels (96 B per element each).  ZKMI_H_FUSE_PW=0 (A/B switch): the two kernels.
-        if (fuse_pw && !g_ntt_saturated) return run_passes(s, st, a, d, 1, 1, b, d->coset_inv_n_rev, &den, nullptr, c);
+        // ZKMI_H_FUSE_PW=0 (A/B switch), or the saturated kernels: the product and the closing step as two element-wise kernels
+        if (fuse_pw && !g_ntt_saturated) return run_passes(s, st, a, 0, 1, d, 1, 1, b, d->coset_inv_n_rev, &den, nullptr, c);
         ZK_LAUNCH(s, st, "fr_mul", k_fr_mul, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, a, (const Fr*)a, (const Fr*)b, N);
-        ZK_TRY(run_passes(s, st, a, d, 1, 1, nullptr, d->coset_inv_n_rev, nullptr));
+        ZK_TRY(run_passes(s, st, a, 0, 1, d, 1, 1, nullptr, d->coset_inv_n_rev, nullptr));
         ZK_LAUNCH(s, st, "h_final", k_h_final, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, a, (const Fr*)c, den, N);
         return ZK_OK;
     }
@@ -994,34 +832,34 @@ int compute_h_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned log
         ZK_HIP(hipEventRecord(fork, st));
         for (int i = 0; i < 2; i++) {
             ZK_HIP(hipStreamWaitEvent(side[i], fork, 0));
-            ZK_TRY(run_inverse_forward(s, side[i], vs[i + 1], d, d->coset_rev_n, src ? src[i + 1] : nullptr));
+            ZK_TRY(run_inverse_forward(s, side[i], vs[i + 1], 0, 1, d, d->coset_rev_n, src ? src[i + 1] : nullptr));
             ZK_HIP(hipEventCreateWithFlags(&join[i], hipEventDisableTiming));
             ZK_HIP(hipEventRecord(join[i], side[i]));
         }
-        ZK_TRY(run_inverse_forward(s, st, vs[0], d, d->coset_rev_n, src ? src[0] : nullptr));
+        ZK_TRY(run_inverse_forward(s, st, vs[0], 0, 1, d, d->coset_rev_n, src ? src[0] : nullptr));
         for (int i = 0; i < 2; i++) {
             ZK_HIP(hipStreamWaitEvent(st, join[i], 0));
             (void)hipEventDestroy(join[i]);
         }
         (void)hipEventDestroy(fork);
     } else {
-        for (int i = 0; i < 3; i++) ZK_TRY(run_inverse_forward(s, st, vs[i], d, d->coset_rev_n, src ? src[i] : nullptr));
+        for (int i = 0; i < 3; i++) ZK_TRY(run_inverse_forward(s, st, vs[i], 0, 1, d, d->coset_rev_n, src ? src[i] : nullptr));
     }
     // den = 1 / (g^N - 1)
     HFr gN = d->coset;
     for (unsigned i = 0; i < logN; i++) gN = gN.sqr();
     HFr den = (gN - HFr::one()).inv();
     ZK_LAUNCH(s, st, "h_pointwise", k_h_pointwise, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, a, (const Fr*)b, (const Fr*)c, to_dev(den), N);
-    ZK_TRY(run_passes(s, st, a, d, 1, 1, nullptr, d->coset_inv_n_rev, nullptr));
+    ZK_TRY(run_passes(s, st, a, 0, 1, d, 1, 1, nullptr, d->coset_inv_n_rev, nullptr));
     return ZK_OK;
 }
 
-// compute_h_inplace on `rows` triples, row i at a / b / c + i * row_stride: the six transforms of the production branch above with the row as a grid dimension --
-// as many launches as ONE computeH whatever the row count.  h of row i is left in a + i * row_stride, bit-reversed, as there.
+// computeH's production schedule on `rows` triples, row i at a / b / c + i * row_stride, with the row as a grid dimension: as many launches as ONE computeH whatever
+// the row count.  h of row i is left in a + i * row_stride, bit-reversed.
 int compute_h_rows_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned logN, size_t rows, size_t row_stride, const Fr* const* src) {
     // src (optional): the rows of the three inputs live in src[0..2] (full 2^logN vectors, row_stride apart) and are left untouched
     if (rows == 0) return ZK_OK;
-    if (!(skip_c && h_batch && fuse_pw) || g_ntt_saturated || logN == 0) {  // the A/B variants and the one-point domain: row by row
+    if (!h_production(logN)) {  // the A/B variants and the one-point domain: row by row
         for (size_t i = 0; i < rows; i++) {
             const Fr* si[3] = {src ? src[0] + i * row_stride : nullptr, src ? src[1] + i * row_stride : nullptr, src ? src[2] + i * row_stride : nullptr};
             ZK_TRY(compute_h_inplace(s, st, a + i * row_stride, b + i * row_stride, c + i * row_stride, logN, src ? si : nullptr));
@@ -1031,12 +869,20 @@ int compute_h_rows_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigne
     ZK_TRY(ensure_lds_attr());
     Domain* d;
     ZK_TRY(get_domain(s, st, logN, DOM_TW | DOM_TW_INV | DOM_COSET_REV_N | DOM_COSET_INV_N_REV, &d));
+    // By linearity (exact field arithmetic, so bit for bit for ANY input): FFTInverse(coset)((a'b' - c') den) = den (FFTInverse(coset)(a'b') - FFTInverse(c)),
+    // where c' = FFT(coset)(FFTInverse(c)) -- the coset transform of c and its way back cancel.  c therefore only needs its first FFTInverse(DIF)
+    // (coefficients, bit-reversed like the result): six transforms instead of gnark's seven.
+    // a, b (and c for the inverse half) go through their passes in the SAME launches (gridDim.y = vector): at 2^20 a pass is ONE round of workgroups moving
+    // in lock-step (load, butterflies, store); with two or three rounds per launch one round's loads and stores run under another's butterflies, and seven
+    // launches disappear.
     const Fr cinv = to_dev(d->card_inv);
-    ZK_TRY(run_inverse_forward_rows(s, st, a, row_stride, rows, d, d->coset_rev_n, b, c, &cinv, src));
+    ZK_TRY(run_inverse_forward(s, st, a, row_stride, rows, d, d->coset_rev_n, src ? src[0] : nullptr, b, src ? src[1] : nullptr, c, src ? src[2] : nullptr, &cinv));
     HFr gN = d->coset;
     for (unsigned i = 0; i < logN; i++) gN = gN.sqr();
     const Fr den = to_dev((gN - HFr::one()).inv());
-    return run_passes_rows(s, st, a, row_stride, rows, d, 1, 1, b, row_stride, d->coset_inv_n_rev, &den, c, row_stride);
+    // the product a*b rides on the loads of the closing transform's first stage (`pre` = b) and (x - c) * den on the stores of its last one (`sub` = c)
+    // instead of two element-wise kernels (96 B per element each)
+    return run_passes(s, st, a, row_stride, rows, d, 1, 1, b, d->coset_inv_n_rev, &den, nullptr, c, true);
 }
 
 int fr_mul_dev(Slot* s, hipStream_t st, Fr* out, const Fr* a, const Fr* b, size_t n) {
@@ -1141,7 +987,7 @@ int compute_h_shard_phase(Slot* s, hipStream_t st, int phase, Fr* a, Fr* b, Fr* 
             return ZK_OK;
         case 1:  // blocks (any subset): rest of FFTInverse(DIF), * 1/D * g^bitrev(i), block part of FFT(DIT, coset)
             for (Fr* v : {a, b, c})
-                if (v) ZK_TRY(run_inverse_forward(s, st, v, dM, tb.coset_rev_n));
+                if (v) ZK_TRY(run_inverse_forward(s, st, v, 0, 1, dM, tb.coset_rev_n));
             return ZK_OK;
         case 4:  // first third of phase 2, per array: cross stages of FFT(DIT) on the transposed arrays given
             for (Fr* v : {a, b, c})
@@ -1159,12 +1005,12 @@ int compute_h_shard_phase(Slot* s, hipStream_t st, int phase, Fr* a, Fr* b, Fr* 
             return launch_cross<true>(s, st, a, dD->tw_inv, logM, logg, rank);
         }
         case 3:  // block of a: rest of FFTInverse(DIF, coset) -> this rank's block of h (gnark's bit-reversed order)
-            return run_passes(s, st, a, dM, 1, 1, nullptr, tb.coset_inv_n_rev, nullptr);
+            return run_passes(s, st, a, 0, 1, dM, 1, 1, nullptr, tb.coset_inv_n_rev, nullptr);
         // ---- the six-transform schedule (c stays in coefficient form: compute_h_inplace's shortcut, sharded; one transpose and two transforms of c fewer)
         case 6: {  // blocks (any subset; the schedule uses it for c): rest of FFTInverse(DIF) with 1/D -> block of the coefficients, bit-reversed order
             const Fr cinv = to_dev(dD->card_inv);
             for (Fr* v : {a, b, c})
-                if (v) ZK_TRY(run_passes(s, st, v, dM, 1, 1, nullptr, nullptr, &cinv));
+                if (v) ZK_TRY(run_passes(s, st, v, 0, 1, dM, 1, 1, nullptr, nullptr, &cinv));
             return ZK_OK;
         }
         case 7:  // transposed a, b (after phase 4 on each): a = a * b, then the cross stages of the final FFTInverse(DIF, coset) on a
@@ -1173,7 +1019,7 @@ int compute_h_shard_phase(Slot* s, hipStream_t st, int phase, Fr* a, Fr* b, Fr* 
             return launch_cross<true>(s, st, a, dD->tw_inv, logM, logg, rank);
         case 8: {  // block of a and block of c's coefficients (phase 6): rest of FFTInverse(DIF, coset), then h = (a - c) / (g^D - 1)
             if (!a || !c) return set_err(ZK_ERR_ARG, "phase 8 needs a and c");
-            ZK_TRY(run_passes(s, st, a, dM, 1, 1, nullptr, tb.coset_inv_n_rev, nullptr));
+            ZK_TRY(run_passes(s, st, a, 0, 1, dM, 1, 1, nullptr, tb.coset_inv_n_rev, nullptr));
             HFr gN = dD->coset;
             for (unsigned i = 0; i < logD; i++) gN = gN.sqr();
             const HFr den = (gN - HFr::one()).inv();
@@ -1220,8 +1066,8 @@ int ntt_shard_step(Slot* s, hipStream_t st, int step, Fr* a, unsigned logD, unsi
             return dif ? launch_cross<true>(s, st, a, inverse ? dD->tw_inv : dD->tw, logM, logg, rank)
                        : launch_cross<false>(s, st, a, inverse ? dD->tw_inv : dD->tw, logM, logg, rank);
         case 1:
-            if (!inverse) return run_passes(s, st, a, dM, 0, dif, (coset && !dif) ? tb.coset_rev : nullptr, nullptr, nullptr);
-            return run_passes(s, st, a, dM, 1, dif, nullptr, (coset && dif) ? tb.coset_inv_n_rev : nullptr, &cinv);
+            if (!inverse) return run_passes(s, st, a, 0, 1, dM, 0, dif, (coset && !dif) ? tb.coset_rev : nullptr, nullptr, nullptr);
+            return run_passes(s, st, a, 0, 1, dM, 1, dif, nullptr, (coset && dif) ? tb.coset_inv_n_rev : nullptr, &cinv);
         case 2: {
             if (!coset || (!inverse && !dif) || (inverse && dif)) return ZK_OK;  // nothing left outside the block transform
             const Fr* t = inverse ? tb.coset_inv_n_nat : tb.coset_nat;
@@ -1387,13 +1233,6 @@ int zk_bn254_groth16_compute_h(const zk_fr* a, const zk_fr* b, const zk_fr* c, s
     return slot_sync(g.s, st);
 }
 
-// rows of `width` bytes: one plain copy where both sides are contiguous, else a pitched one
-static int copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, hipMemcpyKind kind, hipStream_t st) {
-    if (!width || !rows) return ZK_OK;
-    if (rows == 1 || (dpitch == width && spitch == width)) ZK_HIP(hipMemcpyAsync(dst, src, width * rows, kind, st));
-    else ZK_HIP(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, kind, st));
-    return ZK_OK;
-}
 static int zero_rows(Fr* dst, size_t pitch_elems, size_t width_elems, size_t rows, hipStream_t st) {
     if (!width_elems || !rows) return ZK_OK;
     if (rows == 1 || pitch_elems == width_elems) ZK_HIP(hipMemsetAsync(dst, 0, width_elems * rows * 32, st));

@@ -1,4 +1,4 @@
-"""Row-batched NTT and computeH (csrc/ntt.hip k_ntt_pass29_rows / k_ntt_pass29_if_rows: the row as blockIdx.z) through the public entries
+"""Row-batched NTT and computeH (csrc/ntt.hip k_ntt_pass29 / k_ntt_pass29_if with more than one row: the row is blockIdx.z) through the public entries
 zk_bn254_ntt_batch[_dev] and zk_bn254_groth16_compute_h_batch[_dev]  (-m gpu).
 
 Every comparison is bit-exact against the C oracle (orc.fr_ntt, orc.groth16_compute_h); computeH rows are also held against the single-vector entry.
