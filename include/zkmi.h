@@ -529,6 +529,31 @@ int zk_bn254_plonk_ratio_batch_dev(uint64_t pk_handle, const void *d_l, const vo
                                    const void *d_gamma, void *d_z, size_t out_stride, void *stream);
 int zk_bn254_fr_batch_invert_dev(void *d_a, size_t n, void *stream);
 
+/* ---- plonk: the quotient (round 3 of plonk.Prove: prove.go's evaluation of the constraints on the coset of the big domain, iop.DivideByXMinusOne, the
+ * inverse coset transform) for MANY witnesses of one resident key -----
+ * For `rows` witnesses of the key `pk_handle` (domain n, big domain N4 = 4n or 8n), each given by its blinded canonical l, r, o (n + 2 coefficients) and z
+ * (n + 3), its public inputs and its own challenges alpha[v], beta[v], gamma[v]:
+ *     h = [ gate + alpha (z(omega X) prod_j (w_j + beta S_j + gamma) - z prod_j (w_j + beta u^j X + gamma)) + alpha^2 (z - 1) L_1 ] / (X^n - 1)
+ * with gate = ql l + qr r + qm l r + qo o + qk and qk completed with the row's public inputs, evaluated on the coset of the big domain and brought back to
+ * canonical form, regular order: the 3 (n + 2) coefficients H[0] | H[1] | H[2] that zk_bn254_plonk_prove commits, bit for bit.
+ * Row v of l, r, o, z starts at element v * in_stride (in_stride >= n + 3), its n_public public inputs at element v * pub_stride of d_pub (pub_stride >=
+ * n_public; an array of solutions with pub_stride = n_vars works; d_pub may be NULL for a key without public inputs), its h at element v * out_stride
+ * (out_stride >= 3 (n + 2)).  The inputs are only read; elements between the rows of d_h are not touched.
+ * d_status: one int32 per row, written for EVERY row: 0, or 1 where the quotient is not a polynomial (some coefficient of h at or above 3 (n + 2) is non-zero:
+ * the witness violates the constraints).  Such a row does not fail the call: the return code is ZK_OK, the row's 3 (n + 2) coefficients are still the
+ * transform's, and every other row is unaffected.
+ * The row is a grid dimension: one launch per step for all rows (spread, one transform over the 4 * rows polynomials, qk, the quotient kernel, the inverse
+ * transform, the tail), whatever their number; one row is rows = 1 of the same launches.  Workspace: 5 * N4 elements per row (plus n where the key has more
+ * than 32 public inputs) from the slot's arena, at most 1 GiB at a time: more rows run in chunks.  The key's per-proof workspace is not used, so calls on one
+ * key overlap each other and a proof in flight.
+ * INPUT CONTRACT: canonical fr.Element images in Montgomery form (< r), as above.
+ * ARGUMENT ERRORS, decided before a device is looked for: a null pointer, in_stride < n + 3, pub_stride < n_public, out_stride < 3 (n + 2), d_h or d_status
+ * overlapping an input or each other -> ZK_ERR_ARG; an unknown key -> ZK_ERR_HANDLE; rows == 0 -> ZK_OK, nothing happens.
+ * STREAMS: synchronises `stream` (NULL: the slot's own) before it returns, like the entries above. */
+int zk_bn254_plonk_quotient_batch_dev(uint64_t pk_handle, const void *d_l, const void *d_r, const void *d_o, const void *d_z, size_t in_stride, const void *d_pub,
+                                      size_t pub_stride, size_t rows, const void *d_alpha, const void *d_beta, const void *d_gamma, void *d_h, size_t out_stride,
+                                      void *d_status, void *stream);
+
 /* ---- the callers either side of the PLONK path: the reference's exported entry points, restated over the device path -----------------------
  * PlonkPreprocess (gnark_backend_ffi/main.go:58-78) and PlonkProveWithPK (main.go:24-37) take the ACIR as JSON (acir/acir.go:17-75), the witness
  * values as the hex felt vector (internal/backend/helpers.go:24-33) and the key as hex of ProvingKey.WriteTo (helpers.go:49-60, 82-87); the

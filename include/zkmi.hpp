@@ -405,6 +405,22 @@ inline Error Prove(const ProvingKey& pk, const fr::Vector& solution, const fr::E
     return make_error(zk_bn254_plonk_prove(pk.handle(), solution.data(), solution.size(), 0, blinders, challenges, proof->bytes));
 }
 
+// Round 3 of plonk.Prove -- the quotient -- for `rows` witnesses of one key in the launches of one (zk_bn254_plonk_quotient_batch_dev, whose comment in zkmi.h
+// says the rest).  Everything lives on the device: row v of the blinded canonical l, r, o (n + 2 coefficients) and z (n + 3) at element v * in_stride, of the public
+// inputs at v * pub_stride of `pub` (a solutions array with pub_stride = NbVariables() works), alpha / beta / gamma one element per row.  Row v's 3 (n + 2)
+// coefficients go to d_h + v * out_stride and its verdict to d_status[v] (int32: 1 = not a polynomial, which fails neither the call nor the other rows).
+struct QuotientRows {
+    const void *l = nullptr, *r = nullptr, *o = nullptr, *z = nullptr;
+    size_t in_stride = 0;
+    const void* pub = nullptr;
+    size_t pub_stride = 0;
+    const void *alpha = nullptr, *beta = nullptr, *gamma = nullptr;
+};
+inline Error ComputeQuotientBatch(const ProvingKey& pk, const QuotientRows& in, size_t rows, void* d_h, size_t out_stride, void* d_status, void* stream = nullptr) {
+    return make_error(zk_bn254_plonk_quotient_batch_dev(pk.handle(), in.l, in.r, in.o, in.z, in.in_stride, in.pub, in.pub_stride, rows, in.alpha, in.beta, in.gamma, d_h,
+                                                        out_stride, d_status, stream));
+}
+
 // plonk.Verify(proof, vk, publicWitness) on the host: vk = the bytes of VerifyingKey.WriteTo, srs supplies the two G2 points InitKZG attaches.
 // *accepted <- the verdict; malformed encodings come back as errors (what upstream's ReadFrom returns).
 inline Error Verify(const Proof& proof, const std::vector<uint8_t>& vk, const kzg::SRS& srs, const fr::Vector& public_witness, bool* accepted) {

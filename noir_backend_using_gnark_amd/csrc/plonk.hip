@@ -20,6 +20,7 @@
 #include <chrono>
 #include <functional>
 #include <memory>
+#include <shared_mutex>
 #include <thread>
 #include <vector>
 
@@ -477,6 +478,42 @@ __global__ __launch_bounds__(256) void k_quotient(QuotArgs A) {
 // 31-bit limbs would overflow a 64-bit column), products < 2.4, the last sum < 8.1, t < 2.6 -> one partial reduction, canonical image out.
 // The schedule below is restated statement by statement in tools/u29_ntt_model.py (quotient_schedule): bound propagation + exactness against the field formula,
 // run by the CPU suite (tests/test_limb_models.py) -- edit both or the suite fails.
+// One coset point of it: i the point's position (bit-reversed layout), is that of omega * x, xn_inv = 1 / (x^n - 1) there.  k_quotient29 and its row form
+// k_quotient29_rows both call this, so there is ONE schedule for the model to restate.
+struct QuotKey {
+    const Fr *ql, *qr, *qm, *qo, *s1, *s2, *s3, *l1, *id;              // the key's nine tables, as in QuotArgs
+};
+__device__ __forceinline__ Fr quotient29_point(const Fr* __restrict__ el, const Fr* __restrict__ er, const Fr* __restrict__ eo, const Fr* __restrict__ ez,
+                                               const Fr* eqk, const QuotKey& K, size_t i, size_t is, const Fr& alpha, const Fr& beta, const Fr& gamma,
+                                               const Fr& beta_u, const Fr& beta_uu, const Fr& xn_inv) {
+    const Fr fl = ld(el + i), fr = ld(er + i), fo = ld(eo + i), fz = ld(ez + i), fx = ld(K.id + i);
+    const U29 l = u29_unpack(fl), r = u29_unpack(fr), o = u29_unpack(fo), z = u29_unpack(fz);
+    // gate = ql l + qr r + qm (l r) + qo o + qk
+    U29 gate = u29r_mul(l, u29r_load5(ld(K.ql + i)));
+    gate = u29_add(gate, u29r_mul(r, u29r_load5(ld(K.qr + i))));
+    gate = u29_add(gate, u29r_mul(u29r_mul(l, u29r_load5(fr)), u29r_load5(ld(K.qm + i))));
+    gate = u29_add(gate, u29r_mul(o, u29r_load5(ld(K.qo + i))));
+    gate = u29_add(gate, u29_unpack(ld(eqk + i)));
+    const U29 g = u29_unpack(gamma), g5 = u29r_load5(gamma), x5 = u29r_load5(fx);
+    // a = (l + g + beta x) (r + g + beta u x) (o + g + beta u^2 x) z
+    U29 a = u29_add(u29_add(l, g), u29r_mul(u29_unpack(fx), u29r_load5(beta)));
+    a = u29r_mul(a, u29_wnorm(u29_add(u29_add(u29r_load5(fr), g5), u29r_mul(x5, u29r_load5(beta_u)))));
+    a = u29r_mul(a, u29_wnorm(u29_add(u29_add(u29r_load5(fo), g5), u29r_mul(x5, u29r_load5(beta_uu)))));
+    a = u29r_mul(a, u29r_load5(fz));
+    // b = (l + g + beta s1) (r + g + beta s2) (o + g + beta s3) z(omega x)
+    const U29 b5 = u29r_load5(beta);
+    U29 b = u29_add(u29_add(l, g), u29r_mul(u29_unpack(ld(K.s1 + i)), b5));
+    b = u29r_mul(b, u29_wnorm(u29_add(u29_add(u29r_load5(fr), g5), u29r_mul(u29r_load5(ld(K.s2 + i)), b5))));
+    b = u29r_mul(b, u29_wnorm(u29_add(u29_add(u29r_load5(fo), g5), u29r_mul(u29r_load5(ld(K.s3 + i)), b5))));
+    b = u29r_mul(b, u29r_load5(ld(ez + is)));
+    // t = ((one alpha + (b - a)) alpha + gate) / (x^n - 1),  one = (z - 1) L1
+    const U29 a5 = u29r_load5(alpha);
+    const U29 one = u29r_mul(u29r_sub<4>(z, u29_unpack(Fr::one())), u29r_load5(ld(K.l1 + i)));
+    U29 t = u29_add(u29r_mul(one, a5), u29r_sub<4>(b, a));
+    t = u29_add(u29r_mul(t, a5), gate);
+    t = u29r_mul(t, u29r_load5(xn_inv));
+    return u29r_pack(u29r_reduce(t), true);
+}
 __global__ __launch_bounds__(256, 4) void k_quotient29(QuotArgs A) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t N4 = (size_t)1 << A.logN4;
@@ -485,33 +522,95 @@ __global__ __launch_bounds__(256, 4) void k_quotient29(QuotArgs A) {
     const unsigned rho = 1u << A.log_rho;
     const unsigned js = (j + rho) & (unsigned)(N4 - 1);  // z(omega * x): omega = W^rho
     const size_t is = brev(js, A.logN4);
-    const Fr fl = ld(A.el + i), fr = ld(A.er + i), fo = ld(A.eo + i), fz = ld(A.ez + i), fx = ld(A.id + i);
-    const U29 l = u29_unpack(fl), r = u29_unpack(fr), o = u29_unpack(fo), z = u29_unpack(fz);
-    // gate = ql l + qr r + qm (l r) + qo o + qk
-    U29 gate = u29r_mul(l, u29r_load5(ld(A.ql + i)));
-    gate = u29_add(gate, u29r_mul(r, u29r_load5(ld(A.qr + i))));
-    gate = u29_add(gate, u29r_mul(u29r_mul(l, u29r_load5(fr)), u29r_load5(ld(A.qm + i))));
-    gate = u29_add(gate, u29r_mul(o, u29r_load5(ld(A.qo + i))));
-    gate = u29_add(gate, u29_unpack(ld(A.eqk + i)));
-    const U29 g = u29_unpack(A.gamma), g5 = u29r_load5(A.gamma), x5 = u29r_load5(fx);
-    // a = (l + g + beta x) (r + g + beta u x) (o + g + beta u^2 x) z
-    U29 a = u29_add(u29_add(l, g), u29r_mul(u29_unpack(fx), u29r_load5(A.beta)));
-    a = u29r_mul(a, u29_wnorm(u29_add(u29_add(u29r_load5(fr), g5), u29r_mul(x5, u29r_load5(A.beta_u)))));
-    a = u29r_mul(a, u29_wnorm(u29_add(u29_add(u29r_load5(fo), g5), u29r_mul(x5, u29r_load5(A.beta_uu)))));
-    a = u29r_mul(a, u29r_load5(fz));
-    // b = (l + g + beta s1) (r + g + beta s2) (o + g + beta s3) z(omega x)
-    const U29 b5 = u29r_load5(A.beta);
-    U29 b = u29_add(u29_add(l, g), u29r_mul(u29_unpack(ld(A.s1 + i)), b5));
-    b = u29r_mul(b, u29_wnorm(u29_add(u29_add(u29r_load5(fr), g5), u29r_mul(u29r_load5(ld(A.s2 + i)), b5))));
-    b = u29r_mul(b, u29_wnorm(u29_add(u29_add(u29r_load5(fo), g5), u29r_mul(u29r_load5(ld(A.s3 + i)), b5))));
-    b = u29r_mul(b, u29r_load5(ld(A.ez + is)));
-    // t = ((one alpha + (b - a)) alpha + gate) / (x^n - 1),  one = (z - 1) L1
-    const U29 a5 = u29r_load5(A.alpha);
-    const U29 one = u29r_mul(u29r_sub<4>(z, u29_unpack(Fr::one())), u29r_load5(ld(A.l1 + i)));
-    U29 t = u29_add(u29r_mul(one, a5), u29r_sub<4>(b, a));
-    t = u29_add(u29r_mul(t, a5), gate);
-    t = u29r_mul(t, u29r_load5(A.xn_inv[j & (rho - 1)]));
-    A.out[i] = u29r_pack(u29r_reduce(t), true);
+    const QuotKey K = {A.ql, A.qr, A.qm, A.qo, A.s1, A.s2, A.s3, A.l1, A.id};
+    A.out[i] = quotient29_point(A.el, A.er, A.eo, A.ez, A.eqk, K, i, is, A.alpha, A.beta, A.gamma, A.beta_u, A.beta_uu, A.xn_inv[j & (rho - 1)]);
+}
+
+// ------------------------------------------------------------------------------------------------ row form of the quotient (quotient_rows_dev below)
+// Round 3 with the ROW as a grid dimension (blockIdx.y): R witnesses of one key, every row with its own challenges and public inputs.  The workspace of a chunk of
+// R rows is 5 R rows of N4 elements, polynomial-major: l rows, r rows, o rows, z rows, qk rows -- so the first 4 R rows are ONE call of ntt_rows_dev.
+// zero-padded copies of the four blinded polynomials: blockIdx.z = polynomial (l, r, o: n + 2 coefficients, z: n + 3), row v of it at src + v * in_stride
+__global__ __launch_bounds__(256) void k_quot_spread_rows(const Fr* __restrict__ l, const Fr* __restrict__ r, const Fr* __restrict__ o, const Fr* __restrict__ z,
+                                                          size_t in_stride, uint32_t n, unsigned logN4, Fr* __restrict__ ws) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x, N4 = (size_t)1 << logN4;
+    if (p >= N4) return;
+    const unsigned k = blockIdx.z;
+    const size_t row = blockIdx.y, len = (size_t)n + (k == 3 ? 3 : 2);
+    const Fr* __restrict__ src = k == 0 ? l : k == 1 ? r : k == 2 ? o : z;
+    ws[((size_t)k * gridDim.y + row) * N4 + p] = p < len ? ld(src + row * in_stride + p) : Fr::zero();
+}
+// k_qk_coset, row blockIdx.y: public inputs at pub + row * pub_stride, completed qk to out + row * N4
+__global__ __launch_bounds__(256) void k_qk_coset_rows(const Fr* __restrict__ e_cqk, const Fr* __restrict__ e_l1, const Fr* __restrict__ pub, size_t pub_stride,
+                                                       const Fr* __restrict__ lqk, uint32_t npub, unsigned logN4, unsigned log_rho, Fr* __restrict__ out) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t N4 = (size_t)1 << logN4;
+    if (p >= N4) return;
+    const size_t row = blockIdx.y;
+    const Fr* __restrict__ sol = pub + row * pub_stride;
+    const uint32_t j = __brev((uint32_t)p) >> (32 - logN4);
+    Fr v = ld(e_cqk + p);
+    for (uint32_t i = 0; i < npub; i++) {
+        const Fr d = ld(sol + i) - ld(lqk + i);
+        const uint32_t q = __brev((j - (i << log_rho)) & (uint32_t)(N4 - 1)) >> (32 - logN4);  // w = W^rho, rho = N4 / n
+        v = v + d * ld(e_l1 + q);
+    }
+    out[row * N4 + p] = v;
+}
+// the literal sequence for more public inputs: LQk with row blockIdx.y's public inputs in front (Lagrange form, n elements per row) ...
+__global__ __launch_bounds__(256) void k_qk_complete_rows(const Fr* __restrict__ lqk, const Fr* __restrict__ pub, size_t pub_stride, uint32_t npub, uint32_t n,
+                                                          Fr* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t row = blockIdx.y;
+    out[row * n + i] = i < npub ? ld(pub + row * pub_stride + i) : ld(lqk + i);
+}
+// ... and, after the inverse transform (DIF: bit-reversed), its zero-padded copy in regular order in the row's N4 elements: BitReverse folded into the spread
+__global__ __launch_bounds__(256) void k_qk_spread_rows(const Fr* __restrict__ small, unsigned logn, unsigned logN4, Fr* __restrict__ out) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x, N4 = (size_t)1 << logN4, n = (size_t)1 << logn;
+    if (p >= N4) return;
+    const size_t row = blockIdx.y;
+    out[row * N4 + p] = p < n ? ld(small + row * n + brev((unsigned)p, logn)) : Fr::zero();
+}
+struct QuotRowsArgs {
+    const Fr *el, *er, *eo, *ez, *eqk;                                 // row 0 of each; row v is v * N4 further
+    QuotKey key;
+    Fr* out;                                                           // rows N4 apart; may alias eqk
+    const Fr *alpha, *beta, *gamma;                                    // one per row, on the device
+    Fr u, uu;                                                          // the coset shift of the small domain and its square
+    Fr xn_inv[8];
+    unsigned logN4, log_rho;
+};
+// k_quotient29, row blockIdx.y: the row's challenges come from device arrays, beta u and beta u^2 are formed here (exact products: the canonical images the
+// host hands to k_quotient29)
+__global__ __launch_bounds__(256, 4) void k_quotient29_rows(QuotRowsArgs A) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t N4 = (size_t)1 << A.logN4;
+    if (i >= N4) return;
+    const unsigned j = brev((unsigned)i, A.logN4);
+    const unsigned rho = 1u << A.log_rho;
+    const unsigned js = (j + rho) & (unsigned)(N4 - 1);  // z(omega * x): omega = W^rho
+    const size_t is = brev(js, A.logN4);
+    const size_t row = blockIdx.y, off = row * N4;
+    const Fr alpha = ld(A.alpha + row), beta = ld(A.beta + row), gamma = ld(A.gamma + row);
+    Fr beta_u = beta * A.u, beta_uu = beta * A.uu;
+    // the same for every lane of the workgroup: kept in scalar registers like the arguments of k_quotient29 they stand for, not in sixteen vector registers
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        beta_u.l[k] = __builtin_amdgcn_readfirstlane(beta_u.l[k]);
+        beta_uu.l[k] = __builtin_amdgcn_readfirstlane(beta_uu.l[k]);
+    }
+    A.out[off + i] = quotient29_point(A.el + off, A.er + off, A.eo + off, A.ez + off, A.eqk + off, A.key, i, is, alpha, beta, gamma, beta_u, beta_uu,
+                                      A.xn_inv[j & (rho - 1)]);
+}
+// row blockIdx.y: h[0 .. keep) to the caller's row; status[row] |= 1 if any of h[keep .. N4) is non-zero (the caller zeroes status first)
+__global__ __launch_bounds__(256) void k_quot_tail_rows(const Fr* __restrict__ h, unsigned logN4, size_t keep, Fr* __restrict__ out, size_t out_stride,
+                                                        int* __restrict__ status) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x, N4 = (size_t)1 << logN4;
+    if (p >= N4) return;
+    const size_t row = blockIdx.y;
+    const Fr v = ld(h + row * N4 + p);
+    if (p < keep) out[row * out_stride + p] = v;
+    else if (!v.is_zero()) atomicOr(status + row, 1);
 }
 
 // linearised polynomial (prove.go computeLinearizedPolynomial), len = n + 3 coefficients
@@ -611,6 +710,9 @@ struct PlonkPK {
     // per-proof workspace (one proof at a time per key)
     Fr *w_big[5] = {}, *w_small = nullptr;
     std::shared_ptr<std::mutex> mu;
+    // held shared by a call that only READS the key's tables and brings its own workspace (zk_bn254_plonk_quotient_batch_dev): such calls overlap each other and
+    // a proof in flight; zk_bn254_plonk_pk_free takes it exclusively before the key is destroyed
+    std::shared_ptr<std::shared_mutex> live;
     std::vector<void*> allocs;
     size_t bytes = 0;  // HBM held by the key
 };
@@ -883,6 +985,7 @@ static int finish_pk(PlonkPK* P, Slot* s, hipStream_t st) {
     for (int k = 0; k < 5; k++) ZK_TRY(pk_alloc(P, &P->w_big[k], N4));
     ZK_TRY(pk_alloc(P, &P->w_small, 16 * (n + 8)));
     P->mu = std::make_shared<std::mutex>();
+    P->live = std::make_shared<std::shared_mutex>();
     return slot_sync(s, st);
 }
 
@@ -1051,6 +1154,75 @@ static int ratio_dev_args(const void* l, const void* r, const void* o, size_t in
     if (spans_overlap(z, zb, l, ib) || spans_overlap(z, zb, r, ib) || spans_overlap(z, zb, o, ib) || spans_overlap(z, zb, sigma, sigma_elems * sizeof(Fr)) ||
         spans_overlap(z, zb, beta, rows * sizeof(Fr)) || spans_overlap(z, zb, gamma, rows * sizeof(Fr)))
         return set_err(ZK_ERR_ARG, "d_z overlaps an input");
+    return ZK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ round 3 for R witnesses of one key
+// The quotient h = numerator / (X^n - 1) of `rows` witnesses, canonical, 3(n + 2) coefficients each, and a verdict per row.  Per chunk of rows, whatever their number:
+//   k_quot_spread_rows            l, r, o, z zero-padded into 4 R rows of N4
+//   ntt_rows_dev(4 R rows)        FFT(DIF, coset): the four polynomials of every witness share each pass
+//   qk, npub <= PLONK_PI_DIRECT_MAX:  k_qk_coset_rows
+//       above:                    k_qk_complete_rows, ntt_rows_dev(R rows of n, inverse, DIF), k_qk_spread_rows (BitReverse folded in), ntt_rows_dev(R rows, DIF, coset)
+//   k_quotient29_rows             into the qk rows, as the prover's k_quotient29 overwrites qk
+//   ntt_rows_dev(R rows)          FFTInverse(DIT, coset)
+//   k_quot_tail_rows              3(n + 2) coefficients out, status[row] = 1 iff anything above them is non-zero
+// One row is R = 1 of the same launches.  Workspace: 5 N4 elements per row (+ n where qk takes the literal sequence) from the slot's arena, QUOT_SCRATCH bytes at
+// a time; more rows than fit go in chunks on the same stream.  The key's own per-proof workspace is not touched.
+constexpr size_t QUOT_SCRATCH = (size_t)1 << 30;
+static bool quot_qk_direct(const PlonkPK* P) { return P->n_public <= PLONK_PI_DIRECT_MAX && P->logN4 >= 2; }
+static size_t quot_row_bytes(const PlonkPK* P) { return (5 * P->N4 + (quot_qk_direct(P) ? 0 : P->n)) * sizeof(Fr); }
+static size_t quot_chunk(const PlonkPK* P, size_t rows) { return std::min(std::min(rows, RATIO_GRID_ROWS), std::max<size_t>(1, QUOT_SCRATCH / quot_row_bytes(P))); }
+// 1 / (x^n - 1) on the coset of the big domain: x = g W^j  =>  x^n = g^n (W^n)^j, W^n of order rho <= 8
+static void quot_xn_inv(const PlonkPK* P, const Domain* d1, Fr out[8]) {
+    HFr gn = d1->coset, Wn = d1->gen;
+    for (unsigned i = 0; i < P->logn; i++) { gn = gn.sqr(); Wn = Wn.sqr(); }
+    HFr cur = gn;
+    for (unsigned j = 0; j < 8; j++) {
+        out[j] = j < (1u << P->log_rho) ? to_dev((cur - HFr::one()).inv()) : Fr::zero();
+        cur = cur * Wn;
+    }
+}
+// row v: blinded canonical l, r, o (n + 2) and z (n + 3) at + v * in_stride, public inputs at pub + v * pub_stride, challenges d_alpha / d_beta / d_gamma[v]
+// (device), h to h + v * out_stride, verdict to status[v].  ws: chunk * quot_row_bytes(P) bytes.
+static int quotient_rows_dev(Slot* s, hipStream_t st, const PlonkPK* P, const Fr* l, const Fr* r, const Fr* o, const Fr* z, size_t in_stride, const Fr* pub,
+                             size_t pub_stride, size_t rows, const Fr* d_alpha, const Fr* d_beta, const Fr* d_gamma, Fr* h, size_t out_stride, int* status, Fr* ws,
+                             size_t chunk) {
+    const size_t n = P->n, N4 = P->N4, keep = 3 * (n + 2);
+    const unsigned logN4 = P->logN4;
+    const bool direct = quot_qk_direct(P);
+    Domain* d1;
+    ZK_TRY(get_domain(s, st, logN4, DOM_TW, &d1));
+    QuotRowsArgs A;
+    A.key = {P->e[0], P->e[1], P->e[2], P->e[3], P->e[4], P->e[5], P->e[6], P->e[7], P->e[8]};
+    A.u = to_dev(P->u); A.uu = to_dev(P->u * P->u);
+    quot_xn_inv(P, d1, A.xn_inv);
+    A.logN4 = logN4; A.log_rho = P->log_rho;
+    for (size_t first = 0; first < rows; first += chunk) {
+        const unsigned R = (unsigned)std::min(chunk, rows - first);
+        Fr *qk = ws + 4 * (size_t)R * N4, *small = qk + (size_t)R * N4;
+        const size_t in = first * in_stride;
+        ZK_LAUNCH(s, st, "plonk_quotient_spread_rows", k_quot_spread_rows, dim3(grid_of(N4), R, 4), dim3(256), 0, l + in, r + in, o + in, z + in, in_stride, (uint32_t)n,
+                  logN4, ws);
+        ZK_TRY(ntt_rows_dev(s, st, ws, logN4, 4 * (size_t)R, N4, 0, ZK_DIF, 1));
+        const Fr* pubc = pub + first * pub_stride;  // never read when the key has no public inputs
+        if (direct) {
+            ZK_LAUNCH(s, st, "plonk_qk_coset_rows", k_qk_coset_rows, dim3(grid_of(N4), R), dim3(256), 0, (const Fr*)P->e_cqk, (const Fr*)P->e[7], pubc, pub_stride,
+                      (const Fr*)P->lqk, (uint32_t)P->n_public, logN4, P->log_rho, qk);
+        } else {
+            ZK_LAUNCH(s, st, "plonk_qk_complete_rows", k_qk_complete_rows, dim3(grid_of(n), R), dim3(256), 0, (const Fr*)P->lqk, pubc, pub_stride, (uint32_t)P->n_public,
+                      (uint32_t)n, small);
+            ZK_TRY(ntt_rows_dev(s, st, small, P->logn, R, n, 1, ZK_DIF, 0));
+            ZK_LAUNCH(s, st, "plonk_qk_spread_rows", k_qk_spread_rows, dim3(grid_of(N4), R), dim3(256), 0, (const Fr*)small, P->logn, logN4, qk);
+            ZK_TRY(ntt_rows_dev(s, st, qk, logN4, R, N4, 0, ZK_DIF, 1));
+        }
+        A.el = ws; A.er = ws + (size_t)R * N4; A.eo = ws + 2 * (size_t)R * N4; A.ez = ws + 3 * (size_t)R * N4; A.eqk = qk; A.out = qk;
+        A.alpha = d_alpha + first; A.beta = d_beta + first; A.gamma = d_gamma + first;
+        ZK_LAUNCH(s, st, "plonk_quotient_rows", k_quotient29_rows, dim3(grid_of(N4), R), dim3(256), 0, A);
+        ZK_TRY(ntt_rows_dev(s, st, qk, logN4, R, N4, 1, ZK_DIT, 1));  // LagrangeCoset (bit-reversed) -> canonical (regular)
+        ZK_HIP(hipMemsetAsync(status + first, 0, (size_t)R * sizeof(int), st));
+        ZK_LAUNCH(s, st, "plonk_quotient_tail_rows", k_quot_tail_rows, dim3(grid_of(N4), R), dim3(256), 0, (const Fr*)qk, logN4, keep, h + first * out_stride, out_stride,
+                  status + first);
+    }
     return ZK_OK;
 }
 
@@ -1440,6 +1612,10 @@ int zk_bn254_plonk_pk_free(uint64_t handle) {
         g_ppks.erase(it);
     }
     { std::lock_guard<std::mutex> lk(*P->mu); }  // a proof in flight finishes first
+    {   // and so does every call that reads the key's tables
+        const std::shared_ptr<std::shared_mutex> live = P->live;
+        std::unique_lock<std::shared_mutex> lk(*live);
+    }
     pk_destroy(P);
     return ZK_OK;
 }
@@ -1986,6 +2162,56 @@ int zk_bn254_plonk_ratio_batch_dev(uint64_t handle, const void* d_l, const void*
     ZK_TRY(ratio_rows_dev(g.s, st, d0, (const Fr*)P->sig, (const Fr*)d_l, (const Fr*)d_r, (const Fr*)d_o, in_stride, rows, (const Fr*)d_beta, (const Fr*)d_gamma, (Fr*)d_z,
                           out_stride, W));
     return slot_sync(g.s, st);
+}
+
+// ---- round 3 for many witnesses of one resident key (quotient_rows_dev above).  Argument errors are decided before a device is looked for; the key's tables are
+// only read and the workspace is the slot's arena, so the key's per-proof mutex is not taken: calls overlap each other and a proof in flight.
+int zk_bn254_plonk_quotient_batch_dev(uint64_t handle, const void* d_l, const void* d_r, const void* d_o, const void* d_z, size_t in_stride, const void* d_pub,
+                                      size_t pub_stride, size_t rows, const void* d_alpha, const void* d_beta, const void* d_gamma, void* d_h, size_t out_stride,
+                                      void* d_status, void* stream) {
+    if (!d_l || !d_r || !d_o || !d_z || !d_alpha || !d_beta || !d_gamma || !d_h || !d_status) return set_err(ZK_ERR_ARG, "null pointer");
+    if (rows == 0) return ZK_OK;
+    PlonkPK* P;
+    std::shared_ptr<std::shared_mutex> live;
+    std::shared_lock<std::shared_mutex> alive;
+    {   // the table of keys is the host's: an unknown handle is answered without a device.  A key found here is not being freed yet (zk_bn254_plonk_pk_free
+        // erases it under this mutex before it asks for `live`), so the shared lock is granted at once and keeps the key alive from here on
+        std::lock_guard<std::mutex> lk(g_ppk_mu);
+        auto it = g_ppks.find(handle);
+        if (it == g_ppks.end()) return set_err(ZK_ERR_HANDLE, "unknown PLONK proving-key handle %llu", (unsigned long long)handle);
+        P = it->second;
+        live = P->live;
+        alive = std::shared_lock<std::shared_mutex>(*live);
+    }
+    const size_t n = P->n, N4 = P->N4, npub = P->n_public, keep = 3 * (n + 2);
+    if (keep > N4) return set_err(ZK_ERR_ARG, "a domain of %zu rows has no quotient of 3 (n + 2) coefficients on %zu points", n, N4);
+    if (npub && !d_pub) return set_err(ZK_ERR_ARG, "null pointer");
+    if (in_stride < n + 3) return set_err(ZK_ERR_ARG, "in_stride = %zu is below n + 3 = %zu", in_stride, n + 3);
+    if (npub && pub_stride < npub) return set_err(ZK_ERR_ARG, "pub_stride = %zu is below the %zu public inputs", pub_stride, npub);
+    if (out_stride < keep) return set_err(ZK_ERR_ARG, "out_stride = %zu is below 3 (n + 2) = %zu", out_stride, keep);
+    {
+        const size_t hb = rows_span(rows, out_stride, keep), sb = rows * sizeof(int), cb = rows * sizeof(Fr);
+        const void* in[8] = {d_l, d_r, d_o, d_z, d_pub, d_alpha, d_beta, d_gamma};
+        const size_t ib[8] = {rows_span(rows, in_stride, n + 2), rows_span(rows, in_stride, n + 2), rows_span(rows, in_stride, n + 2), rows_span(rows, in_stride, n + 3),
+                              npub ? rows_span(rows, pub_stride, npub) : 0, cb, cb, cb};
+        for (int k = 0; k < 8; k++)
+            if (spans_overlap(d_h, hb, in[k], ib[k]) || spans_overlap(d_status, sb, in[k], ib[k])) return set_err(ZK_ERR_ARG, "d_h or d_status overlaps an input");
+        if (spans_overlap(d_h, hb, d_status, sb)) return set_err(ZK_ERR_ARG, "d_h overlaps d_status");
+    }
+    ZK_ON_ENTRY_OF(handle);
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    Domain *d0, *d1;
+    ZK_TRY(get_domain(g.s, st, P->logn, DOM_TW_INV, &d0));  // every table the transforms below ask for, before the arena is carved
+    ZK_TRY(get_domain(g.s, st, P->logN4, DOM_TW | DOM_TW_INV | DOM_COSET | DOM_COSET_INV_N, &d1));
+    const size_t chunk = quot_chunk(P, rows);
+    ZK_TRY(g.s->reserve(chunk * quot_row_bytes(P) + 4096));
+    Fr* ws = (Fr*)g.s->alloc(chunk * quot_row_bytes(P));
+    if (!ws) return set_err(ZK_ERR_HIP, "quotient batch: workspace");
+    ZK_TRY(quotient_rows_dev(g.s, st, P, (const Fr*)d_l, (const Fr*)d_r, (const Fr*)d_o, (const Fr*)d_z, in_stride, (const Fr*)d_pub, pub_stride, rows, (const Fr*)d_alpha,
+                             (const Fr*)d_beta, (const Fr*)d_gamma, (Fr*)d_h, out_stride, (int*)d_status, ws, chunk));
+    return slot_sync(g.s, st);  // the workspace lives in the slot's arena
 }
 
 // fr.BatchInvert in place on n device elements: a zero stays a zero.  k_batch_inverse with its scratch from the slot's arena, at most RATIO_SCRATCH bytes at a time.

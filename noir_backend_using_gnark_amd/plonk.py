@@ -69,6 +69,29 @@ class ProvingKey:
         and `out` (made here when None) is returned.  Every shape / dtype / stride / count error is raised before the library is called."""
         return _pk_ratio_batch(self, l, r, o, beta, gamma, rows=rows, in_stride=in_stride, out_stride=out_stride, out=out)
 
+    @property
+    def n_public(self) -> int:
+        """NbPublicVariables"""
+        if self.vk is not None:
+            return int(self.vk["n_public"])
+        k = C.c_size_t(0)
+        check(lib().zk_bn254_plonk_pk_info(self.handle, None, C.byref(k), None, None))
+        return int(k.value)
+
+    def quotient_batch(self, l, r, o, z, public, alpha, beta, gamma, *, rows: int | None = None, in_stride: int | None = None, pub_stride: int | None = None,
+                       out_stride: int | None = None, out=None, status=None):
+        """Round 3 of `rows` proofs against this key (zk_bn254_plonk_quotient_batch_dev; include/zkmi.h says the rest): from the blinded canonical l, r, o (n + 2
+        coefficients), z (n + 3), the public inputs and alpha, beta, gamma of each row to the 3 (n + 2) coefficients of its quotient and a verdict per row
+        (int32: 0, or 1 where the quotient is not a polynomial -- which fails neither the call nor the other rows).  Two forms, every shape / dtype / stride /
+        count / overlap error raised before the library is called:
+          host    l, r, o: (rows, n + 2, 4) uint64 arrays, z: (rows, n + 3, 4), public: (rows, n_public, 4), alpha, beta, gamma: (rows, 4)
+                  -> (h, status), new arrays of (rows, 3 (n + 2), 4) uint64 and (rows,) int32
+          device  device buffers / pointers; rows is required; row v of l, r, o, z at element v * in_stride (default n + 3), of the public inputs at v * pub_stride
+                  (default n_public), of h at v * out_stride (default 3 (n + 2)) of `out`; `out` and `status` must overlap nothing else (made here when None)
+                  -> (out, status)"""
+        return quotient_batch(self, l, r, o, z, public, alpha, beta, gamma, rows=rows, in_stride=in_stride, pub_stride=pub_stride, out_stride=out_stride, out=out,
+                              status=status)
+
     def free(self):
         if self.handle.value:
             check(lib().zk_bn254_plonk_pk_free(self.handle))
@@ -181,25 +204,29 @@ def _host_perm(perm, n):
     return np.ascontiguousarray(perm, dtype=np.uint32)
 
 
-def _dev_geometry(bufs, n, rows, in_stride, out_stride, out, extra=()):
-    """the checks of a call on device rows, before the library: bufs = (name, buffer) of l, r, o; extra = (name, buffer, bytes) of what else is read"""
+def _dev_geometry(bufs, n, rows, in_stride, out_stride, out, extra=(), out_width=None):
+    """the checks of a call on device rows, before the library: bufs = (name, buffer) of the rows read, n elements each (the smallest in_stride); extra = (name,
+    buffer, bytes) of what else is read; out_width: elements per row of `out` (the smallest out_stride) where that is not n"""
     if rows is None:
         raise ValueError("rows is required with device-resident data")
     rows = int(rows)
-    in_stride, out_stride = int(n if in_stride is None else in_stride), int(n if out_stride is None else out_stride)
+    wide = n if out_width is None else out_width
+    in_stride, out_stride = int(n if in_stride is None else in_stride), int(wide if out_stride is None else out_stride)
     if rows < 0:
         raise ValueError("rows must not be negative")
-    if in_stride < n or out_stride < n:
+    if out_width is None and (in_stride < n or out_stride < n):
         raise ValueError("in_stride = %d / out_stride = %d is below the domain size %d" % (in_stride, out_stride, n))
-    span = lambda stride: ((rows - 1) * stride + n) * 32 if rows else 0
+    if in_stride < n or out_stride < wide:
+        raise ValueError("in_stride = %d / out_stride = %d is below the %d / %d elements of a row" % (in_stride, out_stride, n, wide))
+    span = lambda stride, width=n: ((rows - 1) * stride + width) * 32 if rows else 0
     reads = [(name, b, span(in_stride)) for name, b in bufs] + list(extra)
-    for name, b, nbytes in reads + ([("out", out, span(out_stride))] if out is not None else []):
+    for name, b, nbytes in reads + ([("out", out, span(out_stride, wide))] if out is not None else []):
         if not isinstance(b, _DEV):
             raise TypeError("%s must be a device buffer or a device pointer, like l" % name)
         if isinstance(b, _lib.DeviceBuffer) and nbytes > b.nbytes:
             raise ValueError("%s: %d bytes do not fit the device buffer (%d bytes)" % (name, nbytes, b.nbytes))
     if out is not None:
-        lo, hi = _ptr(out), _ptr(out) + span(out_stride)
+        lo, hi = _ptr(out), _ptr(out) + span(out_stride, wide)
         for name, b, nbytes in reads:
             if nbytes and _ptr(b) < hi and lo < _ptr(b) + nbytes:
                 raise ValueError("out overlaps %s" % name)
@@ -315,3 +342,101 @@ def _pk_ratio_batch(self, l, r, o, beta, gamma, *, rows: int | None = None, in_s
         for b in bufs:
             b.free()
 
+
+
+# ---- round 3 for many witnesses: the quotient with the row as a grid dimension (zk_bn254_plonk_quotient_batch_dev)
+def _host_rows_of(name, a, widths):
+    """_host_rows for a row of one of `widths` elements"""
+    a = _host_rows(name, a)
+    if a.shape[1] not in widths:
+        raise ValueError("%s has shape %s, not (rows, %s, 4)" % (name, a.shape, " or ".join(str(w) for w in widths)))
+    return a
+
+
+def quotient_batch(pk: ProvingKey, l, r, o, z, public, alpha, beta, gamma, *, rows: int | None = None, in_stride: int | None = None, pub_stride: int | None = None,
+                   out_stride: int | None = None, out=None, status=None):
+    """ProvingKey.quotient_batch"""
+    n, npub = pk.domain_size, pk.n_public
+    keep = 3 * (n + 2)
+    bufs = []
+    if isinstance(l, _DEV):
+        cnt = 0 if rows is None else max(int(rows), 0)
+        pub_stride = int(npub if pub_stride is None else pub_stride)
+        if pub_stride < npub:
+            raise ValueError("pub_stride = %d is below the %d public inputs" % (pub_stride, npub))
+        if npub == 0 and public is None:
+            public = 0
+        extra = [("z", z, ((cnt - 1) * int(n + 3 if in_stride is None else in_stride) + n + 3) * 32 if cnt else 0),
+                 ("public", public, ((cnt - 1) * pub_stride + npub) * 32 if cnt and npub else 0),
+                 ("alpha", alpha, cnt * 32), ("beta", beta, cnt * 32), ("gamma", gamma, cnt * 32)]
+        if in_stride is not None and int(in_stride) < n + 3:
+            raise ValueError("in_stride = %d is below n + 3 = %d" % (in_stride, n + 3))
+        rows, in_stride, out_stride = _dev_geometry((("l", l), ("r", r), ("o", o)), n + 2, rows, n + 3 if in_stride is None else in_stride, out_stride, out, extra,
+                                                    out_width=keep)
+        if status is not None:
+            if not isinstance(status, _DEV):
+                raise TypeError("status must be a device buffer or a device pointer, like l")
+            if isinstance(status, _lib.DeviceBuffer) and rows * 4 > status.nbytes:
+                raise ValueError("status: %d bytes do not fit the device buffer (%d bytes)" % (rows * 4, status.nbytes))
+            lo, hi = _ptr(status), _ptr(status) + rows * 4
+            span = ((rows - 1) * in_stride + n + 2) * 32 if rows else 0
+            for name, b, nbytes in [(k, v, span) for k, v in (("l", l), ("r", r), ("o", o))] + extra + \
+                                   ([("out", out, ((rows - 1) * out_stride + keep) * 32 if rows else 0)] if out is not None else []):
+                if rows and nbytes and _ptr(b) < hi and lo < _ptr(b) + nbytes:
+                    raise ValueError("status overlaps %s" % name)
+        made = []
+        if out is None:
+            out = _lib.DeviceBuffer(max(((rows - 1) * out_stride + keep) * 32 if rows else 0, 32))
+            made.append(out)
+        if status is None:
+            status = _lib.DeviceBuffer(max(rows * 4, 32))
+            made.append(status)
+        host = None
+    else:
+        l, r, o = (_host_rows_of(k, v, (n + 2, n + 3)) for k, v in (("l", l), ("r", r), ("o", o)))
+        z = _host_rows_of("z", z, (n + 3,))
+        cnt = l.shape[0]
+        if not (r.shape[0] == o.shape[0] == z.shape[0] == cnt):
+            raise ValueError("l, r, o and z have %d, %d, %d and %d rows" % (cnt, r.shape[0], o.shape[0], z.shape[0]))
+        if rows is not None and int(rows) != cnt:
+            raise ValueError("rows = %d != %d rows of the arrays" % (rows, cnt))
+        if not (isinstance(public, np.ndarray) and public.dtype == np.uint64 and public.flags["C_CONTIGUOUS"]):
+            raise TypeError("public must be a C-contiguous uint64 numpy array")
+        if public.shape != (cnt, npub, 4):
+            raise ValueError("public has shape %s, not (%d, %d, 4)" % (public.shape, cnt, npub))
+        for name, v, want in (("in_stride", in_stride, n + 3), ("pub_stride", pub_stride, npub), ("out_stride", out_stride, keep)):
+            if v is not None and int(v) != want:
+                raise ValueError("the rows of a host array are contiguous: %s must be %d" % (name, want))
+        if out is not None or status is not None:
+            raise ValueError("out and status belong to the device form: the host form returns new arrays")
+        alpha, beta, gamma = _host_challenges("alpha", alpha, cnt), _host_challenges("beta", beta, cnt), _host_challenges("gamma", gamma, cnt)
+        host = np.zeros((cnt, keep, 4), dtype=np.uint64)
+        if cnt == 0:
+            return host, np.zeros((0,), dtype=np.int32)
+        rows, in_stride, pub_stride, out_stride = cnt, n + 3, npub, keep
+
+        def padded(a):
+            if a.shape[1] == n + 3:
+                return a
+            w = np.zeros((cnt, n + 3, 4), dtype=np.uint64)
+            w[:, :n + 2] = a
+            return w
+        bufs = [_lib.DeviceBuffer.from_numpy(v) for v in (padded(l), padded(r), padded(o), z, public, alpha, beta, gamma)]
+        l, r, o, z, public, alpha, beta, gamma = bufs
+        out, status = _lib.DeviceBuffer(host.nbytes), _lib.DeviceBuffer(max(cnt * 4, 32))
+        bufs += [out, status]
+        made = []
+    try:
+        p = lambda b: C.c_void_p(_ptr(b))
+        check(lib().zk_bn254_plonk_quotient_batch_dev(pk.handle, p(l), p(r), p(o), p(z), C.c_size_t(in_stride), p(public), C.c_size_t(pub_stride), C.c_size_t(rows),
+                                                      p(alpha), p(beta), p(gamma), p(out), C.c_size_t(out_stride), p(status), C.c_void_p(0)))
+        if host is None:
+            return out, status
+        return out.to_numpy(np.uint64, host.shape), status.to_numpy(np.int32, (rows,))
+    except Exception:
+        for b in made:
+            b.free()
+        raise
+    finally:
+        for b in bufs:
+            b.free()
