@@ -554,6 +554,47 @@ int zk_bn254_plonk_quotient_batch_dev(uint64_t pk_handle, const void *d_l, const
                                       size_t pub_stride, size_t rows, const void *d_alpha, const void *d_beta, const void *d_gamma, void *d_h, size_t out_stride,
                                       void *d_status, void *stream);
 
+/* ---- plonk: the openings (rounds 4 and 5 of plonk.Prove: the evaluations at zeta and omega zeta, kzg.Open of Z, computeLinearizedPolynomial, the folded
+ * quotient, kzg.BatchOpenSinglePoint's fold and its division by X - zeta) for MANY witnesses of one resident key -----
+ * The row is a grid dimension and every per-row challenge is read from a device array: the launches of a call do not depend on the number of rows (4, 7 and 5
+ * per chunk for the three entries), nothing is copied to the host inside a call, and one row is rows = 1 of the same kernels, so row v of a call is bit for
+ * bit the one-row call on that row.  The commitments of the outputs are the caller's.
+ *   zk_bn254_fr_poly_open_rows_dev      the ingredient: for each row v, d_values[v] = f_v(a_v) with f_v the `len` coefficients (len >= 1) at d_f + v * in_stride
+ *       (in_stride >= len) and a_v = d_points[v]; where d_q is not NULL, q_v = (f_v - f_v(a_v)) / (X - a_v) (kzg.dividePolyByXminusA), len - 1 coefficients
+ *       at d_q + v * q_stride (q_stride >= len - 1; nothing when len == 1).  d_q may be NULL (evaluate only), d_f itself with q_stride == in_stride (in place:
+ *       element len - 1 of each row stays as it was), or disjoint from d_f.  The Horner suffix scan in three passes on the plan K = max(8, ceil(len / 2^18))
+ *       coefficients per lane, 256 lanes per workgroup; the powers a^K and a^(256 K) of a row's point are computed once per row.
+ *   zk_bn254_plonk_linearize_batch_dev  round 4.  In, per row v: the blinded canonical l, r, o (n + 2 coefficients) and z (n + 3) at element v * in_stride
+ *       (in_stride >= n + 3), the 3 (n + 2) coefficients H[0] | H[1] | H[2] that zk_bn254_plonk_quotient_batch_dev wrote at v * h_stride (h_stride >=
+ *       3 (n + 2)), alpha[v], beta[v], gamma[v], zeta[v].  Out, per row v:
+ *         d_values + 8 v          foldedH(zeta), lin(zeta), l(zeta), r(zeta), o(zeta), s1(zeta), s2(zeta), z(omega zeta): the proof's order
+ *         d_zquot + v out_stride  the n + 2 coefficients of (z - z(omega zeta)) / (X - omega zeta)
+ *         d_lin + v out_stride    the n + 3 coefficients of the linearised polynomial
+ *                                   (alpha c_z + lag) z + alpha c_s3 s3 + l(zeta) r(zeta) qm + l(zeta) ql + r(zeta) qr + o(zeta) qo + qk, with
+ *                                   c_s3 = (l(zeta) + beta s1(zeta) + gamma) (r(zeta) + beta s2(zeta) + gamma) z(omega zeta) beta,
+ *                                   c_z = -(l(zeta) + beta zeta + gamma) (r(zeta) + beta u zeta + gamma) (o(zeta) + beta u^2 zeta + gamma),
+ *                                   lag = (zeta^n - 1) / (zeta - 1) * alpha^2 / n, where 1 / 0 = 0 as fr.Element.Inverse has it
+ *         d_fh + v out_stride     the n + 2 coefficients of h1 + zeta^(n+2) h2 + zeta^(2(n+2)) h3
+ *       with out_stride >= n + 3.  These are the values and polynomials of zk_bn254_plonk_prove, bit for bit.
+ *   zk_bn254_plonk_open_batch_dev       round 5's polynomial.  In, per row v: fh, l, r, o (n + 2 coefficients) and lin (n + 3) at element v * in_stride
+ *       (in_stride >= n + 3), zeta[v] and kzg_gamma[v] = g, the challenge of kzg.BatchOpenSinglePoint (derived by the caller from the digests and values of round
+ *       4).  Out: d_q + v * out_stride, the n + 2 coefficients (out_stride >= n + 2) of (folded - folded(zeta)) / (X - zeta) with
+ *       folded = fh + g lin + g^2 l + g^3 r + g^4 o + g^5 s1 + g^6 s2; d_value[v] = folded(zeta), which is sum_i g^i claimed_i.
+ * Elements between the rows of an output are not touched; the inputs are only read.  Workspace: the slot's arena, at most 1 GiB and 65,535 rows at a time: more
+ * rows run in chunks on the same stream.  The key's per-proof workspace is not used, so calls on one key overlap each other and a proof in flight.
+ * INPUT CONTRACT: canonical fr.Element images in Montgomery form (< r), as above.
+ * ARGUMENT ERRORS, decided before a device is looked for: a null pointer (but for the d_q of the ingredient), len == 0, a stride below what is said above, an
+ * output overlapping an input or another output (but for the in-place form of the ingredient) -> ZK_ERR_ARG; an unknown key -> ZK_ERR_HANDLE; rows == 0 ->
+ * ZK_OK, nothing happens.
+ * STREAMS: each synchronises `stream` (NULL: the slot's own) before it returns, like the entries above. */
+int zk_bn254_fr_poly_open_rows_dev(const void *d_f, size_t in_stride, size_t len, size_t rows, const void *d_points, void *d_q, size_t q_stride, void *d_values,
+                                   void *stream);
+int zk_bn254_plonk_linearize_batch_dev(uint64_t pk_handle, const void *d_l, const void *d_r, const void *d_o, const void *d_z, size_t in_stride, const void *d_h,
+                                       size_t h_stride, size_t rows, const void *d_alpha, const void *d_beta, const void *d_gamma, const void *d_zeta, void *d_values,
+                                       void *d_zquot, void *d_lin, void *d_fh, size_t out_stride, void *stream);
+int zk_bn254_plonk_open_batch_dev(uint64_t pk_handle, const void *d_fh, const void *d_lin, const void *d_l, const void *d_r, const void *d_o, size_t in_stride,
+                                  size_t rows, const void *d_zeta, const void *d_kzg_gamma, void *d_q, size_t out_stride, void *d_value, void *stream);
+
 /* ---- the callers either side of the PLONK path: the reference's exported entry points, restated over the device path -----------------------
  * PlonkPreprocess (gnark_backend_ffi/main.go:58-78) and PlonkProveWithPK (main.go:24-37) take the ACIR as JSON (acir/acir.go:17-75), the witness
  * values as the hex felt vector (internal/backend/helpers.go:24-33) and the key as hex of ProvingKey.WriteTo (helpers.go:49-60, 82-87); the

@@ -32,6 +32,12 @@ inline Error make_error(int rc) {
 namespace fr {
 typedef zk_fr Element;  // Montgomery, 4 x u64 little-endian limbs: gnark-crypto's memory image
 typedef std::vector<Element> Vector;
+// Device rows of polynomials, each opened at its own point (zk_bn254_fr_poly_open_rows_dev): d_values[v] = f_v(d_points[v]) and, where d_q is given, the len - 1
+// coefficients of kzg.dividePolyByXminusA(f_v, f_v(a_v), a_v) at d_q + v * q_stride (d_q = d_f with q_stride = in_stride divides in place).
+inline Error PolyOpenRows(const void* d_f, size_t in_stride, size_t len, size_t rows, const void* d_points, void* d_q, size_t q_stride, void* d_values,
+                          void* stream = nullptr) {
+    return make_error(zk_bn254_fr_poly_open_rows_dev(d_f, in_stride, len, rows, d_points, d_q, q_stride, d_values, stream));
+}
 }  // namespace fr
 
 namespace ecc {
@@ -419,6 +425,36 @@ struct QuotientRows {
 inline Error ComputeQuotientBatch(const ProvingKey& pk, const QuotientRows& in, size_t rows, void* d_h, size_t out_stride, void* d_status, void* stream = nullptr) {
     return make_error(zk_bn254_plonk_quotient_batch_dev(pk.handle(), in.l, in.r, in.o, in.z, in.in_stride, in.pub, in.pub_stride, rows, in.alpha, in.beta, in.gamma, d_h,
                                                         out_stride, d_status, stream));
+}
+
+// Rounds 4 and 5 of plonk.Prove for `rows` witnesses of one key (zk_bn254_plonk_linearize_batch_dev, zk_bn254_plonk_open_batch_dev; zkmi.h says the rest), all on
+// the device.  Linearize: from the rows of round 3 (l, r, o, z at v * in_stride, h at v * h_stride) and alpha / beta / gamma / zeta per row to the eight values
+// of the proof at d_values + 8 v and, v * out_stride apart, the quotient of z at omega zeta (n + 2), the linearised polynomial (n + 3), the folded quotient (n + 2).
+struct LinearizeRows {
+    const void *l = nullptr, *r = nullptr, *o = nullptr, *z = nullptr;
+    size_t in_stride = 0;
+    const void* h = nullptr;
+    size_t h_stride = 0;
+    const void *alpha = nullptr, *beta = nullptr, *gamma = nullptr, *zeta = nullptr;
+};
+struct LinearizedRows {
+    void *values = nullptr, *zquot = nullptr, *lin = nullptr, *fh = nullptr;
+    size_t out_stride = 0;
+};
+inline Error LinearizeBatch(const ProvingKey& pk, const LinearizeRows& in, size_t rows, const LinearizedRows& out, void* stream = nullptr) {
+    return make_error(zk_bn254_plonk_linearize_batch_dev(pk.handle(), in.l, in.r, in.o, in.z, in.in_stride, in.h, in.h_stride, rows, in.alpha, in.beta, in.gamma, in.zeta,
+                                                         out.values, out.zquot, out.lin, out.fh, out.out_stride, stream));
+}
+// Open: kzg.BatchOpenSinglePoint's quotient of (fh, lin, l, r, o, s1, s2) at zeta[v] under the challenge kzg_gamma[v]: n + 2 coefficients at d_q + v * out_stride,
+// the folded value at d_value[v].
+struct OpenRows {
+    const void *fh = nullptr, *lin = nullptr, *l = nullptr, *r = nullptr, *o = nullptr;
+    size_t in_stride = 0;
+    const void *zeta = nullptr, *kzg_gamma = nullptr;
+};
+inline Error OpenBatch(const ProvingKey& pk, const OpenRows& in, size_t rows, void* d_q, size_t out_stride, void* d_value, void* stream = nullptr) {
+    return make_error(zk_bn254_plonk_open_batch_dev(pk.handle(), in.fh, in.lin, in.l, in.r, in.o, in.in_stride, rows, in.zeta, in.kzg_gamma, d_q, out_stride, d_value,
+                                                    stream));
 }
 
 // plonk.Verify(proof, vk, publicWitness) on the host: vk = the bytes of VerifyingKey.WriteTo, srs supplies the two G2 points InitKZG attaches.

@@ -63,7 +63,8 @@ __global__ __launch_bounds__(256) void k_hscan_local_rows(HscanRows R, uint32_t 
     tcarry[blk * 256 + threadIdx.x] = threadIdx.x < 255 ? sh[threadIdx.x + 1] : Fr::zero();
     if (threadIdx.x == 0) btot[blk] = val;
 }
-// pass 2 of k_hscan_blocks (plonk.hip; the same scan -- an edit of one belongs in the other), one workgroup per row with the row's own M:
+// pass 2 of k_hscan_blocks (plonk.hip; the same scan, as are scan.hpp's hscan_*_body under plonk.hip's k_hscan_*_dev -- an edit of one belongs in the others), one
+// workgroup per row with the row's own M:
 // btot[row nb + b] <- sum_{b' > b} btot[row nb + b'] M^(b'-b-1); total[row] = f(a)
 __global__ __launch_bounds__(1024) void k_hscan_blocks_rows(HscanRows R, Fr* __restrict__ btot, uint32_t nb, Fr* __restrict__ total) {
     __shared__ Fr sh[1024];

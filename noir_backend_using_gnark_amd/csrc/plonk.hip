@@ -387,7 +387,8 @@ __global__ __launch_bounds__(256) void k_hscan_local_batch(HscanBatch Bt, uint32
     }
     if (threadIdx.x == 0) btot[(size_t)blockIdx.y * nb + blockIdx.x] = val;
 }
-// (kzg.hip's k_hscan_*_rows are these three passes with polynomial, length and point per row: an edit of one belongs in the other)
+// (kzg.hip's k_hscan_*_rows are these three passes with polynomial, length and point per row, and k_hscan_*_dev below -- over scan.hpp's hscan_*_body -- with
+// the row's point in device memory: an edit of one belongs in the others)
 // pass 2: one block; btot[b] <- C_b = sum_{b' > b} btot[b'] * M^(b'-b-1) (M = A^256); *total = S_0 = f(a).
 __global__ __launch_bounds__(1024) void k_hscan_blocks(Fr* __restrict__ btot, uint32_t nb, Fr M, Fr* __restrict__ total) {
     __shared__ Fr sh[1024];
@@ -439,6 +440,169 @@ __global__ __launch_bounds__(256) void k_hscan_apply(const Fr* f, size_t len, ui
         q[i] = S;
         S = fv + a * S;
     }
+}
+
+// The three passes with the row as a grid dimension and everything that belongs to a row in device memory (scan.hpp's bodies; k_hscan_local / _batch / _blocks /
+// _apply above and kzg.hip's k_hscan_*_rows are the same passes with their points in the kernel arguments: an edit of one belongs in the others).  Row v reads
+// polynomial p at f[p] + v * stride[p] and takes its point from the row's prepared points: a, A = a^K, M = A^256 at pts + v * pstride + 3 pt[p], written once per
+// row by k_hscan_points_dev / k_lin_points_rows.
+constexpr int HSCAN_DEV_POLYS = 6;
+struct HscanDev {
+    const Fr* f[HSCAN_DEV_POLYS];
+    size_t stride[HSCAN_DEV_POLYS];  // 0: a polynomial of the key, the same for every row
+    size_t len[HSCAN_DEV_POLYS];     // >= 1
+    uint32_t pt[HSCAN_DEV_POLYS];
+    const Fr* pts;
+    uint32_t pstride, npoly, K, nb;
+    int carry_poly;                  // the polynomial that pass 3 divides: its lane carries are kept (-1: none)
+    Fr* tcarry;                      // [(row nb + block) 256 + lane]
+    Fr* btot;                        // [(row npoly + p) nb + block]
+    Fr* total;                       // f_p(a) of row v -> total[v * tstride + p]
+    size_t tstride;
+    Fr* q;                           // pass 3: (f - f(a)) / (X - a) of polynomial carry_poly, len - 1 coefficients at q + v * qstride (may be that polynomial)
+    size_t qstride;
+};
+// a -> a, a^K, a^(256 K)
+__device__ __forceinline__ void hscan_point(const Fr& a, uint32_t K, Fr* __restrict__ out) {
+    Fr A = Fr::one(), base = a;
+    for (uint32_t k = K; k; k >>= 1) { if (k & 1) A = A * base; base = base.sqr(); }
+    Fr M = A;
+    for (int i = 0; i < 8; i++) M = M.sqr();
+    out[0] = a; out[1] = A; out[2] = M;
+}
+__global__ __launch_bounds__(256) void k_hscan_points_dev(const Fr* __restrict__ points, uint32_t rows, uint32_t K, Fr* __restrict__ pts) {
+    const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+    if (v < rows) hscan_point(ld(points + v), K, pts + 3 * (size_t)v);
+}
+// pass 1: grid (nb, rows, polynomials).  A workgroup wholly above the polynomial's last coefficient contributes zeros.
+__global__ __launch_bounds__(256) void k_hscan_local_dev(HscanDev H) {
+    __shared__ Fr sh[256];
+    const unsigned p = blockIdx.z;
+    const size_t row = blockIdx.y, len = H.len[p];
+    const size_t blk = (row * H.npoly + p) * H.nb + blockIdx.x, lane0 = (row * H.nb + blockIdx.x) * 256;
+    const bool keep = (int)p == H.carry_poly;
+    const size_t first = (size_t)blockIdx.x * 256 * H.K;
+    if (first >= len) {  // uniform over the workgroup
+        if (keep) H.tcarry[lane0 + threadIdx.x] = Fr::zero();
+        if (threadIdx.x == 0) H.btot[blk] = Fr::zero();
+        return;
+    }
+    const Fr* __restrict__ pt = H.pts + row * H.pstride + 3 * H.pt[p];
+    const Fr a = ld(pt), A = ld(pt + 1);
+    const size_t lanes = (len - first + H.K - 1) / H.K;
+    const Fr val = hscan_local_body(sh, H.f[p] + row * H.stride[p], len, H.K, first + (size_t)threadIdx.x * H.K, a, A, lanes < 256 ? (uint32_t)lanes : 256u);
+    if (keep) H.tcarry[lane0 + threadIdx.x] = threadIdx.x < 255 ? sh[threadIdx.x + 1] : Fr::zero();
+    if (threadIdx.x == 0) H.btot[blk] = val;
+}
+// pass 2: grid (polynomials, rows), one workgroup each
+__global__ __launch_bounds__(1024) void k_hscan_blocks_dev(HscanDev H) {
+    __shared__ Fr sh[1024];
+    const unsigned p = blockIdx.x;
+    const size_t row = blockIdx.y;
+    const Fr M = ld(H.pts + row * H.pstride + 3 * H.pt[p] + 2);
+    const Fr tot = hscan_blocks_body(sh, H.btot + (row * H.npoly + p) * H.nb, H.nb, M);
+    if (threadIdx.x == 0) H.total[row * H.tstride + p] = tot;
+}
+// pass 3: grid (nb, rows), polynomial carry_poly
+__global__ __launch_bounds__(256) void k_hscan_apply_dev(HscanDev H) {
+    const unsigned p = (unsigned)H.carry_poly;
+    const size_t row = blockIdx.y, len = H.len[p];
+    const size_t base = ((size_t)blockIdx.x * 256 + threadIdx.x) * H.K;
+    if (base >= len) return;
+    const Fr* pt = H.pts + row * H.pstride + 3 * H.pt[p];
+    const Fr a = ld(pt), A = ld(pt + 1);
+    hscan_apply_body(H.f[p] + row * H.stride[p], H.q + row * H.qstride, len, len - 1, H.K, base, a, A, ld(H.tcarry + (row * H.nb + blockIdx.x) * 256 + threadIdx.x),
+                     ld(H.btot + (row * H.npoly + p) * H.nb + blockIdx.x));
+}
+
+// ------------------------------------------------------------------------------------------------ rounds 4 and 5 with the row as a grid dimension
+// x^(r - 2): Field::inv with the exponent's words as constants (no array to index); 0 -> 0
+__device__ __forceinline__ Fr fr_inv_fermat(const Fr& x) {
+    Fr acc = Fr::one(), base = x;
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+        const uint32_t e = FrParams::MOD[w] - (w == 0 ? 2u : 0u);
+        for (int i = 0; i < 32; i++) {
+            if ((e >> i) & 1) acc = acc * base;
+            base = base.sqr();
+        }
+    }
+    return acc;
+}
+// what a row of round 4 needs of its zeta, once per row: LIN_PT elements -- the points zeta and omega zeta (a, a^K, a^(256 K) each), zeta^(n+2), and
+// lag = (zeta^n - 1) / (zeta - 1) * alpha^2 / n with 1 / 0 = 0
+constexpr uint32_t LIN_PT = 8;
+__global__ __launch_bounds__(256) void k_lin_points_rows(const Fr* __restrict__ zeta, const Fr* __restrict__ alpha, uint32_t rows, uint32_t K, unsigned logn, Fr gen,
+                                                         Fr card_inv, Fr* __restrict__ pts) {
+    const uint32_t v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= rows) return;
+    Fr* o = pts + (size_t)v * LIN_PT;
+    const Fr z = ld(zeta + v), al = ld(alpha + v);
+    hscan_point(z, K, o);
+    hscan_point(z * gen, K, o + 3);
+    Fr zn = z;
+    for (unsigned i = 0; i < logn; i++) zn = zn.sqr();
+    o[6] = zn * z.sqr();
+    o[7] = (zn - Fr::one()) * fr_inv_fermat(z - Fr::one()) * al * al * card_inv;
+}
+// The linearised polynomial (k_linearized's formula; n + 3 coefficients) and the folded quotient h1 + zeta^(n+2) h2 + zeta^(2(n+2)) h3 (n + 2) of row blockIdx.y.
+// The row's scalars are formed here from its evaluations and challenges: the same in every lane, exact products, so alpha c_z + lag and alpha c_s3 stand for
+// k_linearized's (z c_z + s3 c_s3) alpha + z lag.
+struct LinRowsArgs {
+    const Fr *z, *h;                                  // row 0; row v is v * in_stride / v * h_stride further
+    size_t in_stride, h_stride;
+    const Fr *s3, *ql, *qr, *qm, *qo, *cqk;           // the key's, canonical
+    const Fr *alpha, *beta, *gamma, *zeta, *values;   // one (values: eight, of which [2 .. 8) = l, r, o, s1, s2 at zeta and z at omega zeta are read) per row
+    const Fr* pts;                                    // k_lin_points_rows
+    Fr u, uu;
+    Fr *lin, *fh;
+    size_t out_stride;
+    uint32_t n;
+};
+__global__ __launch_bounds__(256) void k_lin_fold_rows(LinRowsArgs A) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n = A.n;
+    if (i >= n + 3) return;
+    const size_t row = blockIdx.y;
+    const Fr* ev = A.values + 8 * row;
+    const Fr lz = ld(ev + 2), rz = ld(ev + 3), oz = ld(ev + 4), s1z = ld(ev + 5), s2z = ld(ev + 6), zu = ld(ev + 7);
+    const Fr alpha = ld(A.alpha + row), beta = ld(A.beta + row), gamma = ld(A.gamma + row), bzeta = beta * ld(A.zeta + row);
+    const Fr c_s3 = (lz + beta * s1z + gamma) * (rz + beta * s2z + gamma) * zu * beta;
+    const Fr c_z = ((lz + bzeta + gamma) * (rz + bzeta * A.u + gamma) * (oz + bzeta * A.uu + gamma)).neg();
+    Fr sc[8] = {c_z * alpha + ld(A.pts + row * LIN_PT + 7), c_s3 * alpha, lz * rz, lz, rz, oz, ld(A.pts + row * LIN_PT + 6), Fr::zero()};
+    sc[7] = sc[6].sqr();
+    // the same for every lane of the workgroup: scalar registers, like the arguments of k_linearized and k_fold they stand for
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+#pragma unroll
+        for (int k = 0; k < 8; k++) sc[j].l[k] = __builtin_amdgcn_readfirstlane(sc[j].l[k]);
+    Fr v = ld(A.z + row * A.in_stride + i) * sc[0];
+    if (i < n) v = v + ld(A.s3 + i) * sc[1] + ld(A.qm + i) * sc[2] + ld(A.ql + i) * sc[3] + ld(A.qr + i) * sc[4] + ld(A.qo + i) * sc[5] + ld(A.cqk + i);
+    A.lin[row * A.out_stride + i] = v;
+    if (i < n + 2) {
+        const Fr* h = A.h + row * A.h_stride + i;
+        A.fh[row * A.out_stride + i] = ld(h) + ld(h + (n + 2)) * sc[6] + ld(h + 2 * (size_t)(n + 2)) * sc[7];
+    }
+}
+// kzg.BatchOpenSinglePoint's fold of row blockIdx.y: fh + g lin + g^2 l + g^3 r + g^4 o + g^5 s1 + g^6 s2 (n + 3 coefficients) by Horner's rule in g = kg[row]
+// (exact: the sum of k_fold's products), to out + row * (n + 3)
+__global__ __launch_bounds__(256) void k_open_fold_rows(const Fr* __restrict__ fh, const Fr* __restrict__ lin, const Fr* __restrict__ l, const Fr* __restrict__ r,
+                                                        const Fr* __restrict__ o, size_t in_stride, const Fr* __restrict__ s1, const Fr* __restrict__ s2,
+                                                        const Fr* __restrict__ kg, uint32_t n, Fr* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n + 3) return;
+    const size_t row = blockIdx.y, at = row * in_stride + i;
+    const Fr g = ld(kg + row);
+    Fr v = i < n ? ld(s2 + i) * g + ld(s1 + i) : Fr::zero();
+    v = v * g;
+    if (i < n + 2) v = v + ld(o + at);
+    v = v * g;
+    if (i < n + 2) v = v + ld(r + at);
+    v = v * g;
+    if (i < n + 2) v = v + ld(l + at);
+    v = v * g + ld(lin + at);
+    v = v * g;
+    if (i < n + 2) v = v + ld(fh + at);
+    out[row * (size_t)(n + 3) + i] = v;
 }
 
 // ------------------------------------------------------------------------------------------------ quotient numerator on the big coset
@@ -1222,6 +1386,123 @@ static int quotient_rows_dev(Slot* s, hipStream_t st, const PlonkPK* P, const Fr
         ZK_HIP(hipMemsetAsync(status + first, 0, (size_t)R * sizeof(int), st));
         ZK_LAUNCH(s, st, "plonk_quotient_tail_rows", k_quot_tail_rows, dim3(grid_of(N4), R), dim3(256), 0, (const Fr*)qk, logN4, keep, h + first * out_stride, out_stride,
                   status + first);
+    }
+    return ZK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ rounds 4 and 5 for R witnesses of one key
+// The polynomial work after the zeta challenge with the row as a grid dimension and every per-row challenge in device memory: nothing comes back to the host
+// between launches, and the launches of a chunk do not depend on its rows.  One row is R = 1 of the same kernels.
+//   poly_open_rows_dev (the ingredient)  k_hscan_points_dev, k_hscan_local_dev, k_hscan_blocks_dev [, k_hscan_apply_dev]                     3 or 4
+//   linearize_rows_dev (round 4)         k_lin_points_rows, local over (l, r, o, s1, s2 at zeta; z at omega zeta), blocks, apply (z),
+//                                        k_lin_fold_rows, local and blocks over (fh, lin)                                                   7
+//   open_rows_dev (round 5)              k_hscan_points_dev, k_open_fold_rows, local, blocks, apply                                         5
+// on scan_bufs' plan for the longest polynomial: K = max(8, ceil(len / 2^18)) coefficients per lane, nb workgroups of 256 lanes per row.  Workspace per row from
+// the slot's arena, OPEN_SCRATCH bytes at a time: the prepared points, nb block totals per polynomial and 256 nb lane carries (+ the n + 3 folded coefficients in
+// round 5); more rows than fit, or than a grid's y holds, go in chunks on the same stream.
+constexpr size_t OPEN_SCRATCH = (size_t)1 << 30;
+struct OpenWs {
+    uint32_t K = 0, nb = 0;
+    size_t chunk = 0;
+    Fr *pts = nullptr, *btot = nullptr, *tcarry = nullptr, *fold = nullptr;
+};
+static size_t open_row_bytes(size_t len, unsigned npoly, size_t pt, size_t fold) {
+    uint32_t K, nb;
+    ratio_plan(len, &K, &nb);
+    return (pt + (size_t)npoly * nb + (size_t)nb * 256 + fold) * sizeof(Fr);
+}
+static int open_ws_take(Slot* s, size_t len, size_t rows, unsigned npoly, size_t pt, size_t fold, OpenWs* W) {
+    ratio_plan(len, &W->K, &W->nb);
+    const size_t row = open_row_bytes(len, npoly, pt, fold);
+    W->chunk = std::min(std::min(rows, RATIO_GRID_ROWS), std::max<size_t>(1, OPEN_SCRATCH / row));
+    ZK_TRY(s->reserve(W->chunk * row + 5 * 256));
+    W->pts = (Fr*)s->alloc(W->chunk * pt * sizeof(Fr));
+    W->btot = (Fr*)s->alloc(W->chunk * npoly * W->nb * sizeof(Fr));
+    W->tcarry = (Fr*)s->alloc(W->chunk * W->nb * 256 * sizeof(Fr));
+    W->fold = fold ? (Fr*)s->alloc(W->chunk * fold * sizeof(Fr)) : nullptr;
+    if (!W->pts || !W->btot || !W->tcarry || (fold && !W->fold)) return set_err(ZK_ERR_HIP, "opening rows: workspace");
+    return ZK_OK;
+}
+// the passes over H's polynomials for R rows; pass 3 where H.q is set
+static int hscan_dev_passes(Slot* s, hipStream_t st, const HscanDev& H, unsigned R) {
+    ZK_LAUNCH(s, st, "plonk_horner_local_rows", k_hscan_local_dev, dim3(H.nb, R, H.npoly), dim3(256), 0, H);
+    ZK_LAUNCH(s, st, "plonk_horner_blocks_rows", k_hscan_blocks_dev, dim3(H.npoly, R), dim3(1024), 0, H);
+    if (H.q) ZK_LAUNCH(s, st, "plonk_divide_apply_rows", k_hscan_apply_dev, dim3(H.nb, R), dim3(256), 0, H);
+    return ZK_OK;
+}
+static HscanDev hscan_dev_of(const OpenWs& W, unsigned npoly, uint32_t pstride) {
+    HscanDev H = {};
+    H.pts = W.pts; H.pstride = pstride; H.npoly = npoly; H.K = W.K; H.nb = W.nb;
+    H.carry_poly = -1; H.tcarry = W.tcarry; H.btot = W.btot;
+    for (int k = 0; k < HSCAN_DEV_POLYS; k++) H.len[k] = 1;
+    return H;
+}
+// values[v] = f_v(points[v]); q_v = (f_v - f_v(points[v])) / (X - points[v]), len - 1 coefficients, where q is given (q == f: in place)
+static int poly_open_rows_dev(Slot* s, hipStream_t st, const Fr* f, size_t in_stride, size_t len, size_t rows, const Fr* points, Fr* q, size_t q_stride, Fr* values) {
+    OpenWs W;
+    ZK_TRY(open_ws_take(s, len, rows, 1, 3, 0, &W));
+    for (size_t first = 0; first < rows; first += W.chunk) {
+        const unsigned R = (unsigned)std::min(W.chunk, rows - first);
+        ZK_LAUNCH(s, st, "plonk_horner_points_rows", k_hscan_points_dev, dim3(grid_of(R)), dim3(256), 0, points + first, (uint32_t)R, W.K, W.pts);
+        HscanDev H = hscan_dev_of(W, 1, 3);
+        H.f[0] = f + first * in_stride; H.stride[0] = in_stride; H.len[0] = len;
+        H.total = values + first; H.tstride = 1;
+        if (q) { H.carry_poly = 0; H.q = q + first * q_stride; H.qstride = q_stride; }
+        ZK_TRY(hscan_dev_passes(s, st, H, R));
+    }
+    return ZK_OK;
+}
+// round 4 (zk_bn254_plonk_linearize_batch_dev in zkmi.h says what goes where)
+static int linearize_rows_dev(Slot* s, hipStream_t st, const PlonkPK* P, const Fr* l, const Fr* r, const Fr* o, const Fr* z, size_t in_stride, const Fr* h,
+                              size_t h_stride, size_t rows, const Fr* d_alpha, const Fr* d_beta, const Fr* d_gamma, const Fr* d_zeta, Fr* values, Fr* zquot, Fr* lin,
+                              Fr* fh, size_t out_stride) {
+    const size_t n = P->n;
+    OpenWs W;
+    ZK_TRY(open_ws_take(s, n + 3, rows, 6, LIN_PT, 0, &W));
+    LinRowsArgs A;
+    A.s3 = P->s3; A.ql = P->ql; A.qr = P->qr; A.qm = P->qm; A.qo = P->qo; A.cqk = P->cqk;
+    A.u = to_dev(P->u); A.uu = to_dev(P->u * P->u);
+    A.in_stride = in_stride; A.h_stride = h_stride; A.out_stride = out_stride; A.pts = W.pts; A.n = (uint32_t)n;
+    for (size_t first = 0; first < rows; first += W.chunk) {
+        const unsigned R = (unsigned)std::min(W.chunk, rows - first);
+        const size_t in = first * in_stride, out = first * out_stride;
+        ZK_LAUNCH(s, st, "plonk_linearize_points_rows", k_lin_points_rows, dim3(grid_of(R)), dim3(256), 0, d_zeta + first, d_alpha + first, (uint32_t)R, W.K, P->logn,
+                  to_dev(P->gen), to_dev(P->card_inv), W.pts);
+        HscanDev H = hscan_dev_of(W, 6, LIN_PT);
+        const Fr* p6[6] = {l + in, r + in, o + in, P->s1, P->s2, z + in};
+        const size_t l6[6] = {n + 2, n + 2, n + 2, n, n, n + 3};
+        for (int k = 0; k < 6; k++) { H.f[k] = p6[k]; H.len[k] = l6[k]; H.stride[k] = (k == 3 || k == 4) ? 0 : in_stride; H.pt[k] = k == 5; }
+        H.total = values + 8 * first + 2; H.tstride = 8;
+        H.carry_poly = 5; H.q = zquot + out; H.qstride = out_stride;
+        ZK_TRY(hscan_dev_passes(s, st, H, R));
+        A.z = z + in; A.h = h + first * h_stride; A.lin = lin + out; A.fh = fh + out;
+        A.alpha = d_alpha + first; A.beta = d_beta + first; A.gamma = d_gamma + first; A.zeta = d_zeta + first; A.values = values + 8 * first;
+        ZK_LAUNCH(s, st, "plonk_linearize_fold_rows", k_lin_fold_rows, dim3(grid_of(n + 3), R), dim3(256), 0, A);
+        HscanDev G = hscan_dev_of(W, 2, LIN_PT);
+        G.f[0] = fh + out; G.len[0] = n + 2; G.stride[0] = out_stride;
+        G.f[1] = lin + out; G.len[1] = n + 3; G.stride[1] = out_stride;
+        G.total = values + 8 * first; G.tstride = 8;
+        ZK_TRY(hscan_dev_passes(s, st, G, R));
+    }
+    return ZK_OK;
+}
+// round 5's polynomial (zk_bn254_plonk_open_batch_dev)
+static int open_rows_dev(Slot* s, hipStream_t st, const PlonkPK* P, const Fr* fh, const Fr* lin, const Fr* l, const Fr* r, const Fr* o, size_t in_stride, size_t rows,
+                         const Fr* d_zeta, const Fr* d_kg, Fr* q, size_t out_stride, Fr* value) {
+    const size_t n = P->n;
+    OpenWs W;
+    ZK_TRY(open_ws_take(s, n + 3, rows, 1, 3, n + 3, &W));
+    for (size_t first = 0; first < rows; first += W.chunk) {
+        const unsigned R = (unsigned)std::min(W.chunk, rows - first);
+        const size_t in = first * in_stride;
+        ZK_LAUNCH(s, st, "plonk_horner_points_rows", k_hscan_points_dev, dim3(grid_of(R)), dim3(256), 0, d_zeta + first, (uint32_t)R, W.K, W.pts);
+        ZK_LAUNCH(s, st, "plonk_open_fold_rows", k_open_fold_rows, dim3(grid_of(n + 3), R), dim3(256), 0, fh + in, lin + in, l + in, r + in, o + in, in_stride,
+                  (const Fr*)P->s1, (const Fr*)P->s2, d_kg + first, (uint32_t)n, W.fold);
+        HscanDev H = hscan_dev_of(W, 1, 3);
+        H.f[0] = W.fold; H.stride[0] = n + 3; H.len[0] = n + 3;
+        H.total = value + first; H.tstride = 1;
+        H.carry_poly = 0; H.q = q + first * out_stride; H.qstride = out_stride;
+        ZK_TRY(hscan_dev_passes(s, st, H, R));
     }
     return ZK_OK;
 }
@@ -2230,6 +2511,104 @@ int zk_bn254_fr_batch_invert_dev(void* d_a, size_t n, void* stream) {
         ZK_LAUNCH(g.s, st, "plonk_batch_inverse", k_batch_inverse, dim3(grid_of(lanes)), dim3(256), 0, (Fr*)d_a + first, cnt, scr);
     }
     return slot_sync(g.s, st);  // the scratch lives in the slot's arena
+}
+
+// ---- rounds 4 and 5 for many witnesses (poly_open_rows_dev, linearize_rows_dev, open_rows_dev above).  As for round 3: argument errors before a device is looked
+// for, the key's `live` lock shared and not its per-proof mutex, the workspace from the slot's arena.
+int zk_bn254_fr_poly_open_rows_dev(const void* d_f, size_t in_stride, size_t len, size_t rows, const void* d_points, void* d_q, size_t q_stride, void* d_values,
+                                   void* stream) {
+    if (!d_f || !d_points || !d_values) return set_err(ZK_ERR_ARG, "null pointer");
+    if (rows == 0) return ZK_OK;
+    if (len < 1) return set_err(ZK_ERR_ARG, "a polynomial has at least one coefficient");
+    if (in_stride < len) return set_err(ZK_ERR_ARG, "in_stride = %zu is below the %zu coefficients of a row", in_stride, len);
+    if (d_q && q_stride < len - 1) return set_err(ZK_ERR_ARG, "q_stride = %zu is below the %zu coefficients of a quotient", q_stride, len - 1);
+    {
+        const size_t fb = rows_span(rows, in_stride, len), qb = d_q && len > 1 ? rows_span(rows, q_stride, len - 1) : 0, cb = rows * sizeof(Fr);
+        const bool in_place = d_q == d_f && q_stride == in_stride;
+        if (!in_place && spans_overlap(d_q, qb, d_f, fb)) return set_err(ZK_ERR_ARG, "d_q overlaps d_f and is not d_f with its stride");
+        if (spans_overlap(d_q, qb, d_points, cb) || spans_overlap(d_q, qb, d_values, cb)) return set_err(ZK_ERR_ARG, "d_q overlaps d_points or d_values");
+        if (spans_overlap(d_values, cb, d_f, fb) || spans_overlap(d_values, cb, d_points, cb)) return set_err(ZK_ERR_ARG, "d_values overlaps an input");
+    }
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    ZK_TRY(poly_open_rows_dev(g.s, st, (const Fr*)d_f, in_stride, len, rows, (const Fr*)d_points, (Fr*)d_q, q_stride, (Fr*)d_values));
+    return slot_sync(g.s, st);  // the workspace lives in the slot's arena
+}
+
+// a key that is not being freed, kept alive by `alive` (zk_bn254_plonk_quotient_batch_dev says why the shared lock is granted at once)
+static int live_key(uint64_t handle, PlonkPK** P, std::shared_ptr<std::shared_mutex>* live, std::shared_lock<std::shared_mutex>* alive) {
+    std::lock_guard<std::mutex> lk(g_ppk_mu);
+    auto it = g_ppks.find(handle);
+    if (it == g_ppks.end()) return set_err(ZK_ERR_HANDLE, "unknown PLONK proving-key handle %llu", (unsigned long long)handle);
+    *P = it->second;
+    *live = (*P)->live;
+    *alive = std::shared_lock<std::shared_mutex>(**live);
+    return ZK_OK;
+}
+
+int zk_bn254_plonk_linearize_batch_dev(uint64_t handle, const void* d_l, const void* d_r, const void* d_o, const void* d_z, size_t in_stride, const void* d_h,
+                                       size_t h_stride, size_t rows, const void* d_alpha, const void* d_beta, const void* d_gamma, const void* d_zeta, void* d_values,
+                                       void* d_zquot, void* d_lin, void* d_fh, size_t out_stride, void* stream) {
+    if (!d_l || !d_r || !d_o || !d_z || !d_h || !d_alpha || !d_beta || !d_gamma || !d_zeta || !d_values || !d_zquot || !d_lin || !d_fh)
+        return set_err(ZK_ERR_ARG, "null pointer");
+    if (rows == 0) return ZK_OK;
+    PlonkPK* P;
+    std::shared_ptr<std::shared_mutex> live;
+    std::shared_lock<std::shared_mutex> alive;
+    ZK_TRY(live_key(handle, &P, &live, &alive));
+    const size_t n = P->n;
+    if (in_stride < n + 3) return set_err(ZK_ERR_ARG, "in_stride = %zu is below n + 3 = %zu", in_stride, n + 3);
+    if (h_stride < 3 * (n + 2)) return set_err(ZK_ERR_ARG, "h_stride = %zu is below 3 (n + 2) = %zu", h_stride, 3 * (n + 2));
+    if (out_stride < n + 3) return set_err(ZK_ERR_ARG, "out_stride = %zu is below n + 3 = %zu", out_stride, n + 3);
+    {
+        const size_t cb = rows * sizeof(Fr), w2 = rows_span(rows, in_stride, n + 2);
+        const void* in[9] = {d_l, d_r, d_o, d_z, d_h, d_alpha, d_beta, d_gamma, d_zeta};
+        const size_t ib[9] = {w2, w2, w2, rows_span(rows, in_stride, n + 3), rows_span(rows, h_stride, 3 * (n + 2)), cb, cb, cb, cb};
+        const void* out[4] = {d_values, d_zquot, d_lin, d_fh};
+        const size_t ob[4] = {8 * cb, rows_span(rows, out_stride, n + 2), rows_span(rows, out_stride, n + 3), rows_span(rows, out_stride, n + 2)};
+        for (int a = 0; a < 4; a++) {
+            for (int k = 0; k < 9; k++)
+                if (spans_overlap(out[a], ob[a], in[k], ib[k])) return set_err(ZK_ERR_ARG, "an output overlaps an input");
+            for (int b = a + 1; b < 4; b++)
+                if (spans_overlap(out[a], ob[a], out[b], ob[b])) return set_err(ZK_ERR_ARG, "two outputs overlap");
+        }
+    }
+    ZK_ON_ENTRY_OF(handle);
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    ZK_TRY(linearize_rows_dev(g.s, st, P, (const Fr*)d_l, (const Fr*)d_r, (const Fr*)d_o, (const Fr*)d_z, in_stride, (const Fr*)d_h, h_stride, rows, (const Fr*)d_alpha,
+                              (const Fr*)d_beta, (const Fr*)d_gamma, (const Fr*)d_zeta, (Fr*)d_values, (Fr*)d_zquot, (Fr*)d_lin, (Fr*)d_fh, out_stride));
+    return slot_sync(g.s, st);  // the workspace lives in the slot's arena
+}
+
+int zk_bn254_plonk_open_batch_dev(uint64_t handle, const void* d_fh, const void* d_lin, const void* d_l, const void* d_r, const void* d_o, size_t in_stride,
+                                  size_t rows, const void* d_zeta, const void* d_kzg_gamma, void* d_q, size_t out_stride, void* d_value, void* stream) {
+    if (!d_fh || !d_lin || !d_l || !d_r || !d_o || !d_zeta || !d_kzg_gamma || !d_q || !d_value) return set_err(ZK_ERR_ARG, "null pointer");
+    if (rows == 0) return ZK_OK;
+    PlonkPK* P;
+    std::shared_ptr<std::shared_mutex> live;
+    std::shared_lock<std::shared_mutex> alive;
+    ZK_TRY(live_key(handle, &P, &live, &alive));
+    const size_t n = P->n;
+    if (in_stride < n + 3) return set_err(ZK_ERR_ARG, "in_stride = %zu is below n + 3 = %zu", in_stride, n + 3);
+    if (out_stride < n + 2) return set_err(ZK_ERR_ARG, "out_stride = %zu is below n + 2 = %zu", out_stride, n + 2);
+    {
+        const size_t cb = rows * sizeof(Fr), w2 = rows_span(rows, in_stride, n + 2), qb = rows_span(rows, out_stride, n + 2);
+        const void* in[7] = {d_fh, d_lin, d_l, d_r, d_o, d_zeta, d_kzg_gamma};
+        const size_t ib[7] = {w2, rows_span(rows, in_stride, n + 3), w2, w2, w2, cb, cb};
+        for (int k = 0; k < 7; k++)
+            if (spans_overlap(d_q, qb, in[k], ib[k]) || spans_overlap(d_value, cb, in[k], ib[k])) return set_err(ZK_ERR_ARG, "d_q or d_value overlaps an input");
+        if (spans_overlap(d_q, qb, d_value, cb)) return set_err(ZK_ERR_ARG, "d_q overlaps d_value");
+    }
+    ZK_ON_ENTRY_OF(handle);
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    ZK_TRY(open_rows_dev(g.s, st, P, (const Fr*)d_fh, (const Fr*)d_lin, (const Fr*)d_l, (const Fr*)d_r, (const Fr*)d_o, in_stride, rows, (const Fr*)d_zeta,
+                         (const Fr*)d_kzg_gamma, (Fr*)d_q, out_stride, (Fr*)d_value));
+    return slot_sync(g.s, st);  // the workspace lives in the slot's arena
 }
 
 }  // extern "C"

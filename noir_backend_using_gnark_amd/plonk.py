@@ -92,6 +92,27 @@ class ProvingKey:
         return quotient_batch(self, l, r, o, z, public, alpha, beta, gamma, rows=rows, in_stride=in_stride, pub_stride=pub_stride, out_stride=out_stride, out=out,
                               status=status)
 
+    def linearize_batch(self, l, r, o, z, h, alpha, beta, gamma, zeta, *, rows: int | None = None, in_stride: int | None = None, h_stride: int | None = None,
+                        out_stride: int | None = None, out=None):
+        """Round 4 of `rows` proofs against this key (zk_bn254_plonk_linearize_batch_dev; include/zkmi.h says the rest): from the rows of round 3 -- the blinded
+        canonical l, r, o (n + 2 coefficients), z (n + 3), the quotient h (3 (n + 2)) -- and alpha, beta, gamma, zeta of each row to the proof's eight values
+        (foldedH, lin, l, r, o, s1, s2 at zeta, z at omega zeta), the quotient of z at omega zeta (n + 2), the linearised polynomial (n + 3) and the folded
+        quotient (n + 2).  Two forms, every shape / dtype / stride / count / overlap error raised before the library is called:
+          host    l, r, o: (rows, n + 2, 4) uint64 arrays, z: (rows, n + 3, 4), h: (rows, 3 (n + 2), 4), alpha, beta, gamma, zeta: (rows, 4)
+                  -> (values (rows, 8, 4), zquot (rows, n + 2, 4), lin (rows, n + 3, 4), fh (rows, n + 2, 4)), new arrays
+          device  device buffers / pointers; rows is required; row v of l, r, o, z at element v * in_stride (default n + 3), of h at v * h_stride (default
+                  3 (n + 2)); out: the four buffers (values, zquot, lin, fh), values 8 elements per row and the others v * out_stride apart (default n + 3),
+                  overlapping nothing (made here when None) -> out"""
+        return linearize_batch(self, l, r, o, z, h, alpha, beta, gamma, zeta, rows=rows, in_stride=in_stride, h_stride=h_stride, out_stride=out_stride, out=out)
+
+    def open_batch(self, fh, lin, l, r, o, zeta, kzg_gamma, *, rows: int | None = None, in_stride: int | None = None, out_stride: int | None = None, out=None):
+        """Round 5's polynomial of `rows` proofs against this key (zk_bn254_plonk_open_batch_dev): kzg.BatchOpenSinglePoint's fold of (fh, lin, l, r, o, s1, s2)
+        under the challenge kzg_gamma of each row, divided by X - zeta.  Two forms, errors raised before the library is called:
+          host    fh, l, r, o: (rows, n + 2, 4) uint64 arrays, lin: (rows, n + 3, 4), zeta, kzg_gamma: (rows, 4) -> (q (rows, n + 2, 4), value (rows, 4))
+          device  device buffers / pointers; rows is required; row v of the five polynomials at element v * in_stride (default n + 3); out: the two buffers
+                  (q, value), row v of q at v * out_stride (default n + 2), overlapping nothing (made here when None) -> out"""
+        return open_batch(self, fh, lin, l, r, o, zeta, kzg_gamma, rows=rows, in_stride=in_stride, out_stride=out_stride, out=out)
+
     def free(self):
         if self.handle.value:
             check(lib().zk_bn254_plonk_pk_free(self.handle))
@@ -440,3 +461,213 @@ def quotient_batch(pk: ProvingKey, l, r, o, z, public, alpha, beta, gamma, *, ro
     finally:
         for b in bufs:
             b.free()
+
+
+# ---- rounds 4 and 5 for many witnesses: the openings with the row as a grid dimension (zk_bn254_fr_poly_open_rows_dev, zk_bn254_plonk_linearize_batch_dev,
+# zk_bn254_plonk_open_batch_dev)
+def _dev_spans(rows, reads, writes, same=()):
+    """the checks of a call on device rows, before the library: reads / writes = (name, buffer, stride, width) in elements (row v at v * stride, width elements).
+    Every buffer is a device buffer or pointer and holds its rows; a write overlaps no read and no other write, but for the pairs of names in `same`."""
+    span = lambda stride, width: ((rows - 1) * stride + width) * 32 if rows and width else 0
+    for name, b, stride, width in list(reads) + list(writes):
+        if not isinstance(b, _DEV):
+            raise TypeError("%s must be a device buffer or a device pointer" % name)
+        if stride < width:
+            raise ValueError("%s: a stride of %d is below the %d elements of a row" % (name, stride, width))
+        if isinstance(b, _lib.DeviceBuffer) and span(stride, width) > b.nbytes:
+            raise ValueError("%s: %d bytes do not fit the device buffer (%d bytes)" % (name, span(stride, width), b.nbytes))
+    for k, (name, b, stride, width) in enumerate(writes):
+        lo, hi = _ptr(b), _ptr(b) + span(stride, width)
+        for other, c, s2, w2 in list(reads) + list(writes[k + 1:]):
+            if (name, other) not in same and lo < hi and span(s2, w2) and _ptr(c) < hi and lo < _ptr(c) + span(s2, w2):
+                raise ValueError("%s overlaps %s" % (name, other))
+
+
+def _rows_count(rows):
+    if rows is None:
+        raise ValueError("rows is required with device-resident data")
+    if int(rows) < 0:
+        raise ValueError("rows must not be negative")
+    return int(rows)
+
+
+def _host_strides(given):
+    for name, v, want in given:
+        if v is not None and int(v) != want:
+            raise ValueError("the rows of a host array are contiguous: %s must be %d" % (name, want))
+
+
+def _padded(a, width):
+    if a.shape[1] == width:
+        return a
+    w = np.zeros((a.shape[0], width, 4), dtype=np.uint64)
+    w[:, :a.shape[1]] = a
+    return w
+
+
+def _run(call, bufs, made, result):
+    """call() into the library; the buffers of `bufs` are freed afterwards, those of `made` only if it fails"""
+    try:
+        check(call())
+        return result()
+    except Exception:
+        for b in made:
+            b.free()
+        raise
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def poly_open_rows(f, points, *, length: int | None = None, rows: int | None = None, in_stride: int | None = None, q_stride: int | None = None, divide: bool = True,
+                   out=None, values=None):
+    """Rows of polynomials, each opened at its own point (zk_bn254_fr_poly_open_rows_dev): values[v] = f_v(points[v]) and, with divide, the length - 1 coefficients
+    of (f_v - f_v(a_v)) / (X - a_v) (kzg.dividePolyByXminusA).  Every shape / dtype / stride / count / overlap error is raised before the library is called.
+      host    f: (rows, length, 4) uint64, points: (rows, 4) -> (values (rows, 4), q (rows, length - 1, 4) or None without divide)
+      device  device buffers / pointers; rows and length are required; row v of f at element v * in_stride (default length); with divide, q goes to `out` at
+              v * q_stride: a buffer that overlaps nothing else (default stride length - 1; made here when None), or f itself with q_stride = in_stride (in
+              place: element length - 1 of each row stays); `values` (rows elements) is made here when None -> (values, out or None)"""
+    if isinstance(f, _DEV):
+        rows = _rows_count(rows)
+        if length is None or int(length) < 1:
+            raise ValueError("length (>= 1 coefficients per row) is required with device-resident data")
+        length = int(length)
+        in_stride = int(length if in_stride is None else in_stride)
+        in_place = divide and out is not None and isinstance(out, _DEV) and _ptr(out) == _ptr(f)
+        q_stride = int((in_stride if in_place else length - 1) if q_stride is None else q_stride)
+        if not divide and out is not None:
+            raise ValueError("out takes the quotients: there are none without divide")
+        if in_place and q_stride != in_stride:
+            raise ValueError("in place the quotient's stride is in_stride = %d, not %d" % (in_stride, q_stride))
+        reads = [("f", f, in_stride, length), ("points", points, 1, 1)]
+        writes = ([("out", out, q_stride, length - 1)] if out is not None else []) + ([("values", values, 1, 1)] if values is not None else [])
+        _dev_spans(rows, reads, writes, same={("out", "f")} if in_place else ())
+        made = []
+        if divide and out is None:
+            out = _lib.DeviceBuffer(max(((rows - 1) * q_stride + length - 1) * 32 if rows else 0, 32))
+            made.append(out)
+        if values is None:
+            values = _lib.DeviceBuffer(max(rows * 32, 32))
+            made.append(values)
+        if rows == 0:
+            return values, out
+        return _run(lambda: lib().zk_bn254_fr_poly_open_rows_dev(C.c_void_p(_ptr(f)), C.c_size_t(in_stride), C.c_size_t(length), C.c_size_t(rows), C.c_void_p(_ptr(points)),
+                                                                 C.c_void_p(_ptr(out) if divide else 0), C.c_size_t(q_stride), C.c_void_p(_ptr(values)), C.c_void_p(0)),
+                    [], made, lambda: (values, out))
+    f = _host_rows("f", f)
+    cnt, width = f.shape[0], f.shape[1]
+    if width < 1:
+        raise ValueError("a polynomial has at least one coefficient")
+    if rows is not None and int(rows) != cnt:
+        raise ValueError("rows = %d != %d rows of the array" % (rows, cnt))
+    if length is not None and int(length) != width:
+        raise ValueError("length = %d != the %d coefficients of a row" % (length, width))
+    _host_strides((("in_stride", in_stride, width), ("q_stride", q_stride, width - 1)))
+    if out is not None or values is not None:
+        raise ValueError("out and values belong to the device form: the host form returns new arrays")
+    points = _host_challenges("points", points, cnt)
+    if cnt == 0:
+        return np.zeros((0, 4), np.uint64), (np.zeros((0, width - 1, 4), np.uint64) if divide else None)
+    bufs = [_lib.DeviceBuffer.from_numpy(f), _lib.DeviceBuffer.from_numpy(points), _lib.DeviceBuffer(cnt * 32), _lib.DeviceBuffer(max(cnt * (width - 1) * 32, 32))]
+    df, dp, dv, dq = bufs
+    return _run(lambda: lib().zk_bn254_fr_poly_open_rows_dev(C.c_void_p(df.ptr), C.c_size_t(width), C.c_size_t(width), C.c_size_t(cnt), C.c_void_p(dp.ptr),
+                                                             C.c_void_p(dq.ptr if divide else 0), C.c_size_t(width - 1), C.c_void_p(dv.ptr), C.c_void_p(0)),
+                bufs, [], lambda: (dv.to_numpy(np.uint64, (cnt, 4)), dq.to_numpy(np.uint64, (cnt, width - 1, 4)) if divide else None))
+
+
+def _same_rows(named):
+    cnt = named[0][1].shape[0]
+    if any(a.shape[0] != cnt for _, a in named):
+        raise ValueError("%s have %s rows" % (", ".join(k for k, _ in named), ", ".join(str(a.shape[0]) for _, a in named)))
+    return cnt
+
+
+def linearize_batch(pk: ProvingKey, l, r, o, z, h, alpha, beta, gamma, zeta, *, rows: int | None = None, in_stride: int | None = None, h_stride: int | None = None,
+                    out_stride: int | None = None, out=None):
+    """ProvingKey.linearize_batch"""
+    n = pk.domain_size
+    keep = 3 * (n + 2)
+    if isinstance(l, _DEV):
+        rows = _rows_count(rows)
+        in_stride, h_stride, out_stride = int(n + 3 if in_stride is None else in_stride), int(keep if h_stride is None else h_stride), int(n + 3 if out_stride is None else out_stride)
+        if in_stride < n + 3 or h_stride < keep or out_stride < n + 3:
+            raise ValueError("in_stride = %d / h_stride = %d / out_stride = %d is below n + 3 = %d / 3 (n + 2) = %d / n + 3" % (in_stride, h_stride, out_stride, n + 3, keep))
+        if out is not None and not (isinstance(out, (tuple, list)) and len(out) == 4):
+            raise TypeError("out is the four device buffers (values, zquot, lin, fh)")
+        reads = [("l", l, in_stride, n + 2), ("r", r, in_stride, n + 2), ("o", o, in_stride, n + 2), ("z", z, in_stride, n + 3), ("h", h, h_stride, keep),
+                 ("alpha", alpha, 1, 1), ("beta", beta, 1, 1), ("gamma", gamma, 1, 1), ("zeta", zeta, 1, 1)]
+        shapes = (("values", 8, 8), ("zquot", out_stride, n + 2), ("lin", out_stride, n + 3), ("fh", out_stride, n + 2))
+        _dev_spans(rows, reads, [(k, b, s, w) for (k, s, w), b in zip(shapes, out)] if out is not None else [])
+        made = []
+        if out is None:
+            out = made = [_lib.DeviceBuffer(max(((rows - 1) * s + w) * 32 if rows else 0, 32)) for _, s, w in shapes]
+        out = tuple(out)
+        if rows == 0:
+            return out
+        p = lambda b: C.c_void_p(_ptr(b))
+        return _run(lambda: lib().zk_bn254_plonk_linearize_batch_dev(pk.handle, p(l), p(r), p(o), p(z), C.c_size_t(in_stride), p(h), C.c_size_t(h_stride), C.c_size_t(rows),
+                                                                     p(alpha), p(beta), p(gamma), p(zeta), p(out[0]), p(out[1]), p(out[2]), p(out[3]),
+                                                                     C.c_size_t(out_stride), C.c_void_p(0)), [], made, lambda: out)
+    l, r, o = (_host_rows_of(k, v, (n + 2, n + 3)) for k, v in (("l", l), ("r", r), ("o", o)))
+    z, h = _host_rows_of("z", z, (n + 3,)), _host_rows_of("h", h, (keep,))
+    cnt = _same_rows((("l", l), ("r", r), ("o", o), ("z", z), ("h", h)))
+    if rows is not None and int(rows) != cnt:
+        raise ValueError("rows = %d != %d rows of the arrays" % (rows, cnt))
+    _host_strides((("in_stride", in_stride, n + 3), ("h_stride", h_stride, keep), ("out_stride", out_stride, n + 3)))
+    if out is not None:
+        raise ValueError("out belongs to the device form: the host form returns new arrays")
+    ch = [_host_challenges(k, v, cnt) for k, v in (("alpha", alpha), ("beta", beta), ("gamma", gamma), ("zeta", zeta))]
+    shapes = ((cnt, 8, 4), (cnt, n + 2, 4), (cnt, n + 3, 4), (cnt, n + 2, 4))
+    if cnt == 0:
+        return tuple(np.zeros(s, np.uint64) for s in shapes)
+    bufs = [_lib.DeviceBuffer.from_numpy(v) for v in [_padded(l, n + 3), _padded(r, n + 3), _padded(o, n + 3), z, h] + ch]
+    outs = [_lib.DeviceBuffer(cnt * 8 * 32)] + [_lib.DeviceBuffer(cnt * (n + 3) * 32) for _ in range(3)]
+    bufs += outs
+    p = lambda b: C.c_void_p(b.ptr)
+    return _run(lambda: lib().zk_bn254_plonk_linearize_batch_dev(pk.handle, *(p(b) for b in bufs[:4]), C.c_size_t(n + 3), p(bufs[4]), C.c_size_t(keep), C.c_size_t(cnt),
+                                                                 *(p(b) for b in bufs[5:9]), *(p(b) for b in outs), C.c_size_t(n + 3), C.c_void_p(0)),
+                bufs, [], lambda: (outs[0].to_numpy(np.uint64, shapes[0]),) + tuple(np.ascontiguousarray(b.to_numpy(np.uint64, (cnt, n + 3, 4))[:, :s[1]])
+                                                                                     for b, s in zip(outs[1:], shapes[1:])))
+
+
+def open_batch(pk: ProvingKey, fh, lin, l, r, o, zeta, kzg_gamma, *, rows: int | None = None, in_stride: int | None = None, out_stride: int | None = None, out=None):
+    """ProvingKey.open_batch"""
+    n = pk.domain_size
+    if isinstance(fh, _DEV):
+        rows = _rows_count(rows)
+        in_stride, out_stride = int(n + 3 if in_stride is None else in_stride), int(n + 2 if out_stride is None else out_stride)
+        if in_stride < n + 3 or out_stride < n + 2:
+            raise ValueError("in_stride = %d / out_stride = %d is below n + 3 = %d / n + 2 = %d" % (in_stride, out_stride, n + 3, n + 2))
+        if out is not None and not (isinstance(out, (tuple, list)) and len(out) == 2):
+            raise TypeError("out is the two device buffers (q, value)")
+        reads = [("fh", fh, in_stride, n + 2), ("lin", lin, in_stride, n + 3), ("l", l, in_stride, n + 2), ("r", r, in_stride, n + 2), ("o", o, in_stride, n + 2),
+                 ("zeta", zeta, 1, 1), ("kzg_gamma", kzg_gamma, 1, 1)]
+        shapes = (("q", out_stride, n + 2), ("value", 1, 1))
+        _dev_spans(rows, reads, [(k, b, s, w) for (k, s, w), b in zip(shapes, out)] if out is not None else [])
+        made = []
+        if out is None:
+            out = made = [_lib.DeviceBuffer(max(((rows - 1) * s + w) * 32 if rows else 0, 32)) for _, s, w in shapes]
+        out = tuple(out)
+        if rows == 0:
+            return out
+        p = lambda b: C.c_void_p(_ptr(b))
+        return _run(lambda: lib().zk_bn254_plonk_open_batch_dev(pk.handle, p(fh), p(lin), p(l), p(r), p(o), C.c_size_t(in_stride), C.c_size_t(rows), p(zeta), p(kzg_gamma),
+                                                                p(out[0]), C.c_size_t(out_stride), p(out[1]), C.c_void_p(0)), [], made, lambda: out)
+    fh, l, r, o = (_host_rows_of(k, v, (n + 2, n + 3)) for k, v in (("fh", fh), ("l", l), ("r", r), ("o", o)))
+    lin = _host_rows_of("lin", lin, (n + 3,))
+    cnt = _same_rows((("fh", fh), ("lin", lin), ("l", l), ("r", r), ("o", o)))
+    if rows is not None and int(rows) != cnt:
+        raise ValueError("rows = %d != %d rows of the arrays" % (rows, cnt))
+    _host_strides((("in_stride", in_stride, n + 3), ("out_stride", out_stride, n + 2)))
+    if out is not None:
+        raise ValueError("out belongs to the device form: the host form returns new arrays")
+    ch = [_host_challenges(k, v, cnt) for k, v in (("zeta", zeta), ("kzg_gamma", kzg_gamma))]
+    if cnt == 0:
+        return np.zeros((0, n + 2, 4), np.uint64), np.zeros((0, 4), np.uint64)
+    bufs = [_lib.DeviceBuffer.from_numpy(v) for v in [_padded(fh, n + 3), lin, _padded(l, n + 3), _padded(r, n + 3), _padded(o, n + 3)] + ch]
+    dq, dv = _lib.DeviceBuffer(cnt * (n + 2) * 32), _lib.DeviceBuffer(cnt * 32)
+    bufs += [dq, dv]
+    p = lambda b: C.c_void_p(b.ptr)
+    return _run(lambda: lib().zk_bn254_plonk_open_batch_dev(pk.handle, *(p(b) for b in bufs[:5]), C.c_size_t(n + 3), C.c_size_t(cnt), p(bufs[5]), p(bufs[6]), p(dq),
+                                                            C.c_size_t(n + 2), p(dv), C.c_void_p(0)),
+                bufs, [], lambda: (dq.to_numpy(np.uint64, (cnt, n + 2, 4)), dv.to_numpy(np.uint64, (cnt, 4))))
