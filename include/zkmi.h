@@ -156,6 +156,29 @@ int zk_bn254_bases_lagrange(uint64_t handle, uint32_t log_n, uint64_t *out_handl
  * vectors run one after the other.  out: count affine points of the handle's group; the same points as count calls of zk_bn254_msm_bases. */
 int zk_bn254_msm_bases_batch(uint64_t handle, size_t offset, const zk_fr *const *scalars, uint32_t count, size_t n, const zk_msm_cfg *cfg, void *out);
 int zk_bn254_msm_bases_batch_dev(uint64_t handle, size_t offset, const void *const *d_scalars, uint32_t count, size_t n, const zk_msm_cfg *cfg, void *out);
+/* ROW-BATCHED COMMITMENTS: the digests of `rows` scalar vectors -- row v = the n elements at element v * row_stride of one matrix -- against ONE registered G1
+ * base array: gnark-crypto's kzg.Commit for many polynomials at once.  Row v of the output is, byte for byte, the point zk_bn254_msm_bases_dev returns for
+ * (handle, offset, d_scalars + v * row_stride, n, cfg); the compressed form is G1Affine.Bytes() of that point.
+ *   d_out         rows zk_g1_affine -- gnark's Montgomery image, (0, 0) = infinity --, 16-byte aligned    } device memory in the _dev form, host memory in the
+ *   d_compressed  rows x 32 bytes, 4-byte aligned; may be NULL                                             } host form (whose rows are contiguous: stride n)
+ *   flags         ZK_MSM_ROWS_SPARSE: the scalars are wire-like (0 / 1 / small), the zero digits never enter the sort -- same digests either way;
+ *                 ZK_MSM_ROWS_NO_POINTS: the caller only hashes the digests: d_out may be NULL when d_compressed is given.  Any other bit: ZK_ERR_ARG.
+ * BATCHED PATH: a G1 handle on one device entry with its window table (not window-sharded), no explicit cfg->window_bits, rows >= 1: one recoding, one sort,
+ * one task plan, ONE accumulate launch and one reduction for all the rows of a chunk, finished on the device (no point comes back to the host); one row is a
+ * chunk of one row of the same kernels.  A chunk is the largest row count <= 1024 whose workspace fits 1 GiB and whose sort keys and positions fit their 30 /
+ * 31 bits (zk_bn254_msm_rows_info reports it, for a call without an explicit window width, and whether the batched path serves the handle at all: *batched = 0,
+ * *chunk_rows = 1 otherwise; the workspace bound is the one that cuts: it holds a chunk below 2^26 positions); more rows run
+ * chunk after chunk.  Everything else -- no table, a composite handle, an explicit window width -- runs the rows one after the other through the single
+ * multi-exp and delivers the same bytes.  A G2 handle is ZK_ERR_ARG.
+ * ERRORS are decided before a device is looked for: null pointers, unknown flag bits, row_stride < n with more than one row (ZK_ERR_ARG), offset + n beyond the
+ * registered bases (ZK_ERR_LEN), an unknown handle (ZK_ERR_HANDLE).  The entries synchronise before they return. */
+#define ZK_MSM_ROWS_SPARSE 1u
+#define ZK_MSM_ROWS_NO_POINTS 2u
+int zk_bn254_msm_bases_rows_dev(uint64_t handle, size_t offset, const void *d_scalars, size_t row_stride, size_t n, size_t rows, const zk_msm_cfg *cfg,
+                                uint32_t flags, void *d_out, void *d_compressed);
+int zk_bn254_msm_bases_rows(uint64_t handle, size_t offset, const zk_fr *scalars, size_t n, size_t rows, const zk_msm_cfg *cfg, uint32_t flags, zk_g1_affine *out,
+                            uint8_t *compressed);
+int zk_bn254_msm_rows_info(uint64_t handle, size_t n, uint32_t flags, size_t *chunk_rows, int *batched);
 /* Scalars kept resident and recoded ONCE for every base array they pair with.  groth16.Prove's five MultiExp calls (gnark v0.8.0 groth16 prove.go, reached
  * from gnark_backend_ffi/main.go:131) pair A, B1, K and G2.B with the SAME wire values: through zk_bn254_msm_bases each call uploads the 32 B x n scalars and
  * recodes them (digits, radix sort, task plan).  zk_bn254_scalars_register uploads once (cfg->scalars_mont says which form they are in);
@@ -594,6 +617,14 @@ int zk_bn254_plonk_linearize_batch_dev(uint64_t pk_handle, const void *d_l, cons
                                        void *d_zquot, void *d_lin, void *d_fh, size_t out_stride, void *stream);
 int zk_bn254_plonk_open_batch_dev(uint64_t pk_handle, const void *d_fh, const void *d_lin, const void *d_l, const void *d_r, const void *d_o, size_t in_stride,
                                   size_t rows, const void *d_zeta, const void *d_kzg_gamma, void *d_q, size_t out_stride, void *d_value, void *stream);
+/* The digests every round ends in, for the rows of the entries above: row v = the `len` Montgomery images at element v * row_stride of d_rows, committed through
+ * zk_bn254_msm_bases_rows_dev (its contract, chunks and outputs: d_out rows zk_g1_affine, d_compressed rows x 32 bytes, either -- not both -- may be NULL).
+ *   from_values = 0   coefficients against the key's SRS, len <= its size (l, r, o, Z, the thirds of h, the opening quotients)
+ *   from_values = 1   len = n + 2: the n wire VALUES of a row followed by its two blinders b0, b1, against the key's Lagrange form (zk_bn254_plonk_pk_lagrange_srs;
+ *                     ZK_ERR_ARG if the key has none) -- the digest of the blinded l / r / o without their inverse transforms, the zero digits dropped
+ * It holds the key as the entries above do (shared: calls overlap each other and a proof in flight) and synchronises before it returns. */
+int zk_bn254_plonk_commit_batch_dev(uint64_t pk_handle, const void *d_rows, size_t row_stride, size_t len, size_t rows, int from_values, void *d_out,
+                                    void *d_compressed);
 
 /* ---- the callers either side of the PLONK path: the reference's exported entry points, restated over the device path -----------------------
  * PlonkPreprocess (gnark_backend_ffi/main.go:58-78) and PlonkProveWithPK (main.go:24-37) take the ACIR as JSON (acir/acir.go:17-75), the witness

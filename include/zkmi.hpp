@@ -65,6 +65,21 @@ struct G1Affine : zk_g1_affine {
     }
 };
 
+// MultiExp for the rows of one matrix against bases[offset : offset + n] of a registered G1 base array (zk_bn254_msm_bases_rows, whose comment in zkmi.h says
+// the rest): scalars holds rows * n elements, row after row; digests[v] is the point of row v, compressed (optional) its 32-byte G1Affine.Bytes() encoding.
+// sparse: the scalars are wire-like (0 / 1 / small) -- the same digests from fewer sorted digits.
+inline Error G1MultiExpRows(uint64_t bases, size_t offset, const fr::Vector& scalars, size_t n, std::vector<G1Affine>* digests,
+                            const ecc::MultiExpConfig& config = ecc::MultiExpConfig(), bool sparse = false, std::vector<uint8_t>* compressed = nullptr) {
+    if (n == 0 || scalars.size() % n) return Error{ZK_ERR_LEN, "scalars must hold whole rows of n elements"};
+    const size_t rows = scalars.size() / n;
+    zk_msm_cfg c = {config.NbTasks, config.ScalarsMont ? 1 : 0, 0, 0};
+    digests->resize(rows);
+    if (compressed) compressed->resize(rows * 32);
+    static_assert(sizeof(G1Affine) == sizeof(zk_g1_affine), "digests are written back to back");
+    return make_error(zk_bn254_msm_bases_rows(bases, offset, scalars.data(), n, rows, &c, sparse ? ZK_MSM_ROWS_SPARSE : 0u, digests->data(),
+                                              compressed ? compressed->data() : nullptr));
+}
+
 struct G2Affine : zk_g2_affine {
     Error MultiExp(const std::vector<G2Affine>& points, const fr::Vector& scalars, const ecc::MultiExpConfig& config = ecc::MultiExpConfig()) {
         zk_msm_cfg c = {config.NbTasks, config.ScalarsMont ? 1 : 0, 0, 0};
@@ -304,6 +319,14 @@ struct BatchOpeningProof {
 };
 typedef zk_g1_affine Digest;
 
+// kzg.Commit for many polynomials of one length at once: polys holds rows * n Montgomery coefficients, row after row; digests[v] = Commit(row v)
+inline Error CommitRows(const fr::Vector& polys, size_t n, const SRS& srs, std::vector<bn254::G1Affine>* digests, std::vector<uint8_t>* compressed = nullptr) {
+    if (n > srs.Size()) return Error{ZK_ERR_LEN, "kzg: invalid polynomial size (larger than SRS or == 0)"};
+    ecc::MultiExpConfig c;
+    c.ScalarsMont = true;
+    return bn254::G1MultiExpRows(srs.handle(), 0, polys, n, digests, c, false, compressed);
+}
+
 // kzg.Open(p, point, srs): ClaimedValue = p(point), H = Commit((p - p(point)) / (X - point)), on the device
 inline Error Open(const fr::Vector& p, const fr::Element& point, const SRS& srs, OpeningProof* proof) {
     if (p.empty() || p.size() > srs.Size()) return Error{ZK_ERR_LEN, "kzg: invalid polynomial size (larger than SRS or == 0)"};
@@ -455,6 +478,13 @@ struct OpenRows {
 inline Error OpenBatch(const ProvingKey& pk, const OpenRows& in, size_t rows, void* d_q, size_t out_stride, void* d_value, void* stream = nullptr) {
     return make_error(zk_bn254_plonk_open_batch_dev(pk.handle(), in.fh, in.lin, in.l, in.r, in.o, in.in_stride, rows, in.zeta, in.kzg_gamma, d_q, out_stride, d_value,
                                                     stream));
+}
+
+// The digests those rounds end in (zk_bn254_plonk_commit_batch_dev), on the device: row v = the `len` Montgomery images at d_rows + v * row_stride, against the
+// key's SRS (coefficients) or, with from_values, its Lagrange form (len = n + 2: the wire values, then the blinders b0, b1).  d_out: rows points (64 bytes each),
+// d_compressed: rows x 32 bytes; one of the two may be null.
+inline Error CommitBatch(const ProvingKey& pk, const void* d_rows, size_t row_stride, size_t len, size_t rows, bool from_values, void* d_out, void* d_compressed) {
+    return make_error(zk_bn254_plonk_commit_batch_dev(pk.handle(), d_rows, row_stride, len, rows, from_values ? 1 : 0, d_out, d_compressed));
 }
 
 // plonk.Verify(proof, vk, publicWitness) on the host: vk = the bytes of VerifyingKey.WriteTo, srs supplies the two G2 points InitKZG attaches.

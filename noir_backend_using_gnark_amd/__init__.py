@@ -6,7 +6,7 @@ Layout
   _lib.py      ctypes loader (fails loudly when the HIP library or a GPU is missing -- there is no CPU fallback)
   bn254.py     host-side mirror of the gnark-crypto interface for this path (MultiExp, fft.Domain)
   groth16.py   host-side mirror of gnark's groth16 prove for this path (ProvingKey, prove, compute_h)
-  plonk.py     host-side mirror of gnark's plonk setup / prove and of iop's copy-constraint ratio for many witnesses (ratio_copy_batch), the quotient's (quotient_batch) and the openings' (linearize_batch, open_batch, poly_open_rows)
+  plonk.py     host-side mirror of gnark's plonk setup / prove and of iop's copy-constraint ratio for many witnesses (ratio_copy_batch), the quotient's (quotient_batch), the openings' (linearize_batch, open_batch, poly_open_rows) and the digests of their rows (commit_rows)
   parallel.py  one-process-per-GPU sharding of MSMs / proofs with torch.distributed (RCCL)
 """
 from . import _lib  # noqa: F401

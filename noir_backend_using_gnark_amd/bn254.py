@@ -152,6 +152,108 @@ def msm_prep_inspect(vectors, n: int | None = None, window_bits: int = 0, scalar
     return out
 
 
+MSM_ROWS_SPARSE, MSM_ROWS_NO_POINTS = 1, 2
+_DEV = (int, _lib.DeviceBuffer)
+
+
+def _dptr(a) -> int:
+    return a if isinstance(a, int) else a.ptr
+
+
+def _check_len(rc: int) -> None:
+    if rc in (_lib.ZK_ERR_LEN, _lib.ZK_ERR_NB_TASKS):
+        raise ValueError((lib().zk_last_error() or b"").decode())
+    check(rc)
+
+
+def rows_digests(dev_call, host_call, scalars, n, rows, row_stride, out, compressed, points):
+    """The argument rules of a row-batched commitment (ResidentBases.multi_exp_rows, plonk.commit_rows), checked before the library is called, and the call.
+      dev_call(ptr, row_stride, n, rows, out_ptr, compressed_ptr) -> rc on device rows; host_call(array, n, rows, points or None, digests or None) -> rc on a
+      host matrix (None: the matrix goes to the device and dev_call runs).
+      host    scalars: C-contiguous (rows, n, 4) uint64; n / rows / row_stride, when given, must agree with it; out belongs to the device form
+              -> points (rows, 8) uint64, or (points, digests (rows, 32) uint8) with compressed=True, or the digests alone with points=False
+      device  scalars: device buffer / pointer with n and rows, row v at element v * row_stride (default n); out: where the points go (rows x 64 bytes; made
+              here when None); compressed: False, True (a buffer is made here) or the buffer for rows x 32 bytes; nothing written overlaps anything else
+              -> out, or (out, compressed), or compressed alone with points=False"""
+    if not isinstance(compressed, bool) and not isinstance(compressed, _DEV):
+        raise TypeError("compressed must be False, True or a device buffer / pointer")
+    if not points and compressed is False:
+        raise ValueError("points=False leaves nothing to return: ask for the compressed digests")
+    if not points and out is not None:
+        raise ValueError("out takes the points: there are none with points=False")
+    if isinstance(scalars, _DEV):
+        if n is None or rows is None:
+            raise ValueError("n and rows are required with device-resident scalars")
+        n, rows = int(n), int(rows)
+        if n < 0 or rows < 0:
+            raise ValueError("n and rows must not be negative")
+        row_stride = int(n if row_stride is None else row_stride)
+        if row_stride < n and rows > 1:
+            raise ValueError("row_stride = %d is below the n = %d scalars of a row" % (row_stride, n))
+        span = ((rows - 1) * row_stride + n) * 32 if rows and n else 0
+        if isinstance(scalars, _lib.DeviceBuffer) and span > scalars.nbytes:
+            raise ValueError("scalars: %d bytes do not fit the device buffer (%d bytes)" % (span, scalars.nbytes))
+        seen = [("scalars", scalars, span)]
+        for name, b, nbytes in (("out", out, rows * 64), ("compressed", compressed, rows * 32)):
+            if b is None or isinstance(b, bool):
+                continue
+            if not isinstance(b, _DEV):
+                raise TypeError("%s must be a device buffer or a device pointer" % name)
+            if isinstance(b, _lib.DeviceBuffer) and nbytes > b.nbytes:
+                raise ValueError("%s: %d bytes do not fit the device buffer (%d bytes)" % (name, nbytes, b.nbytes))
+            for other, c, cb in seen:
+                if nbytes and cb and _dptr(b) < _dptr(c) + cb and _dptr(c) < _dptr(b) + nbytes:
+                    raise ValueError("%s overlaps %s" % (name, other))
+            seen.append((name, b, nbytes))
+        made = []
+        if points and out is None:
+            out = _lib.DeviceBuffer(max(rows * 64, 64))
+            made.append(out)
+        if compressed is True:
+            compressed = _lib.DeviceBuffer(max(rows * 32, 32))
+            made.append(compressed)
+        enc = None if compressed is False else compressed
+        if rows:
+            try:
+                _check_len(dev_call(_dptr(scalars), row_stride, n, rows, _dptr(out) if points else 0, _dptr(enc) if enc is not None else 0))
+            except Exception:
+                for b in made:
+                    b.free()
+                raise
+        return out if enc is None else ((out, enc) if points else enc)
+    if not (isinstance(scalars, np.ndarray) and scalars.dtype == np.uint64 and scalars.flags["C_CONTIGUOUS"]):
+        raise TypeError("scalars must be a C-contiguous uint64 numpy array (or a device buffer)")
+    if scalars.ndim != 3 or scalars.shape[2] != 4:
+        raise ValueError("scalars has shape %s, not (rows, n, 4)" % (scalars.shape,))
+    cnt, width = scalars.shape[0], scalars.shape[1]
+    for name, v, want in (("rows", rows, cnt), ("n", n, width), ("row_stride", row_stride, width)):
+        if v is not None and int(v) != want:
+            raise ValueError("%s = %d != %d of the host array (its rows are contiguous)" % (name, v, want))
+    if out is not None or not isinstance(compressed, bool):
+        raise ValueError("out and a compressed buffer belong to the device form: the host form returns new arrays")
+    pts = np.zeros((cnt, 8), np.uint64) if points else None
+    enc = np.zeros((cnt, 32), np.uint8) if compressed else None
+    if cnt and host_call is not None:
+        _check_len(host_call(scalars, width, cnt, pts, enc))
+    elif cnt:
+        bufs = [_lib.DeviceBuffer.from_numpy(scalars), _lib.DeviceBuffer(cnt * 64), _lib.DeviceBuffer(cnt * 32)]
+        try:
+            _check_len(dev_call(bufs[0].ptr, width, width, cnt, bufs[1].ptr if points else 0, bufs[2].ptr if compressed else 0))
+            pts = bufs[1].to_numpy(np.uint64, (cnt, 8)) if points else None
+            enc = bufs[2].to_numpy(np.uint8, (cnt, 32)) if compressed else None
+        finally:
+            for b in bufs:
+                b.free()
+    return pts if enc is None else ((pts, enc) if points else enc)
+
+
+def msm_rows_info(bases: "ResidentBases", n: int, sparse: bool = False) -> dict:
+    """zk_bn254_msm_rows_info: {"chunk_rows": rows per launch set of multi_exp_rows at n scalars per row, "batched": whether the batched path serves these bases}"""
+    chunk, batched = C.c_size_t(0), C.c_int(0)
+    _check_len(lib().zk_bn254_msm_rows_info(bases.handle, C.c_size_t(n), C.c_uint32(MSM_ROWS_SPARSE if sparse else 0), C.byref(chunk), C.byref(batched)))
+    return {"chunk_rows": int(chunk.value), "batched": bool(batched.value)}
+
+
 class ResidentBases:
     """pk / SRS bases kept in HBM across calls (zk_bn254_bases_register)."""
 
@@ -224,6 +326,26 @@ class ResidentBases:
             raise ValueError((lib().zk_last_error() or b"").decode())
         check(rc)
         return out
+
+    def multi_exp_rows(self, scalars, *, n: int | None = None, rows: int | None = None, row_stride: int | None = None, offset: int = 0, sparse: bool = False,
+                       out=None, compressed=False, points: bool = True, config: MultiExpConfig | None = None):
+        """kzg.Commit for many polynomials at once (zk_bn254_msm_bases_rows[_dev]; include/zkmi.h says the rest): the rows of one matrix against
+        bases[offset : offset + n], one launch set per chunk of rows, points and / or their 32-byte G1Affine.Bytes() encodings.  Row v is multi_exp_dev's point
+        for that row, byte for byte.  sparse: the scalars are wire-like (zero digits dropped before the sort; same result).  rows_digests says what the two
+        forms (host matrix / device rows) take and return; every shape / dtype / stride / overlap error is raised before the library is called."""
+        cfg = (config or MultiExpConfig())._c()
+        flags = C.c_uint32((MSM_ROWS_SPARSE if sparse else 0) | (0 if points else MSM_ROWS_NO_POINTS))
+        if int(offset) < 0:
+            raise ValueError("offset must not be negative")
+
+        def dev(ptr, stride, n_, rows_, o, c):
+            return lib().zk_bn254_msm_bases_rows_dev(self.handle, C.c_size_t(offset), C.c_void_p(ptr), C.c_size_t(stride), C.c_size_t(n_), C.c_size_t(rows_), C.byref(cfg),
+                                                     flags, C.c_void_p(o), C.c_void_p(c))
+
+        def host(a, n_, rows_, o, c):
+            return lib().zk_bn254_msm_bases_rows(self.handle, C.c_size_t(offset), vp(a), C.c_size_t(n_), C.c_size_t(rows_), C.byref(cfg), flags, vp(o), vp(c))
+
+        return rows_digests(dev, host, scalars, n, rows, row_stride, out, compressed, points)
 
     def multi_exp_prepared(self, scalars: "PreparedScalars", skip: int = 0, offset: int = 0, config: MultiExpConfig | None = None) -> np.ndarray:
         """sum_{i >= skip} scalars[i] * bases[offset + i - skip] against scalars that were uploaded and are recoded once (zk_bn254_msm_bases_prepared)."""

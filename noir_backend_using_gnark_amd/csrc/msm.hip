@@ -35,12 +35,14 @@
 #endif
 
 #include <chrono>
+#include "codec_dev.hpp"
 #include "ctx.hpp"
 #include "curve.hpp"
 #include "ff29.hpp"
 #include "host_ff.hpp"
 #include "msm.hpp"
 #include "multidev.hpp"
+#include "proofio.hpp"
 #include "radix.hpp"
 
 namespace zkmi {
@@ -1360,6 +1362,11 @@ static int msm_accumulate_batch(int nb, Slot* const* sl, const hipStream_t* sts,
         // ---- 7. last-level entries -> pinned host memory (final combination and Horner happen in msm_finish)
         jobs[b]->n_final = N;
         jobs[b]->sh_final = sh;
+        if (jobs[b]->keep_final) {  // the caller finishes on the device (msm_g1_sets_affine_dev): the entries stay where the last level left them
+            jobs[b]->d_final_a = lvlA[b][cur];
+            jobs[b]->d_final_s = lvlS[b][cur];
+            continue;
+        }
         const size_t cnt = (size_t)W * N;
         ZK_TRY(s->pinned_reserve(2 * cnt * sizeof(Pt)));
         ZK_HIP(hipMemcpyAsync(s->pinned, lvlA[b][cur], cnt * sizeof(Pt), hipMemcpyDeviceToHost, st));
@@ -1426,6 +1433,79 @@ static int msm_finish(const MsmJob& job, XYZZ<HF>* total_out, XYZZ<HF>* per_set 
         tot.add(val);
     }
     *total_out = tot;
+    return ZK_OK;
+}
+
+// ---- device finish of a G1 job whose bucket sets are separate sums (the rows of msm_prepare_scalars_table_rows): what msm_finish does on the host for the
+// sets of a job, one lane per set, ending in the affine point and its compressed encoding instead of an XYZZ sum on the host.
+//   value = sum_j A_j + 2^sh * sum_j j S_j over the set's N last-level entries (interchange format x * 2^261: acc29_load), the running sum over j = N-1 .. 1
+//   read entry by entry from memory -- no array indexed by j --, then sh doublings; N = 1 (several sets: the reduction ran to the end) is just A_0, N up to 64
+//   is a job of ONE set (msm_accumulate_batch leaves the last level of a single set to its finisher).
+// One inversion of zz * zzz per lane (as k_build_table normalises): x * (t * zzz), y * (t * zz).  N = 0: an empty job, every set is the point at infinity.
+// Latency-bound -- a chain of ~400 dependent Fp products per lane, ~30 point operations more per remaining entry -- which is why it is ONE launch for all the
+// rows of a chunk and not spread over more lanes.
+__device__ __forceinline__ Fp fp_inv_chain(const Fp& z) {  // z^(p - 2); the exponent's words are immediates, no private array
+    Fp acc = Fp::one(), base = z;
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+        uint32_t e = FpParams::MOD[w] - (w == 0 ? 2u : 0u);
+#pragma unroll 1
+        for (int b = 0; b < 32; b++) {
+            if (e & 1u) acc = acc * base;
+            base = base.sqr();
+            e >>= 1;
+        }
+    }
+    return acc;
+}
+__global__ __launch_bounds__(64) void k_msm_sets_affine(const XYZZ<Fp>* __restrict__ A_in, const XYZZ<Fp>* __restrict__ S_in, uint32_t N, uint32_t sh, uint32_t sets,
+                                                       Affine<Fp>* __restrict__ out, uint32_t* __restrict__ compressed) {
+    prio_hi();
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= sets) return;
+    Affine<Fp> a = Affine<Fp>::inf();
+    if (N) {
+        typedef TailPt<Fp> PT;
+        const XYZZ<Fp>* A = A_in + (size_t)w * N;
+        PT val = PT::load(A);
+        if (N > 1) {
+            const XYZZ<Fp>* S = S_in + (size_t)w * N;
+            PT run = PT::inf(), acc = PT::inf();
+#pragma unroll 1
+            for (uint32_t j = N - 1; j >= 1; j--) {
+                run.add(PT::load(S + j));
+                acc.add(run);
+                val.add(PT::load(A + j));
+            }
+#pragma unroll 1
+            for (uint32_t k = 0; k < sh; k++) acc.dbl();
+            val.add(acc);
+        }
+        const XYZZ<Fp> r = acc29_to_xyzz(val.v);  // gnark's image, canonical
+        if (!r.is_inf()) {
+            const Fp t = fp_inv_chain(r.zz * r.zzz);  // 1 / (zz * zzz)
+            a.x = r.x * (t * r.zzz);                  // x / zz
+            a.y = r.y * (t * r.zz);                   // y / zzz
+        }
+    }
+    if (out) gstore(out + w, a);
+    if (compressed) {
+        uint32_t raw[8];
+        g1_compress_one(a, raw);
+#pragma unroll
+        for (int k = 0; k < 8; k++) compressed[(size_t)w * 8 + k] = raw[k];
+    }
+}
+int msm_g1_sets_affine_dev(const MsmJob& job, unsigned sets, void* d_out, void* d_compressed) {
+    if (!sets || (!d_out && !d_compressed)) return ZK_OK;
+    if (!job.s || !job.st) return set_err(ZK_ERR_ARG, "the job was not launched");
+    if (((uintptr_t)d_compressed & 3) || ((uintptr_t)d_out & 15)) return set_err(ZK_ERR_ARG, "d_out must be 16-byte and d_compressed 4-byte aligned");
+    if (!job.empty) {
+        if (!job.keep_final || !job.d_final_a || !job.d_final_s) return set_err(ZK_ERR_ARG, "the job did not keep its last level on the device");
+        if (job.W != sets) return set_err(ZK_ERR_ARG, "the job holds %u bucket sets, not %u", job.W, sets);
+    }
+    ZK_LAUNCH(job.s, job.st, "msm_sets_affine", k_msm_sets_affine, dim3((sets + 63) / 64), dim3(64), 0, (const XYZZ<Fp>*)job.d_final_a, (const XYZZ<Fp>*)job.d_final_s,
+              job.empty ? 0u : job.n_final, job.sh_final, (uint32_t)sets, (Affine<Fp>*)d_out, (uint32_t*)d_compressed);
     return ZK_OK;
 }
 
@@ -2370,6 +2450,173 @@ int zk_bn254_msm_bases_batch(uint64_t handle, size_t offset, const zk_fr* const*
 }
 int zk_bn254_msm_bases_batch_dev(uint64_t handle, size_t offset, const void* const* d_scalars, uint32_t count, size_t n, const zk_msm_cfg* cfg, void* out) {
     return msm_bases_batch(handle, offset, d_scalars, count, n, cfg, out, hipMemcpyDeviceToDevice);
+}
+
+// ---- the rows of ONE matrix against ONE registered base array, finished on the device ------------------------------------------------------------------
+// Every PLONK round ends in digests (l, r, o; Z; h1, h2, h3; the opening quotients), and the row-form rounds of plonk.hip leave the polynomials of R witnesses as
+// the rows of a matrix.  msm_prepare_scalars_table_rows recodes, sorts and plans up to MSM_MAX_SETS rows at once, one accumulate launch fills a bucket set per
+// row, and k_msm_sets_affine turns the last reduction level into the rows' affine points and compressed encodings ON THE DEVICE: a chunk of rows costs the
+// launches of one multi-exp and nothing comes back to the host.  One row is a chunk of one row: the same kernels, no second path.
+static const size_t kRowsWorkspace = (size_t)1 << 30;  // what a chunk's preparation + accumulate may take of the slot's arena
+static bool rows_table_ok(const Bases& b) { return b.d_table && !b.is_g2 && b.tab.row_first == 0 && b.tab.row_step <= 1; }
+// The largest row count <= MSM_MAX_SETS that msm_plan accepts for n scalars per row -- rows * 2^(c-1) < 2^30 (sort keys), n * Wrows * rows < 2^31 (positions) --
+// and whose workspace fits kRowsWorkspace; 0: not even one row does (the caller falls back to the single multi-exp, which reserves what it needs).
+static int rows_chunk(const Bases& b, size_t n, bool sparse, size_t* chunk) {
+    *chunk = 0;
+    const MsmTable& tab = b.tab;
+    size_t r = std::min<size_t>(MSM_MAX_SETS, (((size_t)1 << 30) - 1) >> (tab.c - 1));
+    const size_t per_row = n * tab.rows();
+    if (per_row) r = std::min(r, (((size_t)1 << 31) - 1) / per_row);
+    if (!r) return ZK_OK;
+    auto fits = [&](size_t k, bool* ok) -> int {
+        size_t np = 0, na = 0;
+        ZK_TRY(msm_prep_need_table_rows(n, (unsigned)k, tab, nullptr, &np, &na, nullptr));
+        *ok = np + na + (sparse ? msm_compact_need(n, (unsigned)k) : 0) <= kRowsWorkspace;
+        return ZK_OK;
+    };
+    bool ok = false;
+    ZK_TRY(fits(r, &ok));
+    if (ok) { *chunk = r; return ZK_OK; }
+    ZK_TRY(fits(1, &ok));
+    if (!ok) return ZK_OK;
+    size_t lo = 1, hi = r;  // fits(lo), !fits(hi): the workspace grows with the row count
+    while (hi - lo > 1) {
+        const size_t mid = lo + (hi - lo) / 2;
+        ZK_TRY(fits(mid, &ok));
+        (ok ? lo : hi) = mid;
+    }
+    *chunk = lo;
+    return ZK_OK;
+}
+// everything the three entries decide without a device: the handle, its group and size
+static int rows_args(uint64_t handle, size_t offset, size_t n, uint32_t flags, size_t* n_bases) {
+    if (flags & ~(ZK_MSM_ROWS_SPARSE | ZK_MSM_ROWS_NO_POINTS)) return set_err(ZK_ERR_ARG, "unknown flag bits 0x%x", flags & ~(ZK_MSM_ROWS_SPARSE | ZK_MSM_ROWS_NO_POINTS));
+    int is_g2 = 0;
+    ZK_TRY(bases_info(handle, n_bases, &is_g2));
+    if (is_g2) return set_err(ZK_ERR_ARG, "row-batched commitments are G1 only: the handle holds G2 bases");
+    if (offset > *n_bases || n > *n_bases - offset)
+        return set_err(ZK_ERR_LEN, "len(points) != len(scalars): offset %zu + n %zu exceeds the %zu registered bases", offset, n, *n_bases);
+    return ZK_OK;
+}
+static int rows_geometry(uint64_t handle, size_t n, const zk_msm_cfg* cfg, bool sparse, Bases* b, size_t* chunk) {
+    *chunk = 0;
+    if (md_is_composite(handle) || (cfg && cfg->window_bits)) return ZK_OK;
+    {
+        std::lock_guard<std::mutex> lk(g_bases_mu);
+        auto it = g_bases.find(handle);
+        if (it == g_bases.end()) return set_err(ZK_ERR_HANDLE, "unknown bases handle %llu", (unsigned long long)handle);
+        *b = it->second;
+    }
+    if (!rows_table_ok(*b)) return ZK_OK;
+    return rows_chunk(*b, n, sparse, chunk);
+}
+static int msm_bases_rows(uint64_t handle, size_t offset, const void* scalars, size_t row_stride, size_t n, size_t rows, const zk_msm_cfg* cfg, uint32_t flags,
+                          void* out, void* compressed, bool on_dev) {
+    if (rows) {
+        if (n && !scalars) return set_err(ZK_ERR_ARG, "null pointer");
+        if (!out && !compressed) return set_err(ZK_ERR_ARG, "null pointer: neither points nor compressed digests are asked for");
+        if (!out && !(flags & ZK_MSM_ROWS_NO_POINTS)) return set_err(ZK_ERR_ARG, "null pointer: the points may be left out only with ZK_MSM_ROWS_NO_POINTS");
+    }
+    if (rows > 1 && row_stride < n) return set_err(ZK_ERR_ARG, "row_stride = %zu is below n = %zu", row_stride, n);
+    if (on_dev && ((((uintptr_t)out) & 15) || (((uintptr_t)compressed) & 3))) return set_err(ZK_ERR_ARG, "d_out must be 16-byte and d_compressed 4-byte aligned");
+    size_t n_bases = 0;
+    ZK_TRY(rows_args(handle, offset, n, flags, &n_bases));
+    ZK_TRY(check_cfg(cfg));
+    if (!rows) return ZK_OK;
+    const bool sparse = (flags & ZK_MSM_ROWS_SPARSE) != 0;
+    Bases b;
+    size_t chunk = 0;
+    ZK_TRY(rows_geometry(handle, n, cfg, sparse, &b, &chunk));
+    ZK_ON_ENTRY_OF(handle);
+    if (!chunk) {  // no table / a composite handle / an explicit window width: row after row through the single multi-exp, the same bytes
+        std::vector<Affine<HFp>> pts(rows);
+        std::vector<uint8_t> enc(rows * 32);
+        for (size_t v = 0; v < rows; v++) {
+            ZK_TRY(msm_bases(handle, offset, (const char*)scalars + v * row_stride * 32, n, cfg, &pts[v], on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+            g1_compress(pts[v], &enc[v * 32]);
+        }
+        if (on_dev) {
+            if (out) ZK_HIP(hipMemcpy(out, pts.data(), rows * 64, hipMemcpyHostToDevice));
+            if (compressed) ZK_HIP(hipMemcpy(compressed, enc.data(), rows * 32, hipMemcpyHostToDevice));
+        } else {
+            if (out) memcpy(out, pts.data(), rows * 64);
+            if (compressed) memcpy(compressed, enc.data(), rows * 32);
+        }
+        return ZK_OK;
+    }
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = g.s->stream;
+    const size_t first = std::min(rows, chunk), last = rows > chunk ? rows % chunk : 0;
+    size_t need = 0;
+    for (size_t k : {first, last}) {
+        if (!k) continue;
+        size_t np = 0, na = 0;
+        ZK_TRY(msm_prep_need_table_rows(n, (unsigned)k, b.tab, st, &np, &na, nullptr));
+        need = std::max(need, np + na);
+    }
+    // (the host form keeps a chunk's scalars and outputs in the arena too)
+    ZK_TRY(g.s->reserve(need + (sparse ? msm_compact_need(n, (unsigned)first) : 0) + 65536 + (on_dev ? 0 : first * (n * 32 + 96) + 4096)));
+    int rc = ZK_OK;
+    for (size_t v0 = 0; v0 < rows && rc == ZK_OK; v0 += chunk) {
+        const size_t k = std::min(chunk, rows - v0);
+        g.s->reset();  // a chunk's workspace takes the place of the one before it: the stream keeps that chunk's kernels ahead of this one's
+        const void* d_sc = (const char*)scalars + v0 * row_stride * 32;
+        void *d_o = out ? (char*)out + v0 * 64 : nullptr, *d_c = compressed ? (char*)compressed + v0 * 32 : nullptr;
+        if (!on_dev) {
+            void* up = g.s->alloc(k * n * 32 + 16);
+            d_o = out ? g.s->alloc(k * 64) : nullptr;
+            d_c = compressed ? g.s->alloc(k * 32) : nullptr;
+            if (!up || (out && !d_o) || (compressed && !d_c)) {
+                rc = set_err(ZK_ERR_HIP, "MSM workspace was not reserved up front (rows)");
+                break;
+            }
+            if (n && hipMemcpyAsync(up, d_sc, k * n * 32, hipMemcpyHostToDevice, st) != hipSuccess) {
+                rc = set_err(ZK_ERR_HIP, "upload of the scalars failed");
+                break;
+            }
+            d_sc = up;
+        }
+        MsmPrep prep;
+        MsmJob job;
+        job.keep_final = true;
+        job.turnstile = !on_dev;  // as in msm_bases: host-slice callers are upstream's goroutines
+        rc = msm_prepare_scalars_table_rows(g.s, st, d_sc, on_dev ? row_stride : n, (unsigned)k, n, cfg, b.tab, &prep, sparse);
+        if (rc == ZK_OK) rc = msm_g1_accumulate(g.s, st, prep, (const char*)b.d_table + offset * 64, 0, &job);
+        if (rc == ZK_OK) rc = msm_g1_sets_affine_dev(job, (unsigned)k, d_o, d_c);
+        msm_prep_release(&prep);
+        if (rc == ZK_OK && !on_dev) {
+            if (out && hipMemcpyAsync((char*)out + v0 * 64, d_o, k * 64, hipMemcpyDeviceToHost, st) != hipSuccess) rc = set_err(ZK_ERR_HIP, "copy of the points failed");
+            if (compressed && hipMemcpyAsync((char*)compressed + v0 * 32, d_c, k * 32, hipMemcpyDeviceToHost, st) != hipSuccess)
+                rc = set_err(ZK_ERR_HIP, "copy of the digests failed");
+        }
+    }
+    if (rc != ZK_OK) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    return slot_sync(g.s, st);  // the workspace lives in the slot's arena
+}
+int zk_bn254_msm_bases_rows_dev(uint64_t handle, size_t offset, const void* d_scalars, size_t row_stride, size_t n, size_t rows, const zk_msm_cfg* cfg, uint32_t flags,
+                                void* d_out, void* d_compressed) {
+    return msm_bases_rows(handle, offset, d_scalars, row_stride, n, rows, cfg, flags, d_out, d_compressed, true);
+}
+int zk_bn254_msm_bases_rows(uint64_t handle, size_t offset, const zk_fr* scalars, size_t n, size_t rows, const zk_msm_cfg* cfg, uint32_t flags, zk_g1_affine* out,
+                            uint8_t* compressed) {
+    return msm_bases_rows(handle, offset, scalars, n, n, rows, cfg, flags, out, compressed, false);
+}
+int zk_bn254_msm_rows_info(uint64_t handle, size_t n, uint32_t flags, size_t* chunk_rows, int* batched) {
+    size_t n_bases = 0;
+    if (flags & ~(ZK_MSM_ROWS_SPARSE | ZK_MSM_ROWS_NO_POINTS)) return set_err(ZK_ERR_ARG, "unknown flag bits 0x%x", flags & ~(ZK_MSM_ROWS_SPARSE | ZK_MSM_ROWS_NO_POINTS));
+    int is_g2 = 0;
+    ZK_TRY(bases_info(handle, &n_bases, &is_g2));
+    if (n > n_bases) return set_err(ZK_ERR_LEN, "len(points) != len(scalars): n %zu exceeds the %zu registered bases", n, n_bases);
+    Bases b;
+    size_t chunk = 0;
+    if (!is_g2) ZK_TRY(rows_geometry(handle, n, nullptr, (flags & ZK_MSM_ROWS_SPARSE) != 0, &b, &chunk));
+    if (chunk_rows) *chunk_rows = chunk ? chunk : 1;
+    if (batched) *batched = chunk ? 1 : 0;
+    return ZK_OK;
 }
 
 }  // extern "C"

@@ -77,7 +77,14 @@ struct MsmJob {
     bool turnstile = false;       // an independent caller: the accumulate kernel takes its turn behind those of other callers on this device entry
     bool quad_tail = false;       // G1: reduction tail with four lanes per point (3x shorter serial chain, ~1.4x the ALU work): for the
                                   // tail nothing else can hide -- the last MSM of a proof
+    // keep_final (set by the caller BEFORE launch; off: nothing changes): the last-level entries stay on the device -- W * n_final entries each, set w at
+    // [w * n_final, (w + 1) * n_final), in the slot's arena -- instead of being copied to pinned memory; msm_g1_sets_affine_dev finishes such a job
+    bool keep_final = false;
+    const void *d_final_a = nullptr, *d_final_s = nullptr;
 };
+// Device finish of a G1 job launched with keep_final: one affine point per bucket set (gnark's Montgomery image, (0, 0) = infinity) to d_out[0 .. sets) and / or
+// its 32-byte compressed encoding to d_compressed (4-byte aligned; either may be null), enqueued on the job's stream.  An empty job writes infinities.
+int msm_g1_sets_affine_dev(const MsmJob& job, unsigned sets, void* d_out, void* d_compressed);
 int msm_g1_launch(Slot* s, hipStream_t st, const void* d_pts, const void* d_scalars, size_t n, const zk_msm_cfg* cfg, MsmJob* job);
 int msm_g2_launch(Slot* s, hipStream_t st, const void* d_pts, const void* d_scalars, size_t n, const zk_msm_cfg* cfg, MsmJob* job);
 // Split form for MSMs that share one scalar vector: prepare once, accumulate per base array (bases indexed by scalar

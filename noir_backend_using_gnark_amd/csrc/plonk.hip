@@ -2611,4 +2611,23 @@ int zk_bn254_plonk_open_batch_dev(uint64_t handle, const void* d_fh, const void*
     return slot_sync(g.s, st);  // the workspace lives in the slot's arena
 }
 
+// The digests of the rows the entries above produce: zk_bn254_msm_bases_rows_dev against the key's SRS (coefficients) or its Lagrange form (wire values followed
+// by the two blinders: the layout round 1 of zk_bn254_plonk_prove commits, zero digits dropped).  Reads the key's two bases handles only: the `live` lock
+// shared, neither the per-proof mutex nor w_big / w_small.
+int zk_bn254_plonk_commit_batch_dev(uint64_t handle, const void* d_rows, size_t row_stride, size_t len, size_t rows, int from_values, void* d_out, void* d_compressed) {
+    if (!d_rows || (!d_out && !d_compressed)) return set_err(ZK_ERR_ARG, "null pointer");
+    PlonkPK* P;
+    std::shared_ptr<std::shared_mutex> live;
+    std::shared_lock<std::shared_mutex> alive;
+    ZK_TRY(live_key(handle, &P, &live, &alive));
+    if (from_values) {
+        if (!P->lag_srs) return set_err(ZK_ERR_ARG, "the key has no Lagrange form of its SRS (zk_bn254_plonk_pk_lagrange_srs)");
+        if (len != P->n + 2) return set_err(ZK_ERR_ARG, "len = %zu: a row of values is the n = %zu wire values and two blinders", len, P->n);
+    }
+    if (rows > 1 && row_stride < len) return set_err(ZK_ERR_ARG, "row_stride = %zu is below len = %zu", row_stride, len);
+    if (rows == 0) return ZK_OK;
+    return zk_bn254_msm_bases_rows_dev(from_values ? P->lag_srs : P->srs, 0, d_rows, row_stride, len, rows, &kMont, (from_values ? ZK_MSM_ROWS_SPARSE : 0u) | ZK_MSM_ROWS_NO_POINTS,
+                                       d_out, d_compressed);
+}
+
 }  // extern "C"

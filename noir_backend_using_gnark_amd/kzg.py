@@ -34,6 +34,13 @@ class SRS:
             return self.g1.multi_exp_dev(poly, n, cfg)
         return self.g1.multi_exp(poly, cfg)
 
+    def commit_rows(self, polys, *, n: int | None = None, rows: int | None = None, row_stride: int | None = None, sparse: bool = False, out=None, compressed=False,
+                    points: bool = True):
+        """kzg.Commit of every row of a matrix of Montgomery coefficients in one launch set per chunk of rows (ResidentBases.multi_exp_rows says the rest):
+        a (rows, n, 4) uint64 array, or device rows with n, rows and row_stride.  Row v is commit's digest of that row."""
+        return self.g1.multi_exp_rows(polys, n=n, rows=rows, row_stride=row_stride, sparse=sparse, out=out, compressed=compressed, points=points,
+                                      config=MultiExpConfig(scalars_mont=True))
+
     @staticmethod
     def _rows(polys, lens):
         """host arrays or DeviceBuffers (then lens[k] = their coefficient counts) -> (pointer array, length array, on_device, keep-alive)"""

@@ -113,6 +113,14 @@ class ProvingKey:
                   (q, value), row v of q at v * out_stride (default n + 2), overlapping nothing (made here when None) -> out"""
         return open_batch(self, fh, lin, l, r, o, zeta, kzg_gamma, rows=rows, in_stride=in_stride, out_stride=out_stride, out=out)
 
+    def commit_rows(self, rows_data, *, from_values: bool = False, length: int | None = None, rows: int | None = None, row_stride: int | None = None, out=None,
+                    compressed=False, points: bool = True):
+        """The digests a round ends in, for the rows of the batch entries above (zk_bn254_plonk_commit_batch_dev): every row of a matrix of Montgomery images
+        committed against this key's SRS -- coefficients: l, r, o, Z, the thirds of h, the opening quotients -- or, with from_values, against its Lagrange form
+        (lagrange_srs() first): a row is then the n wire values followed by the two blinders b0, b1.  A (rows, length, 4) uint64 array, or device rows with
+        length, rows and row_stride; bn254.rows_digests says what the two forms take and return."""
+        return commit_rows(self, rows_data, from_values=from_values, length=length, rows=rows, row_stride=row_stride, out=out, compressed=compressed, points=points)
+
     def free(self):
         if self.handle.value:
             check(lib().zk_bn254_plonk_pk_free(self.handle))
@@ -671,3 +679,20 @@ def open_batch(pk: ProvingKey, fh, lin, l, r, o, zeta, kzg_gamma, *, rows: int |
     return _run(lambda: lib().zk_bn254_plonk_open_batch_dev(pk.handle, *(p(b) for b in bufs[:5]), C.c_size_t(n + 3), C.c_size_t(cnt), p(bufs[5]), p(bufs[6]), p(dq),
                                                             C.c_size_t(n + 2), p(dv), C.c_void_p(0)),
                 bufs, [], lambda: (dq.to_numpy(np.uint64, (cnt, n + 2, 4)), dv.to_numpy(np.uint64, (cnt, 4))))
+
+
+# ---- the digests every round ends in, for the rows of the batch entries above (zk_bn254_plonk_commit_batch_dev)
+def commit_rows(pk: ProvingKey, rows_data, *, from_values: bool = False, length: int | None = None, rows: int | None = None, row_stride: int | None = None, out=None,
+                compressed=False, points: bool = True):
+    """ProvingKey.commit_rows"""
+    from .bn254 import rows_digests
+
+    def dev(ptr, stride, n_, rows_, o, c):
+        return lib().zk_bn254_plonk_commit_batch_dev(pk.handle, C.c_void_p(ptr), C.c_size_t(stride), C.c_size_t(n_), C.c_size_t(rows_), C.c_int(int(bool(from_values))),
+                                                     C.c_void_p(o), C.c_void_p(c))
+
+    if from_values:
+        width = length if isinstance(rows_data, _DEV) else (rows_data.shape[1] if isinstance(rows_data, np.ndarray) and rows_data.ndim == 3 else None)
+        if width is not None and int(width) != pk.domain_size + 2:
+            raise ValueError("a row of values is the n = %d wire values and two blinders, not %d elements" % (pk.domain_size, width))
+    return rows_digests(dev, None, rows_data, length, rows, row_stride, out, compressed, points)
