@@ -744,6 +744,55 @@ typedef struct {
 } zk_msm_prep_result;
 int zk_bn254_msm_prep_inspect(const zk_msm_prep_request *req, zk_msm_prep_result *res);
 
+/* The base-side half of an MSM behind that preparation, for inspection / tests: window table, bucket accumulation, the folds of split
+ * buckets, every reduction level and the finishers -- the production calls themselves (msm_build_table_g1 / _g2, the four preparation
+ * wrappers, msm_g1_accumulate / msm_g2_accumulate, msm_g?_finish / msm_g?_finish_sets / msm_g1_sets_affine_dev), on HOST scalars and
+ * HOST points, with a trace attached to the job: after the accumulate launch, after the two fold launches and after every reduce launch
+ * the job's stream is synchronised and the raw device array copied.  No kernel and no launch differs from a prover's.  Nothing stays
+ * behind: the slot is released, the preparation's event destroyed and points and table freed on every path.
+ *   request   prep: as for zk_bn254_msm_prep_inspect.  points: n affine points (zk_g1_affine, or zk_g2_affine with is_g2; gnark's
+ *             Montgomery image, (0, 0) = infinity).  Table mode: the table of prep.c-bit windows is built from them (rows prep.row_first +
+ *             k * prep.row_step, prep.stride entries apart, into a zeroed buffer); l1_m / l2_m are the buckets per lane of the first level
+ *             and the entries per lane of the second thread-serial level (0: the defaults, 8 and none), as a prover's MsmTable carries them.
+ *             quad_tail (G1): the wave levels with four lanes per point.  keep_final (G1, table mode): the last level stays on the device
+ *             and msm_g1_sets_affine_dev finishes it.  skip_below (plain method only; an argument error against a table): points with a
+ *             smaller index are left out of the sums.
+ *   result    prep: everything zk_msm_prep_result holds, from THIS run (the device picks the task length).  m2 (l2_m as planned), tasks
+ *             (real tasks: task_off[nb]), n_final / sh_final (entries per bucket set left to the finisher and their shift), n_levels
+ *             descriptors: kind (1 = k_reduce_l1, 2 = k_reduce_l2, 3 = k_reduce_wave, 4 = k_reduce_wave with four lanes per point),
+ *             entries per set going in (level 1: buckets) and coming out, the shift sh before and after (value of a set = sum_j A_j +
+ *             2^sh * sum_j j * S_j), and m: the entries one lane (1, 2) or one wave (3, 4) folds.  table_entries = rows * stride;
+ *             level_entries = sum over the levels of W * n_out.
+ *             Arrays, where the pointer is not NULL -- all of them AFFINE points (4 words per coordinate: 8 per G1 point, 16 per G2
+ *             point; (0, 0) = infinity), converted on the host: table [table_entries]; partial_acc / partial_fold [max_tasks]: the task
+ *             array after the accumulate launch and after the two fold launches (the slots of padding tasks, which no kernel writes, come
+ *             back as (0, 0); after the fold a split bucket's sum sits in its first task's slot, the others are scratch); level_a /
+ *             level_s [level_entries]: the levels one after the other, set w of a level at [w * n_out, (w + 1) * n_out); without
+ *             keep_final set_values [W] (plain: the windows' values; table: one sum per vector) and, plain method, total [1]; with
+ *             keep_final final_affine [sets] and final_bytes [sets * 32] (the compressed encodings) from the device finish.
+ * With ALL array pointers NULL (prep's too) only the plan, the level descriptors and the sizes are filled in (host work, no device):
+ * call once for the sizes, allocate, call again; the run's own descriptors are compared with those and a difference is an error.
+ * An empty plan touches nothing, except that with keep_final the device finish still runs and writes infinities. */
+#define ZK_MSM_TAIL_MAX_LEVELS 12
+typedef struct {
+    zk_msm_prep_request prep;
+    const void *points;
+    int is_g2, quad_tail, keep_final, reserved;
+    uint32_t l1_m, l2_m, skip_below, reserved2;
+} zk_msm_tail_request;
+typedef struct {
+    uint32_t kind, n_in, n_out, sh_in, sh_out, m;
+} zk_msm_tail_level;
+typedef struct {
+    zk_msm_prep_result prep;
+    uint32_t m2, tasks, n_final, sh_final, n_levels, reserved;
+    zk_msm_tail_level level[ZK_MSM_TAIL_MAX_LEVELS];
+    uint64_t table_entries, level_entries;
+    uint64_t *table, *partial_acc, *partial_fold, *level_a, *level_s, *set_values, *total, *final_affine;
+    uint8_t *final_bytes;
+} zk_msm_tail_result;
+int zk_bn254_msm_tail_inspect(const zk_msm_tail_request *req, zk_msm_tail_result *res);
+
 /* ---- felt-vector wire codec (the data format in front of the hot path) -------------------------------------------
  * The reference hands witness values to the Go side as hex( u32 BE count || count x 32 B BE canonical felts )
  * [REF src/gnark_backend_wrapper/serialize.rs:33-47,71-106; gnark_backend_ffi/internal/backend/helpers.go:24-33

@@ -47,6 +47,27 @@ class MsmPrepResult(C.Structure):
                                                                          ("ctl", C.c_uint32 * 64)] + [(k, C.c_void_p) for k in MSM_PREP_ARRAYS]
 
 
+MSM_TAIL_MAX_LEVELS = 12
+MSM_TAIL_LEVEL = ("kind", "n_in", "n_out", "sh_in", "sh_out", "m")
+MSM_TAIL_KINDS = {1: "l1", 2: "l2", 3: "wave", 4: "wave_quad"}
+MSM_TAIL_ARRAYS = ("table", "partial_acc", "partial_fold", "level_a", "level_s", "set_values", "total", "final_affine", "final_bytes")
+
+
+class MsmTailRequest(C.Structure):
+    _fields_ = [("prep", MsmPrepRequest), ("points", C.c_void_p), ("is_g2", C.c_int), ("quad_tail", C.c_int), ("keep_final", C.c_int), ("reserved", C.c_int),
+                ("l1_m", C.c_uint32), ("l2_m", C.c_uint32), ("skip_below", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
+class MsmTailLevel(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in MSM_TAIL_LEVEL]
+
+
+class MsmTailResult(C.Structure):
+    _fields_ = [("prep", MsmPrepResult)] + [(k, C.c_uint32) for k in ("m2", "tasks", "n_final", "sh_final", "n_levels", "reserved")] + \
+               [("level", MsmTailLevel * MSM_TAIL_MAX_LEVELS), ("table_entries", C.c_uint64), ("level_entries", C.c_uint64)] + \
+               [(k, C.c_void_p) for k in MSM_TAIL_ARRAYS]
+
+
 class Groth16PK(C.Structure):
     _fields_ = [("log_domain", C.c_uint32), ("n_wires", C.c_size_t), ("n_public", C.c_size_t),
                 ("g1_alpha", C.c_void_p), ("g1_beta", C.c_void_p), ("g1_delta", C.c_void_p),
@@ -85,7 +106,7 @@ SYMBOLS = [
     "zk_device_count", "zk_init", "zk_last_error", "zk_version",
     "zk_bn254_g1_msm", "zk_bn254_g2_msm", "zk_bn254_g1_msm_dev", "zk_bn254_g2_msm_dev",
     "zk_bn254_g1_msm_partial_dev", "zk_bn254_g2_msm_partial_dev", "zk_bn254_g1_sum_xyzz", "zk_bn254_g2_sum_xyzz",
-    "zk_bn254_msm_plan_info", "zk_bn254_msm_prep_inspect", "zk_bn254_bases_register", "zk_bn254_bases_register_dev", "zk_bn254_bases_register_cfg", "zk_bn254_bases_build_table", "zk_bn254_bases_lagrange", "zk_bn254_bases_free", "zk_bn254_msm_bases", "zk_bn254_msm_bases_batch", "zk_bn254_msm_bases_batch_dev", "zk_bn254_msm_bases_dev", "zk_bn254_scalars_register", "zk_bn254_scalars_free", "zk_bn254_msm_bases_prepared",
+    "zk_bn254_msm_plan_info", "zk_bn254_msm_prep_inspect", "zk_bn254_msm_tail_inspect", "zk_bn254_bases_register", "zk_bn254_bases_register_dev", "zk_bn254_bases_register_cfg", "zk_bn254_bases_build_table", "zk_bn254_bases_lagrange", "zk_bn254_bases_free", "zk_bn254_msm_bases", "zk_bn254_msm_bases_batch", "zk_bn254_msm_bases_batch_dev", "zk_bn254_msm_bases_dev", "zk_bn254_scalars_register", "zk_bn254_scalars_free", "zk_bn254_msm_bases_prepared",
     "zk_bn254_ntt", "zk_bn254_ntt_dev", "zk_bn254_bit_reverse", "zk_bn254_bit_reverse_dev",
     "zk_bn254_ntt_batch", "zk_bn254_ntt_batch_dev", "zk_bn254_groth16_compute_h_batch", "zk_bn254_groth16_compute_h_batch_dev",
     "zk_bn254_groth16_compute_h", "zk_bn254_groth16_compute_h_dev", "zk_bn254_groth16_h_shard_dev", "zk_bn254_ntt_shard_dev",

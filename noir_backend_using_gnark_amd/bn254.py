@@ -100,15 +100,8 @@ def g2_sum_partials(partials) -> np.ndarray:
     return out
 
 
-def msm_prep_inspect(vectors, n: int | None = None, window_bits: int = 0, scalars_mont: bool = False, table_c: int = 0, stride: int | None = None,
-                     row_first: int = 0, row_step: int = 1, rows: int = 0, row_stride: int | None = None, drop_zero_digits: bool = False,
-                     plan_only: bool = False, arrays=None) -> dict:
-    """The scalar-side half of an MSM alone (zk_bn254_msm_prep_inspect; for tests): the plan and, unless plan_only (host work, no device), the pair count as the
-    device knows it, the control block and every intermediate array of the production preparation.
-    vectors: one (n, 4) array (plain method, or one vector against a table of width table_c), a list of up to three of them (a batch by pointers; the same
-    array object twice is the same device vector twice), or -- with rows > 0 -- one (rows, row_stride, 4) matrix whose rows' first n elements are the vectors.
-    arrays: names of the arrays to copy back (default: all of _lib.MSM_PREP_ARRAYS; the others come back empty)."""
-    req = _lib.MsmPrepRequest()
+def _msm_prep_request(req, vectors, n, window_bits, scalars_mont, table_c, stride, row_first, row_step, rows, row_stride, drop_zero_digits):
+    """fills a _lib.MsmPrepRequest; returns the arrays it points into (keep them alive across the call)"""
     if rows:
         mat = _as_u64(vectors, 4)
         row_stride = row_stride if row_stride is not None else mat.shape[0] // rows
@@ -133,22 +126,102 @@ def msm_prep_inspect(vectors, n: int | None = None, window_bits: int = 0, scalar
     req.by_rows, req.row_stride = int(rows > 0), (row_stride or 0)
     for i, k in enumerate(keep[:3]):
         req.vec[i] = k.ctypes.data
+    return keep
+
+
+def _msm_prep_plan(res) -> dict:
+    return dict({k: int(getattr(res, k)) for k in _lib.MSM_PREP_PLAN}, total=int(res.total), max_tasks=int(res.max_tasks))
+
+
+def _msm_prep_arrays(res, plan, arrays) -> dict:
+    sizes = dict(keys=plan["total"], vals=plan["total"], start=plan["nb"] + 1, task_off=plan["nb"] + 1, task_begin=plan["max_tasks"], len_keys=plan["max_tasks"],
+                 task_ids=plan["max_tasks"], multi_list=plan["nb"])
+    wanted = _lib.MSM_PREP_ARRAYS if arrays is None else tuple(arrays)
+    out = {k: np.zeros(sizes[k] if k in wanted else 0, np.uint32) for k in _lib.MSM_PREP_ARRAYS}
+    for k in wanted:
+        setattr(res, k, out[k].ctypes.data)
+    return out
+
+
+def msm_prep_inspect(vectors, n: int | None = None, window_bits: int = 0, scalars_mont: bool = False, table_c: int = 0, stride: int | None = None,
+                     row_first: int = 0, row_step: int = 1, rows: int = 0, row_stride: int | None = None, drop_zero_digits: bool = False,
+                     plan_only: bool = False, arrays=None) -> dict:
+    """The scalar-side half of an MSM alone (zk_bn254_msm_prep_inspect; for tests): the plan and, unless plan_only (host work, no device), the pair count as the
+    device knows it, the control block and every intermediate array of the production preparation.
+    vectors: one (n, 4) array (plain method, or one vector against a table of width table_c), a list of up to three of them (a batch by pointers; the same
+    array object twice is the same device vector twice), or -- with rows > 0 -- one (rows, row_stride, 4) matrix whose rows' first n elements are the vectors.
+    arrays: names of the arrays to copy back (default: all of _lib.MSM_PREP_ARRAYS; the others come back empty)."""
+    req = _lib.MsmPrepRequest()
+    keep = _msm_prep_request(req, vectors, n, window_bits, scalars_mont, table_c, stride, row_first, row_step, rows, row_stride, drop_zero_digits)  # noqa: F841
     res = _lib.MsmPrepResult()
     check(lib().zk_bn254_msm_prep_inspect(C.byref(req), C.byref(res)))
-    plan = lambda: dict({k: int(getattr(res, k)) for k in _lib.MSM_PREP_PLAN}, total=int(res.total), max_tasks=int(res.max_tasks))  # noqa: E731
-    out = plan()
+    out = _msm_prep_plan(res)
     if plan_only or out["total"] == 0:
         out.update(device_total=0, dropped=False, ctl=np.zeros(64, np.uint32), **{k: np.zeros(0, np.uint32) for k in _lib.MSM_PREP_ARRAYS})
         return out
-    sizes = dict(keys=out["total"], vals=out["total"], start=out["nb"] + 1, task_off=out["nb"] + 1, task_begin=out["max_tasks"], len_keys=out["max_tasks"],
-                 task_ids=out["max_tasks"], multi_list=out["nb"])
-    wanted = _lib.MSM_PREP_ARRAYS if arrays is None else tuple(arrays)
-    arrays = {k: np.zeros(sizes[k] if k in wanted else 0, np.uint32) for k in _lib.MSM_PREP_ARRAYS}
-    for k in wanted:
-        setattr(res, k, arrays[k].ctypes.data)
+    arrays = _msm_prep_arrays(res, out, arrays)
     check(lib().zk_bn254_msm_prep_inspect(C.byref(req), C.byref(res)))
-    assert plan() == out
+    assert _msm_prep_plan(res) == out
     out.update(device_total=int(res.device_total), dropped=bool(res.dropped), ctl=np.array(res.ctl[:], dtype=np.uint32), **arrays)
+    return out
+
+
+def msm_tail_inspect(points, vectors, is_g2: bool = False, l1_m: int = 0, l2_m: int = 0, quad_tail: bool = False, keep_final: bool = False, skip_below: int = 0,
+                     plan_only: bool = False, **prep) -> dict:
+    """The base-side half of an MSM behind the production preparation (zk_bn254_msm_tail_inspect; for tests): window table, accumulate, folds, every reduction
+    level and the finishers, with every intermediate array back as AFFINE points ((k, 8) uint64 on G1, (k, 16) on G2; (0, 0) = infinity).
+    points: (n, 8) / (n, 16) affine bases; vectors and **prep: as for msm_prep_inspect (n, window_bits, scalars_mont, table_c, stride, row_first, row_step,
+    rows, row_stride, drop_zero_digits).  Returns msm_prep_inspect's dictionary FROM THIS RUN plus m2, tasks, n_final, sh_final, levels (a list of dictionaries:
+    kind 'l1' / 'l2' / 'wave' / 'wave_quad', n_in, n_out, sh_in, sh_out, m and, after a run, the level's A and S as (W, n_out, width)), table, partial_acc,
+    partial_fold, and set_values / total (host finish) or final_affine / final_bytes (keep_final: the device finish).  plan_only: host work, no device."""
+    width = 16 if is_g2 else 8
+    pts = _as_u64(points, width)
+    req = _lib.MsmTailRequest()
+    keep = _msm_prep_request(req.prep, vectors, prep.pop("n", None), prep.pop("window_bits", 0), prep.pop("scalars_mont", False), prep.pop("table_c", 0),  # noqa: F841
+                             prep.pop("stride", None), prep.pop("row_first", 0), prep.pop("row_step", 1), prep.pop("rows", 0), prep.pop("row_stride", None),
+                             prep.pop("drop_zero_digits", False))
+    if prep:
+        raise TypeError("unknown arguments: %s" % sorted(prep))
+    if pts.shape[0] < req.prep.n:
+        raise ValueError("fewer points than scalars")
+    req.points, req.is_g2, req.quad_tail, req.keep_final = pts.ctypes.data, int(is_g2), int(quad_tail), int(keep_final)
+    req.l1_m, req.l2_m, req.skip_below = l1_m, l2_m, skip_below
+    res = _lib.MsmTailResult()
+    check(lib().zk_bn254_msm_tail_inspect(C.byref(req), C.byref(res)))
+
+    def plan():
+        d = _msm_prep_plan(res.prep)
+        d.update({k: int(getattr(res, k)) for k in ("m2", "n_final", "sh_final", "table_entries", "level_entries")})
+        d["levels"] = [dict({k: int(getattr(res.level[i], k)) for k in _lib.MSM_TAIL_LEVEL}, kind=_lib.MSM_TAIL_KINDS[int(res.level[i].kind)])
+                       for i in range(res.n_levels)]
+        return d
+    out = plan()
+    sets = int(req.prep.sets) if req.prep.table else 1
+    if plan_only or (out["total"] == 0 and not keep_final):
+        return out
+    arrays = _msm_prep_arrays(res.prep, out, None) if out["total"] else {}
+    W = out["W"]
+    shapes = dict(table=(out["table_entries"], width), partial_acc=(out["max_tasks"], width), partial_fold=(out["max_tasks"], width),
+                  level_a=(out["level_entries"], width), level_s=(out["level_entries"], width))
+    if keep_final:
+        shapes.update(final_affine=(sets, 8), final_bytes=(sets, 32))
+    else:
+        shapes.update(set_values=(W, width), total=(1, width))
+    tail = {k: np.zeros(shp, np.uint8 if k == "final_bytes" else np.uint64) for k, shp in shapes.items()}
+    for k, a in tail.items():
+        setattr(res, k, a.ctypes.data)
+    check(lib().zk_bn254_msm_tail_inspect(C.byref(req), C.byref(res)))
+    assert plan() == out
+    if out["total"]:
+        out.update(device_total=int(res.prep.device_total), dropped=bool(res.prep.dropped), ctl=np.array(res.prep.ctl[:], dtype=np.uint32), **arrays)
+    out["tasks"] = int(res.tasks)
+    at = 0
+    for lv in out["levels"]:
+        cnt = W * lv["n_out"]
+        lv["A"] = tail["level_a"][at:at + cnt].reshape(W, lv["n_out"], width)
+        lv["S"] = tail["level_s"][at:at + cnt].reshape(W, lv["n_out"], width)
+        at += cnt
+    out.update({k: v for k, v in tail.items() if k not in ("level_a", "level_s")})
     return out
 
 

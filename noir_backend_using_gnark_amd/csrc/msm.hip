@@ -1207,6 +1207,22 @@ static int msm_prepare(Slot* s, hipStream_t st, const MsmPlan& P, const Fr* d_sc
     return ZK_OK;
 }
 
+// MsmJob::trace (inspection, msm.hpp): everything enqueued on `st` so far has run when the copy is made
+static int trace_copy(hipStream_t st, std::vector<unsigned char>& dst, const void* src, size_t bytes) {
+    ZK_HIP(hipStreamSynchronize(st));
+    dst.resize(bytes);
+    if (bytes) ZK_HIP(hipMemcpy(dst.data(), src, bytes, hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+static int trace_level(MsmTrace* tr, hipStream_t st, unsigned kind, uint32_t n_in, uint32_t n_out, uint32_t sh_in, uint32_t sh_out, uint32_t m, const void* A,
+                       const void* S, size_t bytes) {
+    tr->levels.emplace_back();
+    MsmTraceLevel& lv = tr->levels.back();
+    lv.kind = kind; lv.n_in = n_in; lv.n_out = n_out; lv.sh_in = sh_in; lv.sh_out = sh_out; lv.m = m;
+    ZK_TRY(trace_copy(st, lv.A, A, bytes));
+    return trace_copy(st, lv.S, S, bytes);
+}
+
 // Base-side half: bucket accumulation, bucket reduction, window sums to pinned memory.  `nb` jobs (<= 3) over the same prepared
 // scalars share ONE accumulate launch on the first job's stream (which waits for the preparation when it ran elsewhere); each
 // job's reduction tail then runs on its own stream.  `d_pts[b]` is indexed by the scalar index; indices < skip_below[b] are skipped.
@@ -1320,6 +1336,8 @@ static int msm_accumulate_batch(int nb, Slot* const* sl, const hipStream_t* sts,
         Slot* s = sl[b];
         hipStream_t st = sts[b];
         bool folded = false;
+        MsmTrace* const tr = jobs[b]->trace;
+        if (tr) ZK_TRY(trace_copy(sa, tr->partial_acc, partial[b], max_tasks * sizeof(Pt)));
 #ifdef ZKMI_EXPERIMENTS  // launch of the fused fold / tail
 #include "experiments/msm_tail_fused_launch.inc"
 #endif
@@ -1327,6 +1345,7 @@ static int msm_accumulate_batch(int nb, Slot* const* sl, const hipStream_t* sts,
             ZK_LAUNCH(s, st, "msm_fold_giant", (k_fold_giant<F>), dim3(GIANT_MAX * 16), dim3(256), 0, partial[b], R.task_off, (const uint32_t*)R.num_multi);  // exits at once without giants
             ZK_LAUNCH(s, st, "msm_fold_multi", (k_fold_multi<F>), dim3(1024), dim3(256), 0, partial[b], R.task_off, R.multi_list, R.num_multi);
         }
+        if (tr) ZK_TRY(trace_copy(st, tr->partial_fold, partial[b], max_tasks * sizeof(Pt)));
         // ---- 6. bucket reduce
         bool quad = false;
         if constexpr (sizeof(F) == sizeof(Fp)) quad = jobs[b]->quad_tail;
@@ -1338,13 +1357,16 @@ static int msm_accumulate_batch(int nb, Slot* const* sl, const hipStream_t* sts,
         uint32_t N = N1, sh = 0;
         for (uint32_t mm = m1; mm > 1; mm >>= 1) sh++;  // value = sum A + 2^sh * sum j S_j
         int cur = 0;
+        if (tr) ZK_TRY(trace_level(tr, st, MsmTraceLevel::L1, B, N1, 0, sh, m1, lvlA[b][0], lvlS[b][0], (size_t)W * N1 * sizeof(Pt)));
         if (P.m2 > 1 && N > 64 * P.m2) {  // second thread-serial level (tails that hide under the next accumulate)
             uint32_t Nout = (N + P.m2 - 1) / P.m2;
             ZK_LAUNCH(s, st, "msm_reduce_l2", (k_reduce_l2<F>), dim3((unsigned)(((size_t)W * Nout + 255) / 256)), dim3(256), 0, (const Pt*)lvlA[b][cur],
                       (const Pt*)lvlS[b][cur], N, W, sh, P.m2, lvlA[b][cur ^ 1], lvlS[b][cur ^ 1]);
             cur ^= 1;
-            N = Nout;
+            const uint32_t sh_in = sh;
             for (uint32_t mm = P.m2; mm > 1; mm >>= 1) sh++;
+            if (tr) ZK_TRY(trace_level(tr, st, MsmTraceLevel::L2, N, Nout, sh_in, sh, P.m2, lvlA[b][cur], lvlS[b][cur], (size_t)W * Nout * sizeof(Pt)));
+            N = Nout;
         }
         // the last level (<= 64 entries per window) is cheaper on the host than one more latency-bound launch, as long as the host
         // has few windows to do (table mode: one)
@@ -1356,6 +1378,8 @@ static int msm_accumulate_batch(int nb, Slot* const* sl, const hipStream_t* sts,
             }
             if (!quad) ZK_LAUNCH(s, st, "msm_reduce_wave", (k_reduce_wave<F>), dim3(W * Nout), dim3(64), 0, (const Pt*)lvlA[b][cur], (const Pt*)lvlS[b][cur], N, W, sh, lvlA[b][cur ^ 1], lvlS[b][cur ^ 1]);
             cur ^= 1;
+            if (tr) ZK_TRY(trace_level(tr, st, quad ? MsmTraceLevel::WAVE_QUAD : MsmTraceLevel::WAVE, N, Nout, sh, sh + fan_log, fan, lvlA[b][cur], lvlS[b][cur],
+                                       (size_t)W * Nout * sizeof(Pt)));
             N = Nout;
             sh += fan_log;
         }
@@ -1905,15 +1929,16 @@ int zk_bn254_msm_plan_info(size_t n, int window_tables, uint32_t* window_bits, u
 }
 
 // the scalar-side half alone, for inspection / tests (include/zkmi.h): the production msm_prepare through the wrappers the provers call, everything copied back
+// (`extra`: what the caller carves out of the slot's arena after this; `allow_empty`: an empty plan runs the wrappers -- they touch nothing -- and is no error)
 static int msm_prep_inspect_run(Slot* s, const zk_msm_prep_request* q, const zk_msm_cfg* cfg, const MsmTable* tab, const MsmPlan& P, MsmPrep* prep,
-                                zk_msm_prep_result* r) {
+                                zk_msm_prep_result* r, size_t extra = 0, bool allow_empty = false) {
     hipStream_t st = s->stream;
     const size_t n = q->n;
     const unsigned sets = tab ? q->sets : 1;
     const size_t elems = q->by_rows ? (size_t)(sets - 1) * q->row_stride + n : n;  // per uploaded block
-    ZK_TRY(s->reserve((q->by_rows ? 1 : sets) * (elems * 32 + 256) + P.need_prep + msm_compact_need(n, sets) + 4096));
+    ZK_TRY(s->reserve((q->by_rows ? 1 : sets) * (elems * 32 + 256) + P.need_prep + msm_compact_need(n, sets) + 4096 + extra));
     const void* d_vec[3] = {nullptr, nullptr, nullptr};
-    for (unsigned v = 0; v < (q->by_rows ? 1u : sets); v++) {
+    for (unsigned v = 0; v < (q->by_rows ? 1u : sets) && P.total; v++) {
         for (unsigned u = 0; u < v; u++)
             if (q->vec[u] == q->vec[v]) d_vec[v] = d_vec[u];  // the same host vector twice: the same device vector twice
         if (d_vec[v]) continue;
@@ -1927,6 +1952,7 @@ static int msm_prep_inspect_run(Slot* s, const zk_msm_prep_request* q, const zk_
     else if (q->by_rows) ZK_TRY(msm_prepare_scalars_table_rows(s, st, d_vec[0], q->row_stride, sets, n, cfg, *tab, prep, drop));
     else if (sets > 1) ZK_TRY(msm_prepare_scalars_table_batch(s, st, d_vec, sets, n, cfg, *tab, prep, drop));
     else ZK_TRY(msm_prepare_scalars_table(s, st, d_vec[0], n, cfg, *tab, prep, drop));
+    if (prep->empty && allow_empty && P.total == 0) return ZK_OK;
     if (prep->empty) return set_err(ZK_ERR_ARG, "MSM inspection: the preparation is empty where its plan is not");
     ZK_HIP(hipStreamSynchronize(st));
     auto back = [&](uint32_t* dst, const uint32_t* src, size_t count) -> int {
@@ -1948,37 +1974,216 @@ static int msm_prep_inspect_run(Slot* s, const zk_msm_prep_request* q, const zk_
     ZK_TRY(back(r->multi_list, prep->multi_list, P.nb));
     return ZK_OK;
 }
-int zk_bn254_msm_prep_inspect(const zk_msm_prep_request* q, zk_msm_prep_result* r) {
-    if (!q || !r) return set_err(ZK_ERR_ARG, "null pointer");
-    zk_msm_cfg cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.scalars_mont = q->scalars_mont;
-    cfg.window_bits = q->window_bits;
-    MsmTable tab;
+// the request's checks and its plan, shared by the two inspections (l1_m / l2_m: the tail's level sizes, table mode only)
+static int msm_inspect_plan(const zk_msm_prep_request* q, unsigned l1_m, unsigned l2_m, zk_msm_cfg* cfg, MsmTable* tab, MsmPlan* P, zk_msm_prep_result* r) {
+    memset(cfg, 0, sizeof *cfg);
+    cfg->scalars_mont = q->scalars_mont;
+    cfg->window_bits = q->window_bits;
     if (q->table) {
         if (q->sets < 1 || (!q->by_rows && q->sets > 3)) return set_err(ZK_ERR_ARG, "MSM inspection: one to three vectors by pointer, any number by rows");
         if (q->stride < q->n || (q->by_rows && q->sets > 1 && q->row_stride < q->n)) return set_err(ZK_ERR_ARG, "MSM inspection: a stride shorter than the vectors");
-        tab.c = q->c;
-        tab.stride = q->stride;
-        tab.row_first = q->row_first;
-        tab.row_step = q->row_step ? q->row_step : 1;
+        tab->c = q->c;
+        tab->stride = q->stride;
+        tab->row_first = q->row_first;
+        tab->row_step = q->row_step ? q->row_step : 1;
+        tab->l1_m = l1_m;
+        tab->l2_m = l2_m;
     } else if (q->sets > 1 || q->by_rows) {
         return set_err(ZK_ERR_ARG, "MSM inspection: several vectors need table mode");
     }
-    MsmPlan P;
-    ZK_TRY(msm_plan<Fp>(q->n, &cfg, nullptr, &P, q->table ? &tab : nullptr, q->table ? q->sets : 1));
-    r->c = P.c; r->W = P.W; r->Wd = P.Wd; r->Wrows = P.Wrows; r->B = P.B; r->nb = P.nb; r->key_bits = P.key_bits; r->L = P.L; r->Lmin = P.Lmin;
-    r->m1 = P.m1; r->N1 = P.N1; r->dropped = 0;
-    r->total = P.total; r->max_tasks = P.max_tasks; r->device_total = 0;
+    ZK_TRY(msm_plan<Fp>(q->n, cfg, nullptr, P, q->table ? tab : nullptr, q->table ? q->sets : 1));
+    r->c = P->c; r->W = P->W; r->Wd = P->Wd; r->Wrows = P->Wrows; r->B = P->B; r->nb = P->nb; r->key_bits = P->key_bits; r->L = P->L; r->Lmin = P->Lmin;
+    r->m1 = P->m1; r->N1 = P->N1; r->dropped = 0;
+    r->total = P->total; r->max_tasks = P->max_tasks; r->device_total = 0;
     memset(r->ctl, 0, sizeof r->ctl);
-    const bool sizes_only = !r->keys && !r->vals && !r->start && !r->task_off && !r->task_begin && !r->len_keys && !r->task_ids && !r->multi_list;
-    if (sizes_only || P.total == 0) return ZK_OK;
+    return ZK_OK;
+}
+static bool msm_prep_sizes_only(const zk_msm_prep_result* r) {
+    return !r->keys && !r->vals && !r->start && !r->task_off && !r->task_begin && !r->len_keys && !r->task_ids && !r->multi_list;
+}
+int zk_bn254_msm_prep_inspect(const zk_msm_prep_request* q, zk_msm_prep_result* r) {
+    if (!q || !r) return set_err(ZK_ERR_ARG, "null pointer");
+    zk_msm_cfg cfg;
+    MsmTable tab;
+    MsmPlan P;
+    ZK_TRY(msm_inspect_plan(q, 0, 0, &cfg, &tab, &P, r));
+    if (msm_prep_sizes_only(r) || P.total == 0) return ZK_OK;
     for (unsigned v = 0; v < (q->by_rows ? 1u : (q->table ? q->sets : 1u)); v++)
         if (!q->vec[v]) return set_err(ZK_ERR_ARG, "null pointer");
     SlotGuard g;
     ZK_TRY(acquire_slot(&g.s));
     MsmPrep prep;
     int rc = msm_prep_inspect_run(g.s, q, &cfg, q->table ? &tab : nullptr, P, &prep, r);
+    if (rc != ZK_OK) (void)hipStreamSynchronize(g.s->stream);  // nothing of this call is in flight when the slot goes back
+    msm_prep_release(&prep);
+    return rc;
+}
+
+// ---- the base-side half behind the same preparation, for inspection / tests (include/zkmi.h): the production table build, accumulate, folds, reduce levels and
+// finishers, with an MsmTrace attached to the job; every array comes back as affine points
+// the level sequence msm_accumulate_batch runs for a plan, restated (sizes of the caller's arrays before the run; the run's own descriptors are compared with it)
+static unsigned msm_tail_geometry(const MsmPlan& P, bool quad, zk_msm_tail_level* lv, uint32_t* n_final, uint32_t* sh_final) {
+    unsigned k = 0;
+    uint32_t N = P.N1, sh = 0;
+    for (uint32_t mm = P.m1; mm > 1; mm >>= 1) sh++;
+    lv[k++] = zk_msm_tail_level{MsmTraceLevel::L1, P.B, P.N1, 0, sh, P.m1};
+    if (P.m2 > 1 && N > 64 * P.m2) {
+        uint32_t Nout = (N + P.m2 - 1) / P.m2, sh_in = sh;
+        for (uint32_t mm = P.m2; mm > 1; mm >>= 1) sh++;
+        lv[k++] = zk_msm_tail_level{MsmTraceLevel::L2, N, Nout, sh_in, sh, P.m2};
+        N = Nout;
+    }
+    const uint32_t fan = quad ? 16 : 64, fan_log = quad ? 4 : 6, host_n = P.W == 1 ? 64 : 1;
+    while (N > host_n && k < ZK_MSM_TAIL_MAX_LEVELS) {
+        uint32_t Nout = (N + fan - 1) / fan;
+        lv[k++] = zk_msm_tail_level{quad ? (uint32_t)MsmTraceLevel::WAVE_QUAD : (uint32_t)MsmTraceLevel::WAVE, N, Nout, sh, sh + fan_log, fan};
+        N = Nout;
+        sh += fan_log;
+    }
+    *n_final = N;
+    *sh_final = sh;
+    return k;
+}
+}  // extern "C" (templates)
+// raw XYZZ entries as the kernels leave them -> affine images (G1 arrives in the interchange format x * 2^261: scaled as msm_finish scales it)
+template <class HF>
+static void tail_affine(const unsigned char* raw, size_t count, uint64_t* out) {
+    static const HFp inv32 = HFp{{32, 0, 0, 0}}.to_mont().inv();
+    for (size_t i = 0; i < count; i++) {
+        XYZZ<HF> p;
+        memcpy(&p, raw + i * sizeof p, sizeof p);
+        if constexpr (sizeof(HF) == sizeof(HFp)) {
+            p.x = p.x * inv32;
+            p.y = p.y * inv32;
+            p.zz = p.zz * inv32;
+            p.zzz = p.zzz * inv32;
+        }
+        Affine<HF> a = p.to_affine();
+        memcpy(out + i * (sizeof a / 8), &a, sizeof a);
+    }
+}
+struct DevFree {  // (hipFree waits for the device: nothing that reads the buffer is in flight when it goes)
+    void* p = nullptr;
+    ~DevFree() { if (p) (void)hipFree(p); }
+};
+template <int G2>
+static int msm_tail_inspect_run(Slot* s, const zk_msm_tail_request* q, const zk_msm_cfg* cfg, const MsmTable* tab, const MsmPlan& P, size_t need_acc, MsmPrep* prep,
+                                zk_msm_tail_result* r) {
+    typedef typename std::conditional<G2 != 0, HFp2, HFp>::type HF;
+    const size_t psz = G2 ? 128 : 64, aw = psz / 8, n = q->prep.n;
+    const unsigned sets = tab ? q->prep.sets : 1;
+    hipStream_t st = s->stream;
+    // ---- points, table
+    DevFree d_pts, d_tab;
+    ZK_HIP(hipMalloc(&d_pts.p, n * psz + 256));
+    if (n) ZK_HIP(hipMemcpyAsync(d_pts.p, q->points, n * psz, hipMemcpyHostToDevice, st));
+    const size_t tab_entries = (size_t)r->table_entries;
+    if (tab) {
+        const size_t tab_alloc = ((size_t)std::max(tab->rows(), 1u) * tab->stride + 1) * psz;  // (a table without rows: msm_build_table_g? still clears one row)
+        ZK_HIP(hipMalloc(&d_tab.p, tab_alloc));
+        ZK_HIP(hipMemsetAsync(d_tab.p, 0, tab_alloc, st));
+        ZK_TRY(G2 ? msm_build_table_g2(s, st, d_pts.p, n, tab->stride, 0, tab->c, d_tab.p, tab->row_first, tab->row_step)
+                  : msm_build_table_g1(s, st, d_pts.p, n, tab->stride, 0, tab->c, d_tab.p, tab->row_first, tab->row_step));
+        if (r->table && tab_entries) {
+            ZK_HIP(hipStreamSynchronize(st));
+            ZK_HIP(hipMemcpy(r->table, d_tab.p, tab_entries * psz, hipMemcpyDeviceToHost));
+        }
+    }
+    // ---- the preparation (and its arrays, from THIS run: the device picks the task length)
+    ZK_TRY(msm_prep_inspect_run(s, &q->prep, cfg, tab, P, prep, &r->prep, need_acc + (size_t)sets * 128 + 4096, true));
+    uint32_t tasks = 0;
+    if (!prep->empty) ZK_HIP(hipMemcpy(&tasks, prep->task_off + P.nb, 4, hipMemcpyDeviceToHost));
+    // ---- accumulate, folds, reduce levels: the production call, traced
+    MsmTrace trace;
+    MsmJob job;
+    job.trace = &trace;
+    job.quad_tail = q->quad_tail != 0;
+    job.keep_final = q->keep_final != 0;
+    const void* d_bases = tab ? d_tab.p : d_pts.p;
+    ZK_TRY(G2 ? msm_g2_accumulate(s, st, *prep, d_bases, q->skip_below, &job) : msm_g1_accumulate(s, st, *prep, d_bases, q->skip_below, &job));
+    // ---- finish
+    if (q->keep_final) {
+        if constexpr (!G2) {
+            void* d_out = s->alloc((size_t)sets * 64);
+            void* d_enc = s->alloc((size_t)sets * 32);
+            if (!d_out || !d_enc) return set_err(ZK_ERR_HIP, "MSM inspection: the finisher's buffers were not reserved");
+            ZK_TRY(msm_g1_sets_affine_dev(job, sets, d_out, d_enc));
+            ZK_TRY(slot_sync(s, st));
+            if (r->final_affine) ZK_HIP(hipMemcpy(r->final_affine, d_out, (size_t)sets * 64, hipMemcpyDeviceToHost));
+            if (r->final_bytes) ZK_HIP(hipMemcpy(r->final_bytes, d_enc, (size_t)sets * 32, hipMemcpyDeviceToHost));
+        }
+    } else {
+        std::vector<XYZZ<HF>> per_set(std::max(P.W, 3u));
+        XYZZ<HF> tot = XYZZ<HF>::inf();
+        if (!tab) {
+            ZK_TRY(msm_finish<HF>(job, &tot, per_set.data()));  // what msm_g?_finish runs, the windows' values kept
+        } else {
+            if constexpr (G2) ZK_TRY(msm_g2_finish_sets(job, per_set.data(), sets));
+            else ZK_TRY(msm_g1_finish_sets(job, per_set.data(), sets));
+        }
+        if (r->total && !tab) write_affine(tot, r->total);
+        for (unsigned w = 0; r->set_values && w < P.W; w++) write_affine(per_set[w], r->set_values + (size_t)w * aw);
+    }
+    if (job.empty) return ZK_OK;
+    // ---- what the run did, against what the plan-only call said
+    bool same = job.n_final == r->n_final && job.sh_final == r->sh_final && trace.levels.size() == r->n_levels;
+    for (unsigned k = 0; same && k < r->n_levels; k++) {
+        const MsmTraceLevel& a = trace.levels[k];
+        const zk_msm_tail_level& b = r->level[k];
+        same = a.kind == b.kind && a.n_in == b.n_in && a.n_out == b.n_out && a.sh_in == b.sh_in && a.sh_out == b.sh_out && a.m == b.m;
+    }
+    if (!same) return set_err(ZK_ERR_ARG, "MSM inspection: the tail ran %zu levels to n_final = %u, sh_final = %u; the plan states %u, %u, %u", trace.levels.size(),
+                              job.n_final, job.sh_final, r->n_levels, r->n_final, r->sh_final);
+    r->tasks = tasks;
+    // padding tasks are never written: only the real tasks' slots are converted, the others come back as (0, 0)
+    if (r->partial_acc) tail_affine<HF>(trace.partial_acc.data(), tasks, r->partial_acc);
+    if (r->partial_fold) tail_affine<HF>(trace.partial_fold.data(), tasks, r->partial_fold);
+    size_t at = 0;
+    for (const MsmTraceLevel& lv : trace.levels) {
+        const size_t cnt = (size_t)P.W * lv.n_out;
+        if (r->level_a) tail_affine<HF>(lv.A.data(), cnt, r->level_a + at * aw);
+        if (r->level_s) tail_affine<HF>(lv.S.data(), cnt, r->level_s + at * aw);
+        at += cnt;
+    }
+    return ZK_OK;
+}
+extern "C" {
+int zk_bn254_msm_tail_inspect(const zk_msm_tail_request* q, zk_msm_tail_result* r) {
+    if (!q || !r) return set_err(ZK_ERR_ARG, "null pointer");
+    const zk_msm_prep_request* pq = &q->prep;
+    if (q->is_g2 && (q->quad_tail || q->keep_final)) return set_err(ZK_ERR_ARG, "MSM inspection: the four-lane tail and the device finish are G1 only");
+    if (!pq->table && (q->l1_m || q->l2_m || q->keep_final)) return set_err(ZK_ERR_ARG, "MSM inspection: level sizes and the device finish need table mode");
+    if (pq->table && q->skip_below) return set_err(ZK_ERR_ARG, "MSM inspection: skip_below is for the plain method (a table's entries are not point indices)");
+    zk_msm_cfg cfg;
+    MsmTable tab;
+    MsmPlan P;
+    ZK_TRY(msm_inspect_plan(pq, q->l1_m, q->l2_m, &cfg, &tab, &P, &r->prep));
+    size_t need_acc = P.need_acc;
+    if (q->is_g2) {
+        MsmPlan P2;
+        ZK_TRY(msm_plan<Fp2>(pq->n, &cfg, nullptr, &P2, pq->table ? &tab : nullptr, pq->table ? pq->sets : 1));
+        need_acc = P2.need_acc;
+    }
+    r->m2 = P.m2;
+    r->tasks = 0;
+    r->table_entries = pq->table ? (uint64_t)tab.rows() * tab.stride : 0;
+    memset(r->level, 0, sizeof r->level);
+    r->n_levels = P.total ? msm_tail_geometry(P, q->quad_tail != 0, r->level, &r->n_final, &r->sh_final) : 0;
+    if (!P.total) r->n_final = r->sh_final = 0;
+    r->level_entries = 0;
+    for (unsigned k = 0; k < r->n_levels; k++) r->level_entries += (uint64_t)P.W * r->level[k].n_out;
+    const bool sizes_only = msm_prep_sizes_only(&r->prep) && !r->table && !r->partial_acc && !r->partial_fold && !r->level_a && !r->level_s && !r->set_values &&
+                            !r->total && !r->final_affine && !r->final_bytes;
+    if (sizes_only) return ZK_OK;
+    if (P.total == 0 && !q->keep_final) return ZK_OK;  // an empty plan: only the device finish has anything to do (it writes infinities)
+    if (pq->n && !q->points) return set_err(ZK_ERR_ARG, "null pointer");
+    for (unsigned v = 0; P.total && v < (pq->by_rows ? 1u : (pq->table ? pq->sets : 1u)); v++)
+        if (!pq->vec[v]) return set_err(ZK_ERR_ARG, "null pointer");
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    MsmPrep prep;
+    int rc = q->is_g2 ? msm_tail_inspect_run<1>(g.s, q, &cfg, pq->table ? &tab : nullptr, P, need_acc, &prep, r)
+                      : msm_tail_inspect_run<0>(g.s, q, &cfg, pq->table ? &tab : nullptr, P, need_acc, &prep, r);
     if (rc != ZK_OK) (void)hipStreamSynchronize(g.s->stream);  // nothing of this call is in flight when the slot goes back
     msm_prep_release(&prep);
     return rc;

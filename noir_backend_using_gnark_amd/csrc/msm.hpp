@@ -3,6 +3,7 @@
 #include "ctx.hpp"
 #include "curve.hpp"
 #include "host_ff.hpp"
+#include <vector>
 
 namespace zkmi {
 
@@ -60,6 +61,22 @@ struct MsmPrep {
     hipEvent_t ready = nullptr;  // recorded on the preparing stream
 };
 
+// What a job's accumulate + reduction tail computed on the way, for inspection (tests; zk_bn254_msm_tail_inspect): with MsmJob::trace set, msm_accumulate_batch
+// synchronises the job's stream after the accumulate launch, after the two fold launches and after every reduce launch and copies the raw device arrays here
+// (XYZZ entries as the kernels leave them: G1 in the interchange format x * 2^261, G2 canonical).  The launches are the production ones; nothing else changes.
+struct MsmTraceLevel {
+    enum Kind : unsigned { L1 = 1, L2 = 2, WAVE = 3, WAVE_QUAD = 4 };
+    unsigned kind = 0;
+    uint32_t n_in = 0, n_out = 0;    // entries per bucket set before / after the level (level 1: buckets in)
+    uint32_t sh_in = 0, sh_out = 0;  // value = sum_j A_j + 2^sh * sum_j j S_j before / after
+    uint32_t m = 0;                  // entries a lane (l1, l2) or a wave (wave, wave_quad) folds
+    std::vector<unsigned char> A, S; // W * n_out entries each
+};
+struct MsmTrace {
+    std::vector<unsigned char> partial_acc, partial_fold;  // the task array (max_tasks entries) after k_accumulate / after k_fold_giant + k_fold_multi
+    std::vector<MsmTraceLevel> levels;
+};
+
 // Asynchronous form: *_launch enqueues the device pipeline on `st` (window sums land in the slot's pinned buffer),
 // *_finish synchronises that stream and does the host Horner.  One job per slot at a time.
 struct MsmJob {
@@ -81,6 +98,7 @@ struct MsmJob {
     // [w * n_final, (w + 1) * n_final), in the slot's arena -- instead of being copied to pinned memory; msm_g1_sets_affine_dev finishes such a job
     bool keep_final = false;
     const void *d_final_a = nullptr, *d_final_s = nullptr;
+    MsmTrace* trace = nullptr;  // inspection (above); null: nothing is added but this test
 };
 // Device finish of a G1 job launched with keep_final: one affine point per bucket set (gnark's Montgomery image, (0, 0) = infinity) to d_out[0 .. sets) and / or
 // its 32-byte compressed encoding to d_compressed (4-byte aligned; either may be null), enqueued on the job's stream.  An empty job writes infinities.
