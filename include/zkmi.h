@@ -626,6 +626,53 @@ int zk_bn254_plonk_open_batch_dev(uint64_t pk_handle, const void *d_fh, const vo
 int zk_bn254_plonk_commit_batch_dev(uint64_t pk_handle, const void *d_rows, size_t row_stride, size_t len, size_t rows, int from_values, void *d_out,
                                     void *d_compressed);
 
+/* BATCH PLONK PROVING: the proofs of `rows` witnesses against ONE resident key in one call, assembled on the device from the row entries above -- round 1's
+ * gather, blinding and canonical forms, the row forms of rounds 2 to 5, the row-batched commitments, the Fiat-Shamir transcript (one lane per row) and
+ * Proof.WriteTo.  Row v's ZK_PLONK_PROOF_BYTES are, byte for byte, what zk_bn254_plonk_prove writes for that solution, those blinders and those challenges.
+ * Nothing but the finished proofs and the verdicts crosses to the host, and no host work grows with the number of rows.
+ *   zk_bn254_plonk_prove_batch
+ *     solutions    row v = the n_vars Montgomery images at element v * sol_stride (public inputs first): host memory, or device memory when on_device != 0
+ *     blinders     rows x 9, host: the nine blinding scalars of each row (l: 2, r: 2, o: 2, z: 3)
+ *     challenges   NULL: gnark's SHA-256 transcript, exactly as zk_bn254_plonk_prove derives it; otherwise rows x 5 pinned values, host, in the single prover's
+ *                  order (gamma, beta, alpha, zeta, kzg's folding gamma): a copy takes the place of every transcript launch, the path is otherwise the same
+ *     chunk_rows   0, or a cap on the automatic chunk (so that several chunks can be had at a small size); it never changes a byte
+ *     proofs_out   rows x 548 bytes, host;  status_out: rows int, host: 0 = a proof; 1 = the row's solution does not satisfy the circuit (the verdict of
+ *                  zk_bn254_plonk_quotient_batch_dev): its 548 bytes are zero, and neither the call nor the other rows fail
+ *     The digest of the folded quotient is always taken by linearity from the row's own [H0], [H1], [H2]; the digest of the linearised polynomial by linearity from
+ *     [Z] and the key's digests once the key's digests are known to be consistent (Setup's key; a key read from its wire image after a single proof has checked
+ *     it), through the row MSM otherwise -- the same bytes.  The batch itself never marks a key consistent.
+ *     CHUNKS: the rows run in chunks, the largest row count whose workspace -- per row: the solution (host form), l, r, o as values and as coefficients, z, the
+ *     quotient's workspace, h, the linearised polynomial, the folded quotient, the two opening quotients, the openings' workspace, the digests -- fits 1 GiB of the
+ *     slot's arena, capped at a third of the row MSM's own chunk (zk_bn254_msm_rows_info) and by chunk_rows.  Per chunk the host synchronises a fixed number of
+ *     times (in front of every row MSM) and makes one copy of proofs and verdicts.
+ *     The key's `live` lock is held shared; neither its per-proof mutex nor its per-proof workspace is touched: calls overlap each other and a single proof in
+ *     flight.  A key whose bases are not on one device entry runs its rows through zk_bn254_plonk_prove one after the other.
+ *   zk_bn254_plonk_prove_batch_info   *chunk_rows: the automatic chunk for device-resident solutions (1 for a key that runs row by row); *commits_batched: whether
+ *     the row MSM's batched path serves the key's SRS; *lin_by_linearity: whether the next batch takes the linearised polynomial's digest by linearity.  Any of the
+ *     three may be NULL.
+ *   zk_bn254_plonk_challenges_batch_dev   the transcript alone: challenge `stage` of `rows` proofs, one lane per row, everything in device memory.
+ *     stage 0  gamma: binds the key's eight digests, the row's public inputs (npub Montgomery images at d_pub + v * pub_stride), then [L], [R], [O]
+ *     stage 1  beta:  binds gamma's raw digest            stage 2  alpha: beta's raw digest, then [Z]          stage 3  zeta: alpha's raw digest, then [H0], [H1], [H2]
+ *     stage 4  kzg's folding gamma, a transcript of its own: binds zeta, [foldedH], [lin], [L], [R], [O], the key's [S1], [S2], and the seven claimed values
+ *     d_points   the stage's points of row v, zk_g1_affine each ((0, 0) = infinity, bound as 0x40 and 63 zero bytes), at d_points + (3, -, 1, 3, 5 for stages
+ *                0 .. 4) * v in the order above; unused (may be NULL) at stage 1
+ *     d_prev     stages 1 to 3: the previous stage's raw digests, 32 bytes per row, as that stage wrote them; stage 4: zeta[v], one Montgomery image per row;
+ *                unused (may be NULL) at stage 0
+ *     d_values   stage 4: eight elements per row as zk_bn254_plonk_linearize_batch_dev writes them, of which the first seven are bound; unused otherwise
+ *     d_out      2 * rows * 32 bytes: the challenge of row v, reduced as fr.SetBytes, Montgomery, at element v; behind the rows challenges the raw 32-byte digests,
+ *                row v at byte 32 * (rows + v): the next stage's d_prev
+ *     The part of gamma's message that is the same for every row ("gamma" and the key's digests) is hashed once per call on the host.
+ * ARGUMENT ERRORS, decided before a device is looked for: a null pointer, a stage outside 0 .. 4, sol_stride < n_vars or pub_stride < npub with more than one
+ * row, an output overlapping an input or the other output -> ZK_ERR_ARG; n_vars not the key's -> ZK_ERR_LEN; an unknown key -> ZK_ERR_HANDLE; rows == 0 ->
+ * ZK_OK, nothing happens.  zk_bn254_plonk_prove_batch returns ZK_OK whenever its arguments were sound.  The challenges entry synchronises `stream` (NULL: the
+ * slot's own) before it returns. */
+int zk_bn254_plonk_prove_batch(uint64_t pk_handle, const void *solutions, size_t n_vars, size_t sol_stride, size_t rows, int on_device,
+                               const zk_fr *blinders /* rows x 9 */, const zk_fr *challenges /* NULL or rows x 5 */, size_t chunk_rows /* 0 = automatic */,
+                               uint8_t *proofs_out /* rows x 548, host */, int *status_out /* rows, host */);
+int zk_bn254_plonk_prove_batch_info(uint64_t pk_handle, size_t *chunk_rows, int *commits_batched, int *lin_by_linearity);
+int zk_bn254_plonk_challenges_batch_dev(uint64_t pk_handle, int stage, size_t rows, const void *d_pub, size_t pub_stride, const void *d_points,
+                                        const void *d_prev, const void *d_values, void *d_out, void *stream);
+
 /* ---- the callers either side of the PLONK path: the reference's exported entry points, restated over the device path -----------------------
  * PlonkPreprocess (gnark_backend_ffi/main.go:58-78) and PlonkProveWithPK (main.go:24-37) take the ACIR as JSON (acir/acir.go:17-75), the witness
  * values as the hex felt vector (internal/backend/helpers.go:24-33) and the key as hex of ProvingKey.WriteTo (helpers.go:49-60, 82-87); the

@@ -8,6 +8,7 @@
 //   the reference's      DeserializeFelts                                                                 [REF internal/backend/helpers.go:24-33]
 // Go's `(value, error)` returns become `Error` return values (nil == ok()); nothing throws.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -485,6 +486,30 @@ inline Error OpenBatch(const ProvingKey& pk, const OpenRows& in, size_t rows, vo
 // d_compressed: rows x 32 bytes; one of the two may be null.
 inline Error CommitBatch(const ProvingKey& pk, const void* d_rows, size_t row_stride, size_t len, size_t rows, bool from_values, void* d_out, void* d_compressed) {
     return make_error(zk_bn254_plonk_commit_batch_dev(pk.handle(), d_rows, row_stride, len, rows, from_values ? 1 : 0, d_out, d_compressed));
+}
+
+// plonk.Prove for `rows` witnesses of one key in one call (zk_bn254_plonk_prove_batch, whose comment in zkmi.h says the rest): solutions[v] and blinders[9 v ..)
+// are row v's; challenges = nullptr (the transcript) or five pinned values per row.  proofs[v] is what Prove writes for row v; (*satisfied)[v] is false where the
+// row's solution violates the circuit (its proof is then all zero), which fails neither the call nor the other rows.
+inline Error ProveBatch(const ProvingKey& pk, const std::vector<fr::Vector>& solutions, const std::vector<fr::Element>& blinders, std::vector<Proof>* proofs,
+                        std::vector<bool>* satisfied, const fr::Element* challenges = nullptr) {
+    const size_t rows = solutions.size(), nv = pk.NbVariables();
+    if (blinders.size() != 9 * rows) return Error{ZK_ERR_LEN, "nine blinders per solution"};
+    fr::Vector flat(rows * nv);
+    for (size_t v = 0; v < rows; v++) {
+        if (solutions[v].size() != nv) return Error{ZK_ERR_LEN, "len(solution) != number of variables of the constraint system"};
+        std::copy(solutions[v].begin(), solutions[v].end(), flat.begin() + v * nv);
+    }
+    proofs->assign(rows, Proof{});
+    std::vector<int> status(rows, 0);
+    if (rows == 0) {
+        satisfied->clear();
+        return Error{};
+    }
+    Error e = make_error(zk_bn254_plonk_prove_batch(pk.handle(), flat.data(), nv, nv, rows, 0, blinders.data(), challenges, 0, (*proofs)[0].bytes, status.data()));
+    satisfied->assign(rows, false);
+    for (size_t v = 0; v < rows; v++) (*satisfied)[v] = status[v] == 0;
+    return e;
 }
 
 // plonk.Verify(proof, vk, publicWitness) on the host: vk = the bytes of VerifyingKey.WriteTo, srs supplies the two G2 points InitKZG attaches.

@@ -132,6 +132,7 @@ SYMBOLS = [
     "zk_groth16_lower_resident", "zk_groth16_key_resident", "zk_groth16_public_inputs", "zk_bn254_groth16_pk_build_tables", "zk_bn254_groth16_pk_bytes",
     "zk_export_set_new_srs_size", "zk_export_new_srs_size", "zk_warm_session_streams", "zk_warm_session_streams_background", "zk_background_wait", "zk_background_hold", "zk_background_set_yield_ms", "zk_bn254_bases_build_table_background",
     "zk_bn254_msm_bases_rows", "zk_bn254_msm_bases_rows_dev", "zk_bn254_msm_rows_info", "zk_bn254_plonk_commit_batch_dev",
+    "zk_bn254_plonk_prove_batch", "zk_bn254_plonk_prove_batch_info", "zk_bn254_plonk_challenges_batch_dev",
     "zk_bn254_kzg_open", "zk_bn254_kzg_batch_open_single_point", "zk_bn254_kzg_verify", "zk_bn254_kzg_fold_proof", "zk_bn254_kzg_batch_verify_single_point", "zk_bn254_kzg_verify_batch",
 ]
 

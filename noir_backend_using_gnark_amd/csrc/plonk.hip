@@ -33,6 +33,7 @@
 #include "lagrange.hpp"
 #include "multidev.hpp"
 #include "ntt.hpp"
+#include "plonk_batch.hpp"
 #include "proofio.hpp"
 #include "scan.hpp"
 #include "text_host.hpp"
@@ -531,7 +532,6 @@ __device__ __forceinline__ Fr fr_inv_fermat(const Fr& x) {
 }
 // what a row of round 4 needs of its zeta, once per row: LIN_PT elements -- the points zeta and omega zeta (a, a^K, a^(256 K) each), zeta^(n+2), and
 // lag = (zeta^n - 1) / (zeta - 1) * alpha^2 / n with 1 / 0 = 0
-constexpr uint32_t LIN_PT = 8;
 __global__ __launch_bounds__(256) void k_lin_points_rows(const Fr* __restrict__ zeta, const Fr* __restrict__ alpha, uint32_t rows, uint32_t K, unsigned logn, Fr gen,
                                                          Fr card_inv, Fr* __restrict__ pts) {
     const uint32_t v = blockIdx.x * 256 + threadIdx.x;
@@ -854,37 +854,9 @@ __global__ void k_perm_to_be(const uint32_t* __restrict__ in, size_t cnt, uint32
 }
 
 // ------------------------------------------------------------------------------------------------ resident key
-struct PlonkPK {
-    unsigned logn = 0, logN4 = 0, log_rho = 0;
-    size_t n = 0, N4 = 0, n_public = 0, n_constraints = 0, n_vars = 0;
-    uint64_t srs = 0;
-    uint64_t lag_srs = 0;  // the SRS in Lagrange form over this key's domain + the two points of the blinding (lagrange.hip; zk_bn254_plonk_pk_lagrange_srs), or 0
-    HFr gen, u, card_inv;
-    // canonical (regular) polynomials of the key, n each, and LQk (Lagrange)
-    Fr *ql = nullptr, *qr = nullptr, *qm = nullptr, *qo = nullptr, *cqk = nullptr, *lqk = nullptr, *s1 = nullptr, *s2 = nullptr, *s3 = nullptr;
-    uint32_t* perm = nullptr;  // pk.Permutation (3n), kept for ProvingKey.WriteTo
-    Fr* sig = nullptr;      // S1 | S2 | S3 in Lagrange form (3n): what BuildRatioCopyConstraint reads through pk.Permutation
-    Fr* e_cqk = nullptr;    // CQk (qk WITHOUT the public inputs) as LagrangeCoset on the big domain: per proof only the public inputs' share is added (k_qk_coset)
-    Fr* e[9] = {};          // ql, qr, qm, qo, s1, s2, s3, L1, id as LagrangeCoset on the big domain, bit-reversed layout (gnark caches the first 7)
-    uint32_t *xa = nullptr, *xb = nullptr, *xc = nullptr;
-    Affine<HFp> vk_s[3], vk_ql, vk_qr, vk_qm, vk_qo, vk_qk;
-    // the verifying-key digests are known to be the commitments of THIS key's polynomials under ITS SRS (Setup computed them, or a proof has confirmed it):
-    // the digest of the linearised polynomial may then be taken by linearity (seven scalar multiplications on the host) instead of an n-point MSM
-    bool vk_consistent = false;
-    // per-proof workspace (one proof at a time per key)
-    Fr *w_big[5] = {}, *w_small = nullptr;
-    std::shared_ptr<std::mutex> mu;
-    // held shared by a call that only READS the key's tables and brings its own workspace (zk_bn254_plonk_quotient_batch_dev): such calls overlap each other and
-    // a proof in flight; zk_bn254_plonk_pk_free takes it exclusively before the key is destroyed
-    std::shared_ptr<std::shared_mutex> live;
-    std::vector<void*> allocs;
-    size_t bytes = 0;  // HBM held by the key
-};
 static std::mutex g_ppk_mu;
 static std::map<uint64_t, PlonkPK*> g_ppks;
 static uint64_t g_next_ppk = 1;
-
-static const zk_msm_cfg kMont = {0, 1, 0, 0};
 
 static int pk_alloc(PlonkPK* P, Fr** out, size_t elems) {
     void* p = nullptr;
@@ -899,7 +871,6 @@ static void pk_destroy(PlonkPK* P) {
     for (void* p : P->allocs) (void)hipFree(p);
     delete P;
 }
-static unsigned grid_of(size_t n) { return (unsigned)((n + 255) / 256); }
 
 // kzg.Commit(p, srs) = MultiExp(srs.G1[:len(p)], p), p resident in HBM (Montgomery)
 static int commit(const PlonkPK* P, Slot* s, hipStream_t st, const Fr* d_p, size_t len, Affine<HFp>* out) {
@@ -1209,21 +1180,13 @@ static int domains_for(size_t size_system, unsigned* logn, unsigned* logN4) {
 //               on the plan of n itself: K = max(8, ceil(n / 2^18)) elements per lane, nb = ceil(n / 256 K) workgroups per row
 // The workspace comes from the slot's arena, RATIO_SCRATCH bytes at a time: more rows than fit (or than a grid's y holds) go in chunks on the same stream.
 constexpr size_t RATIO_SCRATCH = (size_t)1 << 30;
-constexpr size_t RATIO_GRID_ROWS = 65535;
-struct RatioWs {
-    uint32_t K = 0, nb = 0;
-    size_t chunk = 0;    // rows per group of launches
-    bool single = false; // the one-row form: `one` is the prover's scan plan
-    Fr *num = nullptr, *den = nullptr, *scr = nullptr, *t = nullptr, *b = nullptr;
-    ScanBufs one;
-};
 static void ratio_plan(size_t n, uint32_t* K, uint32_t* nb) {
     uint32_t k = (uint32_t)((n + 256 * 1024 - 1) / (256 * 1024));
     if (k < 8) k = 8;
     *K = k;
     *nb = (uint32_t)(((n + k - 1) / k + 255) / 256);
 }
-static size_t ratio_row_bytes(size_t n) {
+size_t ratio_row_bytes(size_t n) {
     uint32_t K, nb;
     ratio_plan(n, &K, &nb);
     return (3 * n + (size_t)nb * 257) * sizeof(Fr);
@@ -1232,11 +1195,11 @@ static size_t ratio_row_bytes(size_t n) {
 static size_t ratio_chunk(size_t n, size_t rows, size_t extra) {
     return std::min(std::min(rows, RATIO_GRID_ROWS), std::max<size_t>(1, RATIO_SCRATCH / (ratio_row_bytes(n) + extra)));
 }
-static size_t ratio_ws_bytes(size_t n, size_t chunk, bool single) {
+size_t ratio_ws_bytes(size_t n, size_t chunk, bool single) {
     return single ? 3 * (n * sizeof(Fr) + 256) + scan_need(n + 8) + 4096 : chunk * ratio_row_bytes(n) + 5 * 256;
 }
 // after the caller's reserve() of at least ratio_ws_bytes
-static int ratio_ws_take(Slot* s, size_t n, size_t chunk, bool single, RatioWs* W) {
+int ratio_ws_take(Slot* s, size_t n, size_t chunk, bool single, RatioWs* W) {
     W->single = single;
     W->chunk = single ? 1 : chunk;
     W->num = (Fr*)s->alloc(W->chunk * n * sizeof(Fr));
@@ -1251,8 +1214,8 @@ static int ratio_ws_take(Slot* s, size_t n, size_t chunk, bool single, RatioWs* 
     return ZK_OK;
 }
 // row v: wires at l / r / o + v * in_stride, challenges d_beta[v], d_gamma[v] (device), Z to z + v * out_stride.  sig = S1 | S2 | S3 in Lagrange form.
-static int ratio_rows_dev(Slot* s, hipStream_t st, const Domain* d0, const Fr* sig, const Fr* l, const Fr* r, const Fr* o, size_t in_stride, size_t rows,
-                          const Fr* d_beta, const Fr* d_gamma, Fr* z, size_t out_stride, const RatioWs& W) {
+int ratio_rows_dev(Slot* s, hipStream_t st, const Domain* d0, const Fr* sig, const Fr* l, const Fr* r, const Fr* o, size_t in_stride, size_t rows,
+                   const Fr* d_beta, const Fr* d_gamma, Fr* z, size_t out_stride, const RatioWs& W) {
     const size_t n = (size_t)1 << d0->logn;
     const HFr u = d0->coset, uu = u * u;
     const Fr* tw = d0->tw;
@@ -1304,11 +1267,6 @@ static int sigma_checked_dev(Slot* s, hipStream_t st, const Domain* d0, const ui
               d_sigma, d_flag);
     return ZK_OK;
 }
-static bool spans_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const char *a0 = (const char*)a, *b0 = (const char*)b;
-    return a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-static size_t rows_span(size_t rows, size_t stride, size_t n) { return rows ? ((rows - 1) * stride + n) * sizeof(Fr) : 0; }
 // the argument contract of the ratio entries that take device rows (sigma_elems: 3n, or 0 where the key supplies it)
 static int ratio_dev_args(const void* l, const void* r, const void* o, size_t in_stride, size_t n, size_t rows, const void* sigma, size_t sigma_elems, const void* beta,
                           const void* gamma, const void* z, size_t out_stride) {
@@ -1334,7 +1292,7 @@ static int ratio_dev_args(const void* l, const void* r, const void* o, size_t in
 // a time; more rows than fit go in chunks on the same stream.  The key's own per-proof workspace is not touched.
 constexpr size_t QUOT_SCRATCH = (size_t)1 << 30;
 static bool quot_qk_direct(const PlonkPK* P) { return P->n_public <= PLONK_PI_DIRECT_MAX && P->logN4 >= 2; }
-static size_t quot_row_bytes(const PlonkPK* P) { return (5 * P->N4 + (quot_qk_direct(P) ? 0 : P->n)) * sizeof(Fr); }
+size_t quot_row_bytes(const PlonkPK* P) { return (5 * P->N4 + (quot_qk_direct(P) ? 0 : P->n)) * sizeof(Fr); }
 static size_t quot_chunk(const PlonkPK* P, size_t rows) { return std::min(std::min(rows, RATIO_GRID_ROWS), std::max<size_t>(1, QUOT_SCRATCH / quot_row_bytes(P))); }
 // 1 / (x^n - 1) on the coset of the big domain: x = g W^j  =>  x^n = g^n (W^n)^j, W^n of order rho <= 8
 static void quot_xn_inv(const PlonkPK* P, const Domain* d1, Fr out[8]) {
@@ -1348,9 +1306,9 @@ static void quot_xn_inv(const PlonkPK* P, const Domain* d1, Fr out[8]) {
 }
 // row v: blinded canonical l, r, o (n + 2) and z (n + 3) at + v * in_stride, public inputs at pub + v * pub_stride, challenges d_alpha / d_beta / d_gamma[v]
 // (device), h to h + v * out_stride, verdict to status[v].  ws: chunk * quot_row_bytes(P) bytes.
-static int quotient_rows_dev(Slot* s, hipStream_t st, const PlonkPK* P, const Fr* l, const Fr* r, const Fr* o, const Fr* z, size_t in_stride, const Fr* pub,
-                             size_t pub_stride, size_t rows, const Fr* d_alpha, const Fr* d_beta, const Fr* d_gamma, Fr* h, size_t out_stride, int* status, Fr* ws,
-                             size_t chunk) {
+int quotient_rows_dev(Slot* s, hipStream_t st, const PlonkPK* P, const Fr* l, const Fr* r, const Fr* o, const Fr* z, size_t in_stride, const Fr* pub,
+                      size_t pub_stride, size_t rows, const Fr* d_alpha, const Fr* d_beta, const Fr* d_gamma, Fr* h, size_t out_stride, int* status, Fr* ws,
+                      size_t chunk) {
     const size_t n = P->n, N4 = P->N4, keep = 3 * (n + 2);
     const unsigned logN4 = P->logN4;
     const bool direct = quot_qk_direct(P);
@@ -1406,7 +1364,7 @@ struct OpenWs {
     size_t chunk = 0;
     Fr *pts = nullptr, *btot = nullptr, *tcarry = nullptr, *fold = nullptr;
 };
-static size_t open_row_bytes(size_t len, unsigned npoly, size_t pt, size_t fold) {
+size_t open_row_bytes(size_t len, unsigned npoly, size_t pt, size_t fold) {
     uint32_t K, nb;
     ratio_plan(len, &K, &nb);
     return (pt + (size_t)npoly * nb + (size_t)nb * 256 + fold) * sizeof(Fr);
@@ -1453,9 +1411,9 @@ static int poly_open_rows_dev(Slot* s, hipStream_t st, const Fr* f, size_t in_st
     return ZK_OK;
 }
 // round 4 (zk_bn254_plonk_linearize_batch_dev in zkmi.h says what goes where)
-static int linearize_rows_dev(Slot* s, hipStream_t st, const PlonkPK* P, const Fr* l, const Fr* r, const Fr* o, const Fr* z, size_t in_stride, const Fr* h,
-                              size_t h_stride, size_t rows, const Fr* d_alpha, const Fr* d_beta, const Fr* d_gamma, const Fr* d_zeta, Fr* values, Fr* zquot, Fr* lin,
-                              Fr* fh, size_t out_stride) {
+int linearize_rows_dev(Slot* s, hipStream_t st, const PlonkPK* P, const Fr* l, const Fr* r, const Fr* o, const Fr* z, size_t in_stride, const Fr* h,
+                       size_t h_stride, size_t rows, const Fr* d_alpha, const Fr* d_beta, const Fr* d_gamma, const Fr* d_zeta, Fr* values, Fr* zquot, Fr* lin,
+                       Fr* fh, size_t out_stride) {
     const size_t n = P->n;
     OpenWs W;
     ZK_TRY(open_ws_take(s, n + 3, rows, 6, LIN_PT, 0, &W));
@@ -1487,8 +1445,8 @@ static int linearize_rows_dev(Slot* s, hipStream_t st, const PlonkPK* P, const F
     return ZK_OK;
 }
 // round 5's polynomial (zk_bn254_plonk_open_batch_dev)
-static int open_rows_dev(Slot* s, hipStream_t st, const PlonkPK* P, const Fr* fh, const Fr* lin, const Fr* l, const Fr* r, const Fr* o, size_t in_stride, size_t rows,
-                         const Fr* d_zeta, const Fr* d_kg, Fr* q, size_t out_stride, Fr* value) {
+int open_rows_dev(Slot* s, hipStream_t st, const PlonkPK* P, const Fr* fh, const Fr* lin, const Fr* l, const Fr* r, const Fr* o, size_t in_stride, size_t rows,
+                  const Fr* d_zeta, const Fr* d_kg, Fr* q, size_t out_stride, Fr* value) {
     const size_t n = P->n;
     OpenWs W;
     ZK_TRY(open_ws_take(s, n + 3, rows, 1, 3, n + 3, &W));
@@ -1504,6 +1462,17 @@ static int open_rows_dev(Slot* s, hipStream_t st, const PlonkPK* P, const Fr* fh
         H.carry_poly = 0; H.q = q + first * out_stride; H.qstride = out_stride;
         ZK_TRY(hscan_dev_passes(s, st, H, R));
     }
+    return ZK_OK;
+}
+
+// a key that is not being freed, kept alive by `alive` (zk_bn254_plonk_quotient_batch_dev says why the shared lock is granted at once)
+int live_key(uint64_t handle, PlonkPK** P, std::shared_ptr<std::shared_mutex>* live, std::shared_lock<std::shared_mutex>* alive) {
+    std::lock_guard<std::mutex> lk(g_ppk_mu);
+    auto it = g_ppks.find(handle);
+    if (it == g_ppks.end()) return set_err(ZK_ERR_HANDLE, "unknown PLONK proving-key handle %llu", (unsigned long long)handle);
+    *P = it->second;
+    *live = (*P)->live;
+    *alive = std::shared_lock<std::shared_mutex>(**live);
     return ZK_OK;
 }
 
@@ -2534,17 +2503,6 @@ int zk_bn254_fr_poly_open_rows_dev(const void* d_f, size_t in_stride, size_t len
     hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
     ZK_TRY(poly_open_rows_dev(g.s, st, (const Fr*)d_f, in_stride, len, rows, (const Fr*)d_points, (Fr*)d_q, q_stride, (Fr*)d_values));
     return slot_sync(g.s, st);  // the workspace lives in the slot's arena
-}
-
-// a key that is not being freed, kept alive by `alive` (zk_bn254_plonk_quotient_batch_dev says why the shared lock is granted at once)
-static int live_key(uint64_t handle, PlonkPK** P, std::shared_ptr<std::shared_mutex>* live, std::shared_lock<std::shared_mutex>* alive) {
-    std::lock_guard<std::mutex> lk(g_ppk_mu);
-    auto it = g_ppks.find(handle);
-    if (it == g_ppks.end()) return set_err(ZK_ERR_HANDLE, "unknown PLONK proving-key handle %llu", (unsigned long long)handle);
-    *P = it->second;
-    *live = (*P)->live;
-    *alive = std::shared_lock<std::shared_mutex>(**live);
-    return ZK_OK;
 }
 
 int zk_bn254_plonk_linearize_batch_dev(uint64_t handle, const void* d_l, const void* d_r, const void* d_o, const void* d_z, size_t in_stride, const void* d_h,

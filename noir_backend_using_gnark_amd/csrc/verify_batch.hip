@@ -18,6 +18,7 @@
 
 #include "ctx.hpp"
 #include "curve.hpp"
+#include "fs_dev.hpp"
 #include "host_ff.hpp"
 #include "keyio.hpp"
 #include "pairing.hpp"
@@ -202,24 +203,6 @@ ZK_D Fr fr_from_be_words(const uint32_t* p) {
 #pragma unroll
     for (int k = 0; k < 4; k++) r = Fr::reduce_once(r.l);  // 2^256 < 6 r
     return r.to_mont();
-}
-// a digest as fr.SetBytes reads it
-ZK_D Fr fr_from_digest(const uint32_t d[8]) {
-    uint32_t t[8];
-    sha_words_to_limbs(d, t);
-    Fr r = Fr::reduce_once(t);
-#pragma unroll
-    for (int k = 0; k < 4; k++) r = Fr::reduce_once(r.l);
-    return r.to_mont();
-}
-// one 32-byte half of G1Affine.RawBytes() (X || Y big-endian; infinity = 0x40 then zeros) as limbs
-ZK_D void raw_half(const Affine<Fp>& p, int half, uint32_t l[8]) {
-    Fp c = p.x;
-    if (half) c = p.y;
-    c = c.from_mont();
-#pragma unroll
-    for (int k = 0; k < 8; k++) l[k] = c.l[k];
-    if (!half && p.is_inf()) l[7] = 0x40000000u;
 }
 
 // header (bytes 256..259 = 00 00 00 07), the nine compressed points into their own arrays, the eight values reduced mod r

@@ -191,6 +191,111 @@ def prove(pk: ProvingKey, solution, blinders, challenges=None) -> bytes:
     return bytes(out)
 
 
+# ---- many witnesses against one key in one call, the proofs assembled on the device (zk_bn254_plonk_prove_batch; include/zkmi.h says the rest)
+def _batch_rows(name, a, width):
+    """a (rows, width, 4) uint64 array of Montgomery images, or ValueError"""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if a.ndim != 3 or a.shape[1:] != (width, 4):
+        raise ValueError("%s has shape %s, not (rows, %d, 4)" % (name, a.shape, width))
+    return a
+
+
+def prove_batch(pk: ProvingKey, solutions, blinders, challenges=None, *, on_device: bool = False, chunk_rows: int = 0) -> list:
+    """plonk.Prove for every row of `solutions` against one key in one device call -> a list of Proof.WriteTo bytes (548 each), None where the row's solution
+    does not satisfy the circuit (which fails neither the call nor the other rows).  Row v is byte for byte prove(pk, solutions[v], blinders[v], challenges[v]).
+    solutions: (rows, n_vars, 4) Montgomery values, public inputs first -- a numpy array, or with on_device a DeviceBuffer / device pointer of rows * n_vars
+    contiguous elements; blinders: (rows, 9, 4); challenges: None (Fiat-Shamir as upstream) or (rows, 5, 4) = gamma, beta, alpha, zeta, kzg gamma of each row;
+    chunk_rows: 0, or a cap on the rows per chunk (it never changes a byte).  Shapes are checked before the library is called."""
+    bl = _batch_rows("blinders", blinders, 9)
+    rows = bl.shape[0]
+    ch = None if challenges is None else _batch_rows("challenges", challenges, 5)
+    if ch is not None and ch.shape[0] != rows:
+        raise ValueError("challenges has %d rows, blinders %d" % (ch.shape[0], rows))
+    if int(chunk_rows) < 0:
+        raise ValueError("chunk_rows must not be negative")
+    if on_device:
+        if not isinstance(solutions, _DEV):
+            raise TypeError("with on_device, solutions is a device buffer or a device pointer")
+        if isinstance(solutions, _lib.DeviceBuffer) and rows * pk.n_vars * 32 > solutions.nbytes:
+            raise ValueError("solutions: %d rows of %d variables do not fit the device buffer (%d bytes)" % (rows, pk.n_vars, solutions.nbytes))
+        ptr = C.c_void_p(_ptr(solutions))
+    else:
+        sol = _batch_rows("solutions", solutions, pk.n_vars)
+        if sol.shape[0] != rows:
+            raise ValueError("solutions has %d rows, blinders %d" % (sol.shape[0], rows))
+        ptr = vp(sol)
+    if rows == 0:
+        return []
+    out = np.zeros((rows, PROOF_BYTES), dtype=np.uint8)
+    status = np.zeros(rows, dtype=np.int32)
+    rc = lib().zk_bn254_plonk_prove_batch(pk.handle, ptr, C.c_size_t(pk.n_vars), C.c_size_t(pk.n_vars), C.c_size_t(rows), C.c_int(int(bool(on_device))), vp(bl),
+                                          vp(ch) if ch is not None else None, C.c_size_t(int(chunk_rows)), vp(out), vp(status))
+    if rc == _lib.ZK_ERR_LEN:
+        raise ValueError((lib().zk_last_error() or b"").decode())
+    check(rc)
+    return [None if status[v] else out[v].tobytes() for v in range(rows)]
+
+
+def prove_batch_info(pk: ProvingKey) -> dict:
+    """zk_bn254_plonk_prove_batch_info: {"chunk_rows": rows per chunk of prove_batch with device-resident solutions, "commits_batched": whether the row MSM's
+    batched path serves the key's SRS, "lin_by_linearity": whether the linearised polynomial's digest is taken from the key's digests instead of an MSM}"""
+    chunk, batched, lin = C.c_size_t(0), C.c_int(0), C.c_int(0)
+    check(lib().zk_bn254_plonk_prove_batch_info(pk.handle, C.byref(chunk), C.byref(batched), C.byref(lin)))
+    return {"chunk_rows": int(chunk.value), "commits_batched": bool(batched.value), "lin_by_linearity": int(lin.value)}
+
+
+_STAGE_POINTS = (3, 0, 1, 3, 5)
+
+
+def challenges_rows(pk: ProvingKey, stage: int, *, public=None, points=None, prev=None, values=None):
+    """One challenge of the prover's transcript for every row, on the device (zk_bn254_plonk_challenges_batch_dev) -> (challenges (rows, 4) uint64 Montgomery,
+    raw (rows, 32) uint8: the digests the next stage binds as `prev`).  stage 0 gamma: public (rows, n_public, 4), points (rows, 3, 8) = [L], [R], [O] as affine
+    Montgomery images, (0, 0) = infinity; 1 beta: prev; 2 alpha: prev, points (rows, 1, 8) = [Z]; 3 zeta: prev, points (rows, 3, 8) = [H0], [H1], [H2];
+    4 kzg's folding gamma: prev = zeta (rows, 4), points (rows, 5, 8) = [foldedH], [lin], [L], [R], [O], values (rows, 8, 4) of which the first seven are bound.
+    Every shape is checked before the library is called."""
+    stage = int(stage)
+    if stage not in range(5):
+        raise ValueError("stage %d is not one of the five challenges 0 .. 4" % stage)
+    arrays, rows = [], None
+
+    def take(name, a, dtype, shape):
+        nonlocal rows
+        if a is None:
+            raise ValueError("stage %d needs %s" % (stage, name))
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.ndim != len(shape) + 1 or a.shape[1:] != shape:
+            raise ValueError("%s has shape %s, not (rows,%s)" % (name, a.shape, "".join(" %d," % k for k in shape)))
+        if rows is not None and a.shape[0] != rows:
+            raise ValueError("%s has %d rows, not %d" % (name, a.shape[0], rows))
+        rows = a.shape[0]
+        arrays.append(a)
+        return a
+
+    npub = pk.n_public
+    pub = take("public", public, np.uint64, (npub, 4)) if stage == 0 and npub else None  # a key without public inputs binds none
+    pts = take("points", points, np.uint64, (_STAGE_POINTS[stage], 8)) if stage != 1 else None
+    prv = None
+    if stage in (1, 2, 3):
+        prv = take("prev", prev, np.uint8, (32,))
+    elif stage == 4:
+        prv = take("prev", prev, np.uint64, (4,))
+    val = take("values", values, np.uint64, (8, 4)) if stage == 4 else None
+    if rows == 0:
+        return np.zeros((0, 4), np.uint64), np.zeros((0, 32), np.uint8)
+    bufs = {k: _lib.DeviceBuffer.from_numpy(a) for k, a in (("pub", pub), ("pts", pts), ("prev", prv), ("val", val)) if a is not None}
+    out = _lib.DeviceBuffer(2 * rows * 32)
+    p = lambda k: C.c_void_p(bufs[k].ptr if k in bufs else 0)
+    try:
+        check(lib().zk_bn254_plonk_challenges_batch_dev(pk.handle, C.c_int(stage), C.c_size_t(rows), p("pub"), C.c_size_t(npub), p("pts"), p("prev"), p("val"),
+                                                        C.c_void_p(out.ptr), C.c_void_p(0)))
+        both = out.to_numpy(np.uint8, (2 * rows, 32))
+        return np.ascontiguousarray(both[:rows]).view(np.uint64).reshape(rows, 4), np.ascontiguousarray(both[rows:])
+    finally:
+        out.free()
+        for b in bufs.values():
+            b.free()
+
+
 # ---- round 2 for many witnesses: iop.BuildRatioCopyConstraint with the row as a grid dimension (zk_bn254_iop_ratio_copy_batch[_dev], zk_bn254_plonk_ratio_batch_dev)
 _DEV = (int, _lib.DeviceBuffer)
 
