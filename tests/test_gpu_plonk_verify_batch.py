@@ -190,6 +190,42 @@ def test_mixed_batch_matches_the_host(keys):
     assert (zv.plonk_verify_batch(proofs, key.vk, key.g2, pubs) == got).all()
 
 
+POINT_SLOTS = [("L", 0), ("R", 32), ("O", 64), ("Z", 96), ("H0", 128), ("H1", 160), ("H2", 192), ("BatchH", 224), ("ZShiftH", 484)]
+
+
+def test_every_point_slot_with_every_refused_encoding(keys):
+    """every refused G1 encoding of the codec tables, the point at infinity and four other points, in each of the nine point slots, untouched proofs
+    between them.  A refused encoding gives 0 whatever else holds (the reference decoder says so, not the host verifier); the rest gets the host's verdict"""
+    from tests import codec_edges as ce
+    key = keys[1]
+    base, bpubs = key.proofs(8)
+    vectors = [(lab, b, kind) for lab, b, kind in ce.g1_decompress_vectors() if kind in ("invalid", "inf")]
+    vectors += [v for v in ce.g1_decompress_vectors() if v[2] == "valid"][3:42:11]
+    assert sum(kind == "invalid" for _, _, kind in vectors) >= 59 and sum(kind == "valid" for _, _, kind in vectors) == 4
+    for _, b, kind in vectors:
+        if kind == "invalid":
+            with pytest.raises(ValueError):
+                pl.g1_decompress(b)
+    ps, ws, labels, kinds = [], [], [], []
+    for slot, off in POINT_SLOTS:
+        for lab, b, kind in vectors:
+            j = len(ps) % 8
+            if len(ps) % 5 == 0:
+                ps.append(base[j]), ws.append(bpubs[j]), labels.append("untouched"), kinds.append("untouched")
+            ps.append(_with(base[j], off, b)), ws.append(bpubs[j]), labels.append("%s <- %s" % (slot, lab)), kinds.append(kind)
+    ws = np.stack(ws)
+    want = _host(ps, key.vk, key.g2, ws)
+    got, prof = _batch(ps, key.vk, key.g2, ws)
+    assert "pv_single" in prof
+    for i, (lab, kind) in enumerate(zip(labels, kinds)):
+        if kind == "untouched":
+            assert got[i] and want[i], (i, lab)
+        elif kind == "invalid":
+            assert not got[i], (i, lab)
+        assert got[i] == want[i], (i, lab, kind)
+    assert (zv.plonk_verify_batch(ps, key.vk, key.g2, ws) == got).all()
+
+
 def test_coefficients_are_independent(keys):
     """ZShiftH + P in one copy of a proof and ZShiftH - P in another: no transcript binds that point, so equal coefficients would cancel the errors"""
     key = keys[1]

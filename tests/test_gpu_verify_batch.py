@@ -45,6 +45,30 @@ def test_device_pairing_equals_host_value(n):
     assert (dev == zv.pair(P, Q, on_device=False)).all()
 
 
+@pytest.fixture(scope="module")
+def tile_of_eight():
+    """eight pairs (a_i G, b_i H) with a = 0, b = 0, a = r - 1 and the generators among them, and the host's e(a_i b_i G, H) per pair's worth"""
+    g = ref.SplitMix64(0x7113)
+    ka = [1, 0, g.felt(), ref.R - 1, g.felt(), g.felt(), g.felt(), g.felt()]
+    kb = [1, g.felt(), 0, g.felt(), ref.R - 1, g.felt(), g.felt(), g.felt()]
+    return ka, kb, g1_points_from_scalars(ka), g2_points_from_scalars(kb)
+
+
+@pytest.mark.parametrize("n", [65, 128, 129, 257, 1 << 16, (1 << 16) + 1])
+def test_device_pairing_beyond_one_workgroup_and_one_chunk(n, tile_of_eight):
+    """a second workgroup of k_miller (64 lanes each), odd levels of the product tree, and past 2^16 pairs the chunk products multiplied on the host:
+    prod e(a_i G, b_i H) = e(s G, H), s = sum a_i b_i mod r, by bilinearity -- the host's value of that one pair (test_pair_cpu.py pins it to the oracle)"""
+    ka, kb, P8, Q8 = tile_of_eight
+    idx = np.arange(n) % 8
+    s = sum(ka[i] * kb[i] for i in idx[:8]) * (n // 8) + sum(ka[i] * kb[i] for i in idx[:n % 8])
+    want = zv.pair(g1_points_from_scalars([s % ref.R]), g2_points_from_scalars([1]), on_device=False)
+    P, Q = P8[idx], Q8[idx]
+    dev = zv.pair(P, Q)
+    assert (dev == want).all()
+    if n <= 257:
+        assert (zv.pair(P, Q, on_device=False) == want).all()
+
+
 def test_device_pairing_bilinearity():
     a, b = 0x1234567, 0x7654321
     lhs = zv.pair(g1_points_from_scalars([a]), g2_points_from_scalars([b]))
