@@ -328,6 +328,11 @@ int zk_bn254_r1cs_load(const zk_r1cs *r1cs, uint64_t *handle);
 int zk_bn254_r1cs_free(uint64_t handle);
 /* a = L w, b = R w, c = O w: what r1cs.Solve leaves for a system without hints (one lane per matrix row); device pointers. */
 int zk_bn254_r1cs_eval_abc_dev(uint64_t handle, const void *d_w, size_t n_wires, void *d_a, void *d_b, void *d_c, void *stream);
+/* The same for `rows` wire vectors in ONE launch -- the launch zk_bn254_groth16_prove_r1cs_batch makes for a step of its rows.  d_w: rows x n_wires elements,
+ * row-major (row z at d_w + z * n_wires), only read; d_a, d_b, d_c: rows x n_constraints elements each, row z at offset z * n_constraints, every element
+ * written and nothing beyond.  Device pointers, all Montgomery fr.Element.  rows == 0: ZK_OK, nothing touched.  At most 65535 rows per call (the row is a grid
+ * dimension): more is ZK_ERR_ARG and nothing is written.  Other errors as above: ZK_ERR_ARG null pointer, ZK_ERR_HANDLE, ZK_ERR_LEN n_wires. */
+int zk_bn254_r1cs_eval_abc_rows_dev(uint64_t handle, const void *d_w, size_t n_wires, size_t rows, void *d_a, void *d_b, void *d_c, void *stream);
 /* groth16.Setup with the toxic waste (tau, alpha, beta, gamma, delta; Montgomery, non-zero) as INPUT -- upstream draws it; pinning it is what
  * makes a key reproducible.  The key is built in HBM (Lagrange basis at tau, transposed products, fixed-base scalar multiplications) and comes
  * back as a resident proving key; vk_g1 (1 + n_public points: [alpha]G1, then K_i / gamma) and vk_g2 ([beta]G2, [gamma]G2, [delta]G2) on

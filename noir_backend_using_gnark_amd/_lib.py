@@ -115,7 +115,7 @@ SYMBOLS = [
     "zk_bn254_groth16_pk_read", "zk_bn254_groth16_pk_write", "zk_bn254_groth16_vk_write",
     "zk_bn254_groth16_verify", "zk_bn254_plonk_verify", "zk_bn254_pairing_check",
     "zk_bn254_pair", "zk_bn254_pair_host", "zk_bn254_groth16_verify_batch", "zk_bn254_plonk_verify_batch",
-    "zk_bn254_r1cs_load", "zk_bn254_r1cs_free", "zk_bn254_r1cs_eval_abc_dev", "zk_bn254_groth16_setup", "zk_bn254_groth16_prove_r1cs",
+    "zk_bn254_r1cs_load", "zk_bn254_r1cs_free", "zk_bn254_r1cs_eval_abc_dev", "zk_bn254_r1cs_eval_abc_rows_dev", "zk_bn254_groth16_setup", "zk_bn254_groth16_prove_r1cs",
     "zk_bn254_groth16_prove_batch", "zk_bn254_groth16_prove_r1cs_batch", "zk_bn254_groth16_batch_info",
     "zk_bn254_groth16_msm5_dev", "zk_bn254_groth16_msm5_pk", "zk_bn254_groth16_msm5_pk_begin", "zk_bn254_groth16_msm5_pk_end", "zk_bn254_groth16_msm5_pk_abort", "zk_bn254_groth16_msm5_session_stream", "zk_bn254_groth16_finalize",
     "zk_bn254_groth16_finalize_batch", "zk_bn254_groth16_finalize_batch_dev",

@@ -371,6 +371,23 @@ int zk_bn254_r1cs_eval_abc_dev(uint64_t handle, const void* d_w, size_t n_wires,
     return ZK_OK;
 }
 
+// The same for `rows` wire vectors in the one launch the batch prover makes (r1cs_eval_abc_rows with out_stride = n_constraints): row z reads
+// d_w + z * n_wires and writes n_constraints elements at d_a / d_b / d_c + z * n_constraints.  For callers that hold many witnesses in HBM, and for the tests.
+int zk_bn254_r1cs_eval_abc_rows_dev(uint64_t handle, const void* d_w, size_t n_wires, size_t rows, void* d_a, void* d_b, void* d_c, void* stream) {
+    if (rows == 0) return ZK_OK;
+    if (!d_w || !d_a || !d_b || !d_c) return set_err(ZK_ERR_ARG, "null pointer");
+    ZK_ON_ENTRY_OF(handle);
+    std::shared_ptr<R1csDev> Dref;  // keeps the matrices alive until the launch below has been waited for
+    ZK_TRY(lookup_r1cs(handle, &Dref));
+    if (n_wires != Dref->n_wires) return set_err(ZK_ERR_LEN, "len(w) = %zu != %zu wires of the constraint system", n_wires, Dref->n_wires);
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    ZK_TRY(r1cs_eval_abc_rows(handle, g.s, st, (const Fr*)d_w, rows, Dref->n_constraints, (Fr*)d_a, (Fr*)d_b, (Fr*)d_c));
+    if (!stream || profiling_on()) ZK_TRY(slot_sync(g.s, st));
+    return ZK_OK;
+}
+
 // groth16.Setup with the toxic waste as input: tau, alpha, beta, gamma, delta (Montgomery fr.Elements, all non-zero).  The proving key is
 // built in HBM and loaded as a resident key (*pk_handle, usable with zk_bn254_groth16_prove); the verifying key comes back to the host:
 // vk_g1 = [alpha]G1 followed by the n_public points K_i / gamma (gnark's vk.G1.K), vk_g2 = [beta]G2, [gamma]G2, [delta]G2.

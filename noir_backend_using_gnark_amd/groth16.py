@@ -223,6 +223,35 @@ class R1CS:
         check(rc)
         return tuple(o.to_numpy(np.uint64, (self.n_constraints, 4)) for o in out)
 
+    def eval_abc_rows(self, w, on_device: bool = False, rows: int | None = None, out=None) -> tuple:
+        """eval_abc of every row of w (rows, n_wires, 4) in ONE launch -- the launch prove_r1cs_batch makes (zk_bn254_r1cs_eval_abc_rows_dev) -> a, b, c, each
+        (rows, n_constraints, 4) numpy.  on_device=True: w is a DeviceBuffer of `rows` rows of this system's n_wires elements, only read.  out: three
+        DeviceBuffers of at least rows x n_constraints elements to write into (theirs otherwise); the arrays returned are read back from them."""
+        if on_device:
+            if not isinstance(w, _lib.DeviceBuffer):
+                raise TypeError("on_device=True takes a DeviceBuffer of rows")
+            if rows is None:
+                raise ValueError("a device buffer carries no shape: rows is needed")
+            n, n_wires, dw = int(rows), self.n_wires, w
+            if n < 0 or n * n_wires * 32 > w.nbytes:
+                raise ValueError("%d rows of %d wires do not fit the buffer's %d bytes" % (n, n_wires, w.nbytes))
+        else:
+            w = _rows(w, "w")
+            n, n_wires = w.shape[0], w.shape[1]
+            if rows is not None and rows != n:
+                raise ValueError("rows = %d, w has %d" % (rows, n))
+            dw = _lib.DeviceBuffer.from_numpy(w)
+        need = n * self.n_constraints * 32
+        if out is None:
+            out = [_lib.DeviceBuffer(max(need, 32)) for _ in range(3)]
+        elif len(out) != 3 or not all(isinstance(o, _lib.DeviceBuffer) and o.nbytes >= need for o in out):
+            raise ValueError("out must be three DeviceBuffers of at least %d bytes" % need)
+        rc = lib().zk_bn254_r1cs_eval_abc_rows_dev(self.handle, C.c_void_p(dw.ptr), C.c_size_t(n_wires), C.c_size_t(n), *[C.c_void_p(o.ptr) for o in out], None)
+        if rc == _lib.ZK_ERR_LEN:
+            raise ValueError((lib().zk_last_error() or b"").decode())
+        check(rc)
+        return tuple(o.to_numpy(np.uint64, (n, self.n_constraints, 4)) for o in out)
+
     def free(self):
         if self.handle.value:
             check(lib().zk_bn254_r1cs_free(self.handle))
@@ -331,13 +360,25 @@ def finalize_batch(pk: ProvingKey, partials, r, s) -> list:
     return [raw[128 * i:128 * i + 128] for i in range(n)]
 
 
-def prove_r1cs_batch(r1cs: R1CS, pk: ProvingKey, w, r, s) -> list:
-    """groth16.Prove(r1cs, pk, witness) for many witnesses: w (rows, n_wires, 4) -> one proof per row, each what prove_r1cs() returns for it."""
-    w = _rows(w, "w")
-    r, s = _rs_rows(r, s, w.shape[0])
-    n = w.shape[0]
+def prove_r1cs_batch(r1cs: R1CS, pk: ProvingKey, w, r, s, on_device: bool = False) -> list:
+    """groth16.Prove(r1cs, pk, witness) for many witnesses: w (rows, n_wires, 4) -> one proof per row, each what prove_r1cs() returns for it.
+    on_device=True: w is a DeviceBuffer of row-major rows already in HBM, the constraint system's wire count wide and only read; the row count comes from r."""
+    if on_device:
+        if not isinstance(w, _lib.DeviceBuffer):
+            raise TypeError("on_device=True takes a DeviceBuffer of rows")
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        r, s = _rs_rows(r, s, r.shape[0])
+        n, n_wires, wp = r.shape[0], r1cs.n_wires, C.c_void_p(w.ptr)
+        if n * n_wires * 32 > w.nbytes:
+            raise ValueError("%d rows of %d wires do not fit the buffer's %d bytes" % (n, n_wires, w.nbytes))
+    else:
+        if isinstance(w, _lib.DeviceBuffer):
+            raise TypeError("a DeviceBuffer of rows needs on_device=True")
+        w = _rows(w, "w")
+        r, s = _rs_rows(r, s, w.shape[0])
+        n, n_wires, wp = w.shape[0], w.shape[1], vp(w)
     proofs = (C.c_uint8 * (128 * max(n, 1)))()
-    rc = lib().zk_bn254_groth16_prove_r1cs_batch(r1cs.handle, pk.handle, vp(w), C.c_size_t(w.shape[1]), vp(r), vp(s), C.c_size_t(n), C.c_int(0), proofs)
+    rc = lib().zk_bn254_groth16_prove_r1cs_batch(r1cs.handle, pk.handle, wp, C.c_size_t(n_wires), vp(r), vp(s), C.c_size_t(n), C.c_int(int(on_device)), proofs)
     if rc == _lib.ZK_ERR_LEN:
         raise ValueError((lib().zk_last_error() or b"").decode())
     check(rc)

@@ -12,7 +12,7 @@ from noir_backend_using_gnark_amd import _lib
 from noir_backend_using_gnark_amd import groth16 as zk
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BATCH = ("zk_bn254_groth16_prove_batch", "zk_bn254_groth16_prove_r1cs_batch", "zk_bn254_groth16_batch_info")
+BATCH = ("zk_bn254_groth16_prove_batch", "zk_bn254_groth16_prove_r1cs_batch", "zk_bn254_groth16_batch_info", "zk_bn254_r1cs_eval_abc_rows_dev")
 BOGUS = C.c_uint64(0x00ffffffffffff)  # no such handle
 
 
@@ -105,3 +105,79 @@ def test_wrappers_refuse_ragged_shapes_before_any_c_call():
         zk.prove_r1cs_batch(r1, pk, w[0], r, s)
     with pytest.raises(ValueError):
         zk.prove_batch(pk, 1, 2, 3, 4, r, s, on_device=True)  # device matrices need n_constraints
+
+
+# ---- the row-batched R1CS step on its own (zk_bn254_r1cs_eval_abc_rows_dev) and the device-pointer form of prove_r1cs_batch
+def _fake_buffer(nbytes):
+    """a DeviceBuffer that owns nothing (no device here): an address no call may reach, forgotten before the object goes"""
+    b = _lib.DeviceBuffer.__new__(_lib.DeviceBuffer)
+    b.ptr, b.nbytes = 0, nbytes
+    return b
+
+
+def test_eval_abc_rows_argument_errors_before_the_device():
+    lib = _lib.lib()
+    fn = lib.zk_bn254_r1cs_eval_abc_rows_dev
+    w, a, b, c = (np.zeros((2, 5, 4), np.uint64) for _ in range(4))  # stand-ins for device addresses: no call below gets as far as reading them
+    vp, nw = _lib.vp, C.c_size_t(5)
+    assert fn(BOGUS, None, nw, C.c_size_t(0), None, None, None, None) == _lib.ZK_OK  # no rows: nothing to do, whatever the rest is
+    for hole in range(4):
+        ptrs = [vp(w), vp(a), vp(b), vp(c)]
+        ptrs[hole] = None
+        assert fn(BOGUS, ptrs[0], nw, C.c_size_t(2), ptrs[1], ptrs[2], ptrs[3], None) == _lib.ZK_ERR_ARG, hole
+        assert b"null pointer" in lib.zk_last_error()
+    no_dev = _lib.device_count() <= 0
+    for rows in (2, 65536):  # the handle is looked up before the row limit
+        assert fn(BOGUS, vp(w), nw, C.c_size_t(rows), vp(a), vp(b), vp(c), None) == (_lib.ZK_ERR_NO_DEVICE if no_dev else _lib.ZK_ERR_HANDLE)
+        if not no_dev:
+            assert b"unknown R1CS handle" in lib.zk_last_error()
+
+
+def test_eval_abc_rows_wrapper_refuses_bad_shapes_before_any_c_call():
+    r1 = zk.R1CS.from_handle(BOGUS.value, 1, 5, 3)
+    w = np.zeros((2, 5, 4), np.uint64)
+    with pytest.raises(ValueError):
+        r1.eval_abc_rows(w[0])                               # one vector is eval_abc's argument
+    with pytest.raises(ValueError):
+        r1.eval_abc_rows(w[:, :, :3])                        # not limbs
+    with pytest.raises(ValueError):
+        r1.eval_abc_rows(w, rows=3)                          # rows contradicts the array
+    with pytest.raises(TypeError):
+        r1.eval_abc_rows(w, on_device=True, rows=2)          # host rows are not a device buffer
+    with pytest.raises(ValueError):
+        r1.eval_abc_rows(_fake_buffer(320), on_device=True)  # a device buffer carries no shape
+    with pytest.raises(ValueError):
+        r1.eval_abc_rows(_fake_buffer(319), on_device=True, rows=2)  # 2 rows of 5 wires are 320 bytes
+    with pytest.raises(ValueError):
+        r1.eval_abc_rows(_fake_buffer(320), on_device=True, rows=2, out=[_fake_buffer(192)] * 2)          # three outputs
+    with pytest.raises(ValueError):
+        r1.eval_abc_rows(_fake_buffer(320), on_device=True, rows=2, out=[_fake_buffer(192)] * 2 + [_fake_buffer(191)])  # 2 rows of 3 constraints are 192 bytes
+
+
+def test_prove_r1cs_batch_on_device_argument_validation():
+    pk = zk.ProvingKey.from_handle(BOGUS.value, 2, 5, 1)
+    r1 = zk.R1CS.from_handle(BOGUS.value, 1, 5, 3)
+    _, _, _, w, r, s, _ = _args()
+    with pytest.raises(TypeError):
+        zk.prove_r1cs_batch(r1, pk, w, r, s, on_device=True)           # host rows are not a device buffer
+    with pytest.raises(TypeError):
+        zk.prove_r1cs_batch(r1, pk, _fake_buffer(320), r, s)           # and a device buffer is not host rows
+    with pytest.raises(TypeError):
+        zk.prove_r1cs_batch(r1, pk, 12345, r, s, on_device=True)       # a bare address carries no size to check
+    with pytest.raises(ValueError):
+        zk.prove_r1cs_batch(r1, pk, _fake_buffer(320), r, s[:1], on_device=True)   # the row count comes from r: one s for two rows
+    with pytest.raises(ValueError):
+        zk.prove_r1cs_batch(r1, pk, _fake_buffer(320), r[:, :3], s, on_device=True)  # not limbs
+    with pytest.raises(ValueError):
+        zk.prove_r1cs_batch(r1, pk, _fake_buffer(319), r, s, on_device=True)       # 2 rows of 5 wires are 320 bytes
+    empty = np.zeros((0, 4), np.uint64)
+    assert zk.prove_r1cs_batch(r1, pk, _fake_buffer(0), empty, empty, on_device=True) == []
+    # a well-formed call reaches the library with on_device = 1: no device here, or no such handle there
+    buf = _fake_buffer(320)
+    buf.ptr = w.ctypes.data  # never read: the handles are looked up first
+    try:
+        with pytest.raises(_lib.ZkmiError) as ei:
+            zk.prove_r1cs_batch(r1, pk, buf, r, s, on_device=True)
+        assert ei.value.code == (_lib.ZK_ERR_NO_DEVICE if _lib.device_count() <= 0 else _lib.ZK_ERR_HANDLE)
+    finally:
+        buf.ptr = 0
