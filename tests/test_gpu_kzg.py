@@ -1,6 +1,7 @@
 """KZG openings on the device against the oracle (oracle/plonk_ref.py: poly_eval, divide_by_x_minus_a, kzg_derive_gamma; oracle/oracle.py: g1_msm for the
 commitment), bit for bit: SRS.open / open_many / batch_open_single_point; the golden PLONK proofs' BatchedProof and ZShiftedOpening rebuilt through them;
-kzg.batch_verify_multi_points (zk_bn254_kzg_verify_batch) against the host zk_bn254_kzg_verify, which tests/test_kzg_cpu.py pins to the oracle."""
+kzg.batch_verify_multi_points (zk_bn254_kzg_verify_batch) against the host zk_bn254_kzg_verify, which tests/test_kzg_cpu.py pins to the oracle, and against
+openings forged under a known SRS secret (tests/plonk_forge.py): edge values and points, points at infinity, errors that cancel under equal coefficients."""
 import json
 import os
 import random
@@ -278,3 +279,51 @@ def test_verify_batch_bad_openings_get_the_host_verdicts():
     idx = [1, 2, 10, 3]
     got, _ = _run(D[idx], H[idx], V[idx], Z[idx], g2)
     assert got.tolist() == [1, 1, 0, 1]
+
+
+# ---- zk_bn254_kzg_verify_batch against openings forged under a known tau (tests/plonk_forge.py; tests/test_plonk_forge_cpu.py holds them against the host)
+def _forged(lanes):
+    from tests import plonk_forge as pf
+    D, H, V, Z, want, g2 = pf.kzg_arrays(lanes)
+    got, prof = _run(D, H, V, Z, g2)
+    wrong = ["lane %d of %d: %s: got %d, expected %d" % (i, len(lanes), l.label, got[i], l.expect) for i, l in enumerate(lanes) if got[i] != l.expect]
+    assert not wrong, wrong[:12]
+    # the combined check decided exactly when nothing is to be rejected: the fallback adds a Miller launch
+    assert prof["kzg_combine"][0] == 1 and prof["miller_loop"][0] == (1 if want.all() else 2), prof
+    return got
+
+
+def test_verify_batch_forged_accepts_at_the_edges():
+    """v and z among 0, 1, 2^192 - 1, 2^224, r - 1 and random; C, H and C - v G + z H at infinity; z = tau with c = v and any H"""
+    from tests import plonk_forge as pf
+    lanes = pf.kzg_accepts()
+    assert len(lanes) >= 31
+    assert _forged(lanes).all()
+    for l in lanes:
+        _forged([l])
+    for n in (2, 65):
+        for start in (0, 5, 24):
+            _forged([lanes[(start + j) % len(lanes)] for j in range(n)])
+
+
+def test_verify_batch_forged_rejects_and_cancelling_pairs():
+    """H off by a known multiple of G; two lanes whose errors cancel when lambda_1 == lambda_2: alone, 1 and 64 lanes apart, and in the middle of 1000 lanes"""
+    from tests import plonk_forge as pf
+    good, bad, pairs = pf.kzg_accepts(), pf.kzg_rejects(), pf.kzg_cancelling_pairs()
+    for l in bad:
+        _forged([l])
+        _forged([good[3], l])
+    for a, b in pairs:
+        _forged([a, b])
+        _forged([b, a])
+        fill = [good[j % len(good)] for j in range(65)]
+        for at_a, at_b in ((10, 11), (0, 64), (64, 0)):
+            lanes = list(fill)
+            lanes[at_a], lanes[at_b] = a, b
+            _forged(lanes)
+    lanes = [good[j % len(good)] for j in range(1000)]
+    assert _forged(lanes).all()
+    lanes[500:500 + len(bad)] = bad
+    (lanes[498], lanes[499]), (lanes[436], lanes[600]), (lanes[0], lanes[999]) = pairs
+    got = _forged(lanes)
+    assert got.sum() == 1000 - len(bad) - 6
