@@ -758,6 +758,52 @@ int zk_groth16_lower_resident(const char *raw_json, size_t raw_len, int to_devic
 int zk_groth16_key_resident(const char *pk_hex, size_t pk_len);
 int zk_groth16_public_inputs(const char *raw_json, size_t raw_len, zk_fr *out, size_t cap, size_t *n_public);
 
+/* MANY WITNESS-VALUE TEXTS OF ONE CIRCUIT PER CALL.  A caller of the export path holds the circuit text and one hex felt vector (encode_felts) per witness;
+ * zk_bn254_plonk_prove_batch / zk_bn254_groth16_prove_r1cs_batch take rows that are already lowered.  These entries are the step between: the texts of a chunk go
+ * up in one pitched copy, ONE launch decodes them (zk_bn254_felts_decode_hex_rows_dev), one or two assemble the rows -- HandleValues' variable order (duplicated
+ * secret variables included) for PLONK; [ONE, public, secret, one product per mul term] for Groth16 -- and the rows go to the batch prover as they lie in HBM.
+ *   values_hex     host: row v is the values_len characters at values_hex + v * values_stride.  Every row has the same length: for PLONK values_len = 8 + 64 *
+ *                  (the count in row 0's header) -- the n_values the circuit is lowered with, as in zk_plonk_prove_with_pk; for Groth16 the length of the values
+ *                  string the RawR1CS text was read with (ZK_ERR_LEN otherwise).
+ *   raw_json       the RawR1CS text: its own embedded values string only identifies the circuit (it must be plain hex) and is NOT a row.
+ *   status_out     host, one per row (the enum below).  A bad row fails neither the call nor its neighbours; its output row is defined: zeros where a felt was
+ *                  rejected (its proof: all '0').  For any status but ZK_ROW_OK the proof characters of the row are all '0'.
+ *   zk_plonk_solutions_rows / zk_groth16_wires_rows   the assembly alone: rows x n_vars (n_wires) Montgomery elements in device memory, row v at element
+ *                  v * sol_stride (wire_stride); the stride may be anything for one row and must hold a row otherwise (ZK_ERR_ARG).
+ *   zk_plonk_prove_batch_with_pk / zk_groth16_prove_batch_with_pk   for a row with status ZK_ROW_OK the 1096 (256) characters at proofs_hex_out + v * 1096 (256)
+ *                  are exactly what zk_plonk_prove_with_pk / zk_groth16_prove_with_pk writes for the same circuit, that row's values text, the same key and
+ *                  that row's blinders (nine) / (r, s).  blinders / rs == NULL: drawn from /dev/urandom, rows x 9 / rows x 2.  The key as in the single entries:
+ *                  a text found or made resident by its content key and pinned for the call, or a resident handle; its shape is checked against the circuit once
+ *                  per call.  A cached PLONK key's proof count advances by `rows` (the Lagrange form of its SRS is built before the batch that reaches the
+ *                  sixteenth); a cached Groth16 key that proves again gets its window tables in the background, and until it has them its rows run one by one
+ *                  inside zk_bn254_groth16_prove_r1cs_batch -- the same bytes.
+ *   CHUNKS         assembly, then the prover, per chunk of zk_bn254_plonk_prove_batch_info / zk_bn254_groth16_batch_info rows, capped by chunk_rows (0 = no cap;
+ *                  it never changes a byte): the call's staging -- texts, decoded values, rows -- never exceeds one chunk.  The staging is the call's own: the
+ *                  resident circuit's per-proof buffers are not touched and its mutex is held only while the circuit and the key are made resident, so a
+ *                  call overlaps a single proof on the same circuit.  No stream slot is held while another is acquired.
+ *   The PLONK batch is only faster than the loop of single calls where the batch prover is: on an SRS registered without a window table it is not
+ *   (zk_bn254_plonk_prove_batch_info's commits_batched = 0), and no table is built here.
+ * ARGUMENT ERRORS, decided before a device is looked for: a null pointer, values_stride < values_len with more than one row, neither pk_hex nor pk_handle ->
+ * ZK_ERR_ARG; values_len != 8 + 64 * (row 0's count) -> ZK_ERR_LEN; rows == 0 -> ZK_OK, nothing written. */
+enum {
+    ZK_ROW_OK = 0,            /* decoded (and, from the batch provers, proved) */
+    ZK_ROW_UNSATISFIED = 1,   /* the batch prover's verdict: the solution violates the circuit (PLONK only) */
+    ZK_ROW_BAD_HEX = 2,       /* invalid hex character in the row's felts */
+    ZK_ROW_NOT_CANONICAL = 3, /* a felt >= r */
+    ZK_ROW_BAD_COUNT = 4      /* the row's count header is not n_values */
+};
+int zk_plonk_solutions_rows(const char *acir_json, size_t acir_len, int layout, const char *values_hex, size_t values_len, size_t values_stride,
+                            size_t rows, void *d_solutions /* rows x n_vars, device */, size_t sol_stride, int *status_out /* rows, host */);
+int zk_groth16_wires_rows(const char *raw_json, size_t raw_len, const char *values_hex, size_t values_len, size_t values_stride,
+                          size_t rows, void *d_wires /* rows x n_wires, device */, size_t wire_stride, int *status_out /* rows, host */);
+int zk_plonk_prove_batch_with_pk(const char *acir_json, size_t acir_len, int layout, const char *values_hex, size_t values_len, size_t values_stride,
+                                 size_t rows, const char *pk_hex, size_t pk_len, uint64_t pk_handle, uint64_t srs_handle,
+                                 const zk_fr *blinders /* NULL or rows x 9 */, size_t chunk_rows /* 0 = automatic */,
+                                 char *proofs_hex_out /* rows x 1096 */, int *status_out /* rows */);
+int zk_groth16_prove_batch_with_pk(const char *raw_json, size_t raw_len, const char *values_hex, size_t values_len, size_t values_stride, size_t rows,
+                                   const char *pk_hex, size_t pk_len, uint64_t pk_handle, const zk_fr *rs /* NULL or rows x 2 */,
+                                   size_t chunk_rows, char *proofs_hex_out /* rows x 256 */, int *status_out /* rows */);
+
 /* What the MSM planner picks for n points (with / without resident window tables): window width c and the number of c-bit
  * digits per scalar, i.e. mixed additions per scalar multiplication -- used by bench.py to turn launches into work. */
 int zk_bn254_msm_plan_info(size_t n, int window_tables, uint32_t *window_bits, uint32_t *digits);
@@ -856,13 +902,24 @@ int zk_bn254_msm_tail_inspect(const zk_msm_tail_request *req, zk_msm_tail_result
  *   decode_hex      : hex on the host -> d_out (device, capacity `cap` felts); *n_out = count.
  *   decode_hex_dev  : the whole text already in HBM (d_text must sit 8 bytes before a 16-byte boundary; n = its count).
  *   decode_bytes_dev: raw fr.Vector.MarshalBinary bytes in HBM (d_raw 4 bytes before a 16-byte boundary).
- *   encode_hex      : Montgomery vector in HBM -> 8 + 64 n hex characters on the host (encode_felts), no terminator. */
+ *   encode_hex      : Montgomery vector in HBM -> 8 + 64 n hex characters on the host (encode_felts), no terminator.
+ *   decode_hex_rows_dev: `rows` texts of the same count n in ONE launch (the row is a grid dimension), everything in HBM.  d_text points at row 0's count
+ *                     header, 8 bytes before a 16-byte boundary; row z's text starts z * pitch bytes further (pitch: a multiple of 16, at least 8 + 64 n -- a
+ *                     contiguous host buffer does not give that: stage the rows with one pitched copy, e.g. to pitch 64 n + 16).  Row z's n elements go to
+ *                     d_out + z * out_stride (out_stride >= n elements; the gap is not written), its verdict to d_status[z]: 0, 1 = invalid hex character,
+ *                     2 = a felt >= r.  A bad row fails neither the call nor its neighbours, and every one of its n elements is still written: zero where the
+ *                     felt was rejected.  The count headers are the caller's to check (they are not read).  With `stream` the call only enqueues (the status
+ *                     words are cleared on that stream first) and the caller decides when to read them; stream == NULL runs on a stream of the library's and
+ *                     returns when the launch is complete.  At most 65,535 rows per call, more is ZK_ERR_ARG, as are a null pointer, a pitch or stride that
+ *                     does not hold a row and a misaligned d_text -- all decided before a device is looked for; rows == 0 or n == 0: ZK_OK, nothing launched. */
 int zk_bn254_felts_decode_hex(const char *hex, size_t hex_len, void *d_out, size_t cap, size_t *n_out);
 int zk_bn254_felts_decode_hex_dev(const void *d_text, size_t text_len, void *d_out, size_t cap, size_t n, int to_mont,
                                   void *stream);
 int zk_bn254_felts_decode_bytes_dev(const void *d_raw, size_t raw_len, void *d_out, size_t cap, size_t n, int to_mont,
                                     void *stream);
 int zk_bn254_felts_encode_hex(const void *d_in, size_t n, char *hex_out, size_t cap);
+int zk_bn254_felts_decode_hex_rows_dev(const void *d_text, size_t pitch, size_t rows, size_t n, void *d_out, size_t out_stride,
+                                       int to_mont, int *d_status /* rows */, void *stream);
 
 /* ---- synthetic data on the device (bench / tests; deterministic SplitMix64 streams) -------------- */
 int zk_bn254_fr_random_dev(void *d_out, size_t n, uint64_t seed, int mont, int witness_like, void *stream);

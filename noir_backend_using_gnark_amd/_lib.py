@@ -133,8 +133,21 @@ SYMBOLS = [
     "zk_export_set_new_srs_size", "zk_export_new_srs_size", "zk_warm_session_streams", "zk_warm_session_streams_background", "zk_background_wait", "zk_background_hold", "zk_background_set_yield_ms", "zk_bn254_bases_build_table_background",
     "zk_bn254_msm_bases_rows", "zk_bn254_msm_bases_rows_dev", "zk_bn254_msm_rows_info", "zk_bn254_plonk_commit_batch_dev",
     "zk_bn254_plonk_prove_batch", "zk_bn254_plonk_prove_batch_info", "zk_bn254_plonk_challenges_batch_dev",
+    "zk_bn254_felts_decode_hex_rows_dev", "zk_plonk_solutions_rows", "zk_groth16_wires_rows", "zk_plonk_prove_batch_with_pk", "zk_groth16_prove_batch_with_pk",
     "zk_bn254_kzg_open", "zk_bn254_kzg_batch_open_single_point", "zk_bn254_kzg_verify", "zk_bn254_kzg_fold_proof", "zk_bn254_kzg_batch_verify_single_point", "zk_bn254_kzg_verify_batch",
 ]
+
+# ctypes signatures of the row entries of the export path (the other entries are called with explicit ctypes values at every call site)
+_SZ, _VP, _CP = C.c_size_t, C.c_void_p, C.c_char_p
+ARGTYPES = {
+    "zk_bn254_felts_decode_hex_rows_dev": [_VP, _SZ, _SZ, _SZ, _VP, _SZ, C.c_int, _VP, _VP],
+    "zk_plonk_solutions_rows": [_CP, _SZ, C.c_int, _CP, _SZ, _SZ, _SZ, _VP, _SZ, _VP],
+    "zk_groth16_wires_rows": [_CP, _SZ, _CP, _SZ, _SZ, _SZ, _VP, _SZ, _VP],
+    "zk_plonk_prove_batch_with_pk": [_CP, _SZ, C.c_int, _CP, _SZ, _SZ, _SZ, _CP, _SZ, C.c_uint64, C.c_uint64, _VP, _SZ, _VP, _VP],
+    "zk_groth16_prove_batch_with_pk": [_CP, _SZ, _CP, _SZ, _SZ, _SZ, _CP, _SZ, C.c_uint64, _VP, _SZ, _VP, _VP],
+}
+# status of a row of those entries (include/zkmi.h: ZK_ROW_*)
+ROW_OK, ROW_UNSATISFIED, ROW_BAD_HEX, ROW_NOT_CANONICAL, ROW_BAD_COUNT = 0, 1, 2, 3, 4
 
 _lib = None
 
@@ -155,6 +168,8 @@ def lib() -> C.CDLL:
                 fn.restype = C.c_size_t
             elif name not in ("zk_last_error", "zk_version"):
                 fn.restype = C.c_int
+            if name in ARGTYPES:
+                fn.argtypes = ARGTYPES[name]
     return _lib
 
 

@@ -20,6 +20,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <future>
 #include <list>
@@ -48,6 +49,12 @@ __global__ void k_gather_fr(const Fr* __restrict__ vals, const uint32_t* __restr
     if (i < n) out[i] = vals[order[i]];
 }
 
+// the same with the row as blockIdx.y: row z gathers from vals + z * vals_stride into out + z * out_stride
+__global__ void k_gather_fr_rows(const Fr* __restrict__ vals, size_t vals_stride, const uint32_t* __restrict__ order, size_t n, Fr* __restrict__ out, size_t out_stride) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[blockIdx.y * out_stride + i] = vals[blockIdx.y * vals_stride + order[i]];
+}
+
 static int count_of(const char* hex, size_t len, size_t* n) {
     if (len < 8) return set_err(ZK_ERR_ARG, "felt vector: %zu characters cannot hold the 4-byte count", len);
     if (!count_from_hex(hex, len, n)) return set_err(ZK_ERR_ARG, "felt vector: invalid hex character in the count");
@@ -66,6 +73,8 @@ static int circuit_of(const Gates& G, zk_plonk_circuit* c) {
 
 // wall-clock sections of the export path, reported beside the kernels when profiling is on (zk_profile_*; bench.py's `export_path` block)
 int felts_decode_hex_on_slot(Slot* s, hipStream_t st, const void* d_text, size_t text_len, void* d_out, size_t cap, size_t n, int to_mont, int* d_status);  // wire.hip
+int felts_decode_hex_rows_on_slot(Slot* s, hipStream_t st, const void* d_text, size_t pitch, size_t rows, size_t n, void* d_out, size_t out_stride, int to_mont,
+                                  int* d_status);  // wire.hip
 struct InFlight {  // background jobs wait for calls in flight (ctx.hip)
     InFlight() { zk_background_hold(1); }
     ~InFlight() { zk_background_hold(-1); }
@@ -303,6 +312,26 @@ static void key_adopt(const char* pk_hex, size_t pk_len, const Lowered& L, uint6
     free_handles(dead);
 }
 
+// `count` blinding scalars from the OS generator, as upstream draws them with fr.SetRandom (both PlonkProveWithPK entries: nine per proof)
+static int plonk_blinders_draw(zk_fr* out, size_t count) {
+    FILE* f = fopen("/dev/urandom", "rb");
+    std::vector<uint8_t> raw(count * 32);
+    if (!f || fread(raw.data(), 1, raw.size(), f) != raw.size()) {
+        if (f) fclose(f);
+        return set_err(ZK_ERR_ARG, "no randomness source for the blinding scalars");
+    }
+    fclose(f);
+    for (size_t i = 0; i < count; i++) {
+        uint64_t t[4];
+        memcpy(t, raw.data() + 32 * i, 32);
+        t[3] &= 0x3fffffffffffffffULL;  // < 2^254, then one conditional subtraction: uniform enough for blinding (upstream: rejection sampling)
+        while (HFr::geq_mod(t)) HFr::sub_mod(t);
+        HFr m = HFr{{t[0], t[1], t[2], t[3]}}.to_mont();
+        memcpy(&out[i], &m, 32);
+    }
+    return ZK_OK;
+}
+
 // One proof on a resident circuit with a resident key (under L.work): DeserializeFelts on the device, the public-first gather (BuildWitnesses), the prover.
 static int plonk_prove_on(Lowered& L, const char* values_hex, size_t values_len, size_t n_values, uint64_t h, const zk_fr* blinders, uint8_t* proof) {
     Phase ph;
@@ -399,21 +428,7 @@ int zk_plonk_prove_with_pk(const char* acir_json, size_t acir_len, const char* v
     if (pk_hex) pk_key = std::async(std::launch::async, [pk_hex, pk_len] { return content_key(pk_hex, pk_len); });
     zk_fr rnd[9];
     if (!blinders) {
-        FILE* f = fopen("/dev/urandom", "rb");
-        uint8_t raw[9 * 32];
-        if (!f || fread(raw, 1, sizeof raw, f) != sizeof raw) {
-            if (f) fclose(f);
-            return set_err(ZK_ERR_ARG, "no randomness source for the blinding scalars");
-        }
-        fclose(f);
-        for (int i = 0; i < 9; i++) {
-            uint64_t t[4];
-            memcpy(t, raw + 32 * i, 32);
-            t[3] &= 0x3fffffffffffffffULL;  // < 2^254, then one conditional subtraction: uniform enough for blinding (upstream: rejection sampling)
-            while (HFr::geq_mod(t)) HFr::sub_mod(t);
-            HFr m = HFr{{t[0], t[1], t[2], t[3]}}.to_mont();
-            memcpy(&rnd[i], &m, 32);
-        }
+        ZK_TRY(plonk_blinders_draw(rnd, 9));
         blinders = rnd;
     }
     uint8_t proof[ZK_PLONK_PROOF_BYTES];
@@ -623,6 +638,20 @@ __global__ void k_raw_products(const uint32_t* __restrict__ pa, const uint32_t* 
     size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_products) return;
     w[base + j] = w[pa[j]] * w[pb[j]];  // operands are witness wires (below `base`), never products: no ordering among the lanes
+}
+
+// both with the row as blockIdx.y: row z's values at vals + z * vals_stride, its wires at w + z * w_stride; a product reads only its own row's wires below `base`
+__global__ void k_raw_wires_rows(const Fr* __restrict__ vals, size_t vals_stride, const uint32_t* __restrict__ order, size_t n_values, Fr one, Fr* __restrict__ w,
+                                 size_t w_stride) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n_values) return;
+    w[blockIdx.y * w_stride + i] = i == 0 ? one : vals[blockIdx.y * vals_stride + order[i - 1]];
+}
+__global__ void k_raw_products_rows(const uint32_t* __restrict__ pa, const uint32_t* __restrict__ pb, size_t n_products, size_t base, Fr* __restrict__ w, size_t w_stride) {
+    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_products) return;
+    Fr* wr = w + blockIdx.y * w_stride;
+    wr[base + j] = wr[pa[j]] * wr[pb[j]];
 }
 
 struct RawCircuit {
@@ -1267,6 +1296,351 @@ int zk_groth16_prove_with_meta(const char* raw_json, size_t raw_len, const zk_fr
     (void)zk_bn254_groth16_pk_free(h);
     if (rc == ZK_OK) hex_of(proof, 128, proof_hex_out);
     return rc;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ many witness-value texts of ONE circuit per call
+// What is left per proof once circuit and key are resident is "values text -> witness row".  Here that step has its row form: the texts of a chunk go up in one
+// pitched copy, one launch decodes them (wire.hip: k_felts_decode_hex_rows), one or two assemble the rows (k_gather_fr_rows; k_raw_wires_rows, k_raw_products_rows)
+// and the rows are handed to the batch provers as they lie in HBM.  The staging is the call's own -- nothing of Lowered / RawCircuit but the read-only order and
+// operand arrays is touched, so a call overlaps a single proof on the same circuit -- and is bounded by one chunk.
+namespace zkmi {
+
+// the staging of one chunk: the texts at a pitch that puts every row's felts on a 16-byte boundary (a text is 8 + 64 n characters: pitch 64 n + 16, the count
+// header of row 0 at offset 8), the decoded values, the rows' verdicts
+struct RowStage {
+    char* d_text = nullptr;
+    void* d_vals = nullptr;
+    int* d_status = nullptr;
+    size_t pitch = 0, cap = 0, n_values = 0;
+    std::vector<int> wire;  // the device verdicts of the chunk, host side
+    RowStage() = default;
+    RowStage(const RowStage&) = delete;
+    RowStage& operator=(const RowStage&) = delete;
+    ~RowStage() {
+        for (void* q : {(void*)d_text, d_vals, (void*)d_status})
+            if (q) (void)hipFree(q);
+    }
+    int make(size_t rows, size_t n) {
+        cap = rows;
+        n_values = n;
+        pitch = 64 * n + 16;
+        wire.assign(rows, 0);
+        ZK_HIP(hipMalloc((void**)&d_text, rows * pitch + 16));
+        ZK_HIP(hipMalloc(&d_vals, (rows * n ? rows * n : 1) * 32));
+        ZK_HIP(hipMalloc((void**)&d_status, rows * sizeof(int)));
+        return ZK_OK;
+    }
+    // R <= cap texts (row v = the values_len characters at values + v * values_stride) -> device, decoded; enqueued on `st`, the verdicts' download included
+    int upload_decode(Slot* s, hipStream_t st, const char* values, size_t values_len, size_t values_stride, size_t R) {
+        if (R == 1) ZK_HIP(hipMemcpyAsync(d_text + 8, values, values_len, hipMemcpyHostToDevice, st));  // (one row's stride may be anything)
+        else ZK_HIP(hipMemcpy2DAsync(d_text + 8, pitch, values, values_stride, values_len, R, hipMemcpyHostToDevice, st));
+        ZK_TRY(felts_decode_hex_rows_on_slot(s, st, d_text + 8, pitch, R, n_values, d_vals, n_values, 1, d_status));
+        if (n_values) ZK_HIP(hipMemcpyAsync(wire.data(), d_status, R * sizeof(int), hipMemcpyDeviceToHost, st));
+        return ZK_OK;
+    }
+    // the row's status (zkmi.h: ZK_ROW_*) from its count header, read on the host, and the decoder's verdict
+    int status_of(const char* row_text, size_t v) const {
+        size_t n = 0;
+        if (!count_from_hex(row_text, 8, &n) || n != n_values) return ZK_ROW_BAD_COUNT;
+        return wire[v] == 1 ? ZK_ROW_BAD_HEX : wire[v] == 2 ? ZK_ROW_NOT_CANONICAL : ZK_ROW_OK;  // wire.hip: WIRE_BAD_HEX, WIRE_NOT_CANONICAL
+    }
+};
+
+static int rows_args(const void* circuit, const char* values_hex, size_t values_len, size_t values_stride, size_t rows, const void* out, const int* status_out) {
+    if (!circuit || !values_hex || !out || !status_out) return set_err(ZK_ERR_ARG, "null pointer");
+    if (rows > 1 && values_stride < values_len) return set_err(ZK_ERR_ARG, "values_stride = %zu is below the %zu characters of a row", values_stride, values_len);
+    return ZK_OK;
+}
+// n_values of a call's rows: row 0's count header, which values_len must agree with (every row has that length; a row whose own header differs is ZK_ROW_BAD_COUNT)
+static int rows_n_values(const char* values_hex, size_t values_len, size_t* n_values) {
+    ZK_TRY(count_of(values_hex, values_len, n_values));
+    if (values_len != 8 + 64 * *n_values) return set_err(ZK_ERR_LEN, "felt vector: %zu characters, the count says %zu felts", values_len, *n_values);
+    return ZK_OK;
+}
+
+// rows per chunk of the assembly entries: what keeps the staging (96 bytes per felt and row) within 256 MiB, and the row a grid dimension
+static size_t assembly_chunk(size_t rows, size_t n_values) {
+    const size_t fit = ((size_t)256 << 20) / (96 * n_values + 16);
+    return std::max<size_t>(1, std::min(rows, std::min<size_t>(fit, 65535)));
+}
+// R solutions of a resident circuit (L.d_order uploaded) at d_sol + v * sol_stride; status[v] = ZK_ROW_*.  Takes one stream slot and gives it back.
+static int plonk_solutions_chunk(const Lowered& L, RowStage& S, const char* values, size_t values_len, size_t values_stride, size_t R, void* d_sol, size_t sol_stride,
+                                 int* status) {
+    Phase ph;
+    {
+        SlotGuard g;
+        ZK_TRY(acquire_slot(&g.s));
+        hipStream_t st = g.s->stream;
+        int rc = S.upload_decode(g.s, st, values, values_len, values_stride, R);
+        if (rc == ZK_OK && L.n_vars)
+            ZK_LAUNCH(g.s, st, "witness_gather_rows", k_gather_fr_rows, dim3((unsigned)((L.n_vars + 255) / 256), (unsigned)R), dim3(256), 0, (const Fr*)S.d_vals, L.n_values,
+                      (const uint32_t*)L.d_order, L.n_vars, (Fr*)d_sol, sol_stride);
+        const int rs = slot_sync(g.s, st);  // also on an error: what was enqueued drains before the caller's text goes
+        ZK_TRY(rc);
+        ZK_TRY(rs);
+    }
+    for (size_t v = 0; v < R; v++) status[v] = S.status_of(values + v * values_stride, v);
+    ph.lap("export.batch_witness_rows");
+    return ZK_OK;
+}
+// R wire vectors [ONE, public, secret, products] of a resident circuit at d_w + v * w_stride
+static int raw_wires_chunk(const RawCircuit& C, RowStage& S, const char* values, size_t values_len, size_t values_stride, size_t R, void* d_w, size_t w_stride, int* status) {
+    Phase ph;
+    Fr one;
+    {
+        const HFr h1 = HFr::one();
+        memcpy(&one, &h1, 32);
+    }
+    {
+        SlotGuard g;
+        ZK_TRY(acquire_slot(&g.s));
+        hipStream_t st = g.s->stream;
+        int rc = S.upload_decode(g.s, st, values, values_len, values_stride, R);
+        if (rc == ZK_OK) {
+            ZK_LAUNCH(g.s, st, "raw_wires_rows", k_raw_wires_rows, dim3((unsigned)((C.n_values + 256) / 256), (unsigned)R), dim3(256), 0, (const Fr*)S.d_vals, C.n_values,
+                      (const uint32_t*)C.d_order, C.n_values, one, (Fr*)d_w, w_stride);
+            if (C.n_products)
+                ZK_LAUNCH(g.s, st, "raw_products_rows", k_raw_products_rows, dim3((unsigned)((C.n_products + 255) / 256), (unsigned)R), dim3(256), 0, (const uint32_t*)C.d_pa,
+                          (const uint32_t*)C.d_pb, C.n_products, 1 + C.n_values, (Fr*)d_w, w_stride);
+        }
+        const int rs = slot_sync(g.s, st);
+        ZK_TRY(rc);
+        ZK_TRY(rs);
+    }
+    for (size_t v = 0; v < R; v++) status[v] = S.status_of(values + v * values_stride, v);
+    ph.lap("export.batch_witness_rows");
+    return ZK_OK;
+}
+// the resident circuit behind a RawR1CS text whose embedded values string only identifies it
+static int raw_circuit_for_rows(const char* raw_json, size_t raw_len, size_t values_len, std::shared_ptr<RawCircuit>* C) {
+    size_t at = 0;
+    ZK_TRY(raw_circuit_get(raw_json, raw_len, C, &at));
+    if (!at) return set_err(ZK_ERR_ARG, "RawR1CS JSON: the values string must be plain hex (no escapes)");
+    ZK_TRY(raw_span_is_hex(raw_json + at, (*C)->span_len));
+    if (values_len != (*C)->span_len) return set_err(ZK_ERR_LEN, "felt vector: %zu characters, the circuit was read with %zu", values_len, (*C)->span_len);
+    return ZK_OK;
+}
+// rows of '0' for the rows without a proof, hex for the others
+static void proofs_hex_rows(const uint8_t* proofs, size_t bytes, const int* status, size_t rows, char* out) {
+    for (size_t v = 0; v < rows; v++) {
+        if (status[v] == ZK_ROW_OK) hex_of(proofs + bytes * v, bytes, out + 2 * bytes * v);
+        else memset(out + 2 * bytes * v, '0', 2 * bytes);
+    }
+}
+
+}  // namespace zkmi
+
+extern "C" {
+
+int zk_plonk_solutions_rows(const char* acir_json, size_t acir_len, int layout, const char* values_hex, size_t values_len, size_t values_stride, size_t rows,
+                            void* d_solutions, size_t sol_stride, int* status_out) {
+    InFlight _in_flight;
+    ZK_TRY(rows_args(acir_json, values_hex, values_len, values_stride, rows, d_solutions, status_out));
+    if (rows == 0) return ZK_OK;
+    size_t n_values = 0;
+    ZK_TRY(rows_n_values(values_hex, values_len, &n_values));
+    std::shared_ptr<Lowered> L;
+    ZK_TRY(lowered_get(acir_json, acir_len, n_values, layout, &L, nullptr));
+    if (rows > 1 && sol_stride < L->n_vars) return set_err(ZK_ERR_ARG, "sol_stride = %zu is below the %zu variables of a row", sol_stride, L->n_vars);
+    ZK_TRY(ensure_init());
+    {
+        std::lock_guard<std::mutex> work(L->work);
+        ZK_TRY(L->device_buffers());
+    }
+    const size_t chunk = assembly_chunk(rows, n_values);
+    RowStage S;
+    ZK_TRY(S.make(chunk, n_values));
+    for (size_t first = 0; first < rows; first += chunk)
+        ZK_TRY(plonk_solutions_chunk(*L, S, values_hex + first * values_stride, values_len, values_stride, std::min(chunk, rows - first),
+                                     (Fr*)d_solutions + first * sol_stride, sol_stride, status_out + first));
+    return ZK_OK;
+}
+
+int zk_groth16_wires_rows(const char* raw_json, size_t raw_len, const char* values_hex, size_t values_len, size_t values_stride, size_t rows, void* d_wires,
+                          size_t wire_stride, int* status_out) {
+    InFlight _in_flight;
+    ZK_TRY(rows_args(raw_json, values_hex, values_len, values_stride, rows, d_wires, status_out));
+    if (rows == 0) return ZK_OK;
+    std::shared_ptr<RawCircuit> C;
+    ZK_TRY(raw_circuit_for_rows(raw_json, raw_len, values_len, &C));
+    if (rows > 1 && wire_stride < C->n_wires) return set_err(ZK_ERR_ARG, "wire_stride = %zu is below the %zu wires of a row", wire_stride, C->n_wires);
+    ZK_TRY(ensure_init());
+    {
+        std::lock_guard<std::mutex> work(C->work);
+        ZK_TRY(C->device_buffers());
+    }
+    const size_t chunk = assembly_chunk(rows, C->n_values);
+    RowStage S;
+    ZK_TRY(S.make(chunk, C->n_values));
+    for (size_t first = 0; first < rows; first += chunk)
+        ZK_TRY(raw_wires_chunk(*C, S, values_hex + first * values_stride, values_len, values_stride, std::min(chunk, rows - first), (Fr*)d_wires + first * wire_stride,
+                               wire_stride, status_out + first));
+    return ZK_OK;
+}
+
+int zk_plonk_prove_batch_with_pk(const char* acir_json, size_t acir_len, int layout, const char* values_hex, size_t values_len, size_t values_stride, size_t rows,
+                                 const char* pk_hex, size_t pk_len, uint64_t pk_handle, uint64_t srs_handle, const zk_fr* blinders, size_t chunk_rows, char* proofs_hex_out,
+                                 int* status_out) {
+    InFlight _in_flight;
+    ZK_TRY(rows_args(acir_json, values_hex, values_len, values_stride, rows, proofs_hex_out, status_out));
+    if (!pk_hex && !pk_handle) return set_err(ZK_ERR_ARG, "neither a key text nor a resident key");
+    if (rows == 0) return ZK_OK;
+    size_t n_values = 0;
+    ZK_TRY(rows_n_values(values_hex, values_len, &n_values));
+    ZK_ON_ENTRY_OF(pk_handle ? pk_handle : srs_handle);
+    std::vector<zk_fr> drawn;
+    if (!blinders) {
+        drawn.resize(9 * rows);
+        ZK_TRY(plonk_blinders_draw(drawn.data(), drawn.size()));
+        blinders = drawn.data();
+    }
+    std::shared_ptr<Lowered> L;
+    ZK_TRY(lowered_get(acir_json, acir_len, n_values, layout, &L, nullptr));
+    ZK_TRY(ensure_init());
+    Phase ph;
+    uint64_t h = pk_handle;
+    bool cached = false;
+    std::unique_lock<std::mutex> work(L->work);  // around the circuit's upload and the key's residency only: the launches below touch nothing a single proof writes
+    ZK_TRY(L->device_buffers());
+    if (pk_hex) ZK_TRY(key_get(pk_hex, pk_len, *L, srs_handle, &h, &cached));
+    struct Done {  // whatever happens below: a cached key is unpinned, an uncached one freed
+        uint64_t h; bool from_text, cached;
+        ~Done() { if (from_text) { if (cached) key_release(h); else (void)zk_bn254_plonk_pk_free(h); } }
+    } done{h, pk_hex != nullptr, cached};
+    ph.lap("export.pk_resident");
+    {   // the key must be the key of THIS circuit (plonk_prove_on): once per call
+        size_t kp = 0, kv = 0, kc = 0;
+        ZK_TRY(zk_bn254_plonk_pk_info(h, nullptr, &kp, &kc, &kv));
+        if (kp != L->n_public || kv != L->n_vars || kc != L->n_gates)
+            return set_err(ZK_ERR_ARG, "proving key is for %zu public / %zu variables / %zu gates, the circuit has %zu / %zu / %zu", kp, kv, kc, L->n_public, L->n_vars, L->n_gates);
+    }
+    if (cached) {  // the key's proof count advances by the rows; the Lagrange form of its SRS is built before the batch that crosses the threshold (no byte changes)
+        bool build = false;
+        {
+            std::lock_guard<std::mutex> lk(g_cache_mu);
+            for (auto& k : g_keys)
+                if (k.handle == h) {
+                    build = k.proofs < kLagrangeAfterProofs && k.proofs + rows >= kLagrangeAfterProofs;
+                    k.proofs = (unsigned)std::min<size_t>(k.proofs + rows, 1u << 30);
+                    break;
+                }
+        }
+        if (build) {
+            if (zk_bn254_plonk_pk_lagrange_srs(h) == ZK_OK) {
+                size_t bytes = 0;
+                (void)zk_bn254_plonk_pk_bytes(h, &bytes);
+                std::lock_guard<std::mutex> lk(g_cache_mu);
+                for (auto& k : g_keys)
+                    if (k.handle == h) k.bytes = bytes;
+            }
+            ph.lap("export.pk_lagrange_srs");
+        }
+    }
+    work.unlock();
+    size_t chunk = 1;
+    ZK_TRY(zk_bn254_plonk_prove_batch_info(h, &chunk, nullptr, nullptr));
+    if (chunk_rows) chunk = std::min(chunk, chunk_rows);
+    chunk = std::min(chunk, rows);
+    RowStage S;
+    ZK_TRY(S.make(chunk, n_values));
+    void* d_sol = nullptr;
+    struct Free { void** p; ~Free() { if (*p) (void)hipFree(*p); } } guard{&d_sol};
+    ZK_HIP(hipMalloc(&d_sol, (chunk * L->n_vars ? chunk * L->n_vars : 1) * 32));
+    std::vector<uint8_t> proofs(chunk * ZK_PLONK_PROOF_BYTES);
+    std::vector<int> verdict(chunk);
+    ph.lap("export.batch_staging");
+    for (size_t first = 0; first < rows; first += chunk) {
+        const size_t R = std::min(chunk, rows - first);
+        int* status = status_out + first;
+        ZK_TRY(plonk_solutions_chunk(*L, S, values_hex + first * values_stride, values_len, values_stride, R, d_sol, L->n_vars, status));  // (its slot is back)
+        ZK_TRY(zk_bn254_plonk_prove_batch(h, d_sol, L->n_vars, L->n_vars, R, 1, blinders + 9 * first, nullptr, 0, proofs.data(), verdict.data()));
+        for (size_t v = 0; v < R; v++)
+            if (status[v] == ZK_ROW_OK) status[v] = verdict[v];  // (a row the decoder refused was proved from its zero-padded form: that verdict does not count)
+        proofs_hex_rows(proofs.data(), ZK_PLONK_PROOF_BYTES, status, R, proofs_hex_out + 2 * ZK_PLONK_PROOF_BYTES * first);
+        ph.lap("export.batch_plonk_prove");
+    }
+    return ZK_OK;
+}
+
+int zk_groth16_prove_batch_with_pk(const char* raw_json, size_t raw_len, const char* values_hex, size_t values_len, size_t values_stride, size_t rows, const char* pk_hex,
+                                   size_t pk_len, uint64_t pk_handle, const zk_fr* rs, size_t chunk_rows, char* proofs_hex_out, int* status_out) {
+    InFlight _in_flight;
+    ZK_TRY(rows_args(raw_json, values_hex, values_len, values_stride, rows, proofs_hex_out, status_out));
+    if (!pk_hex && !pk_handle) return set_err(ZK_ERR_ARG, "neither a key text nor a resident key");
+    if (rows == 0) return ZK_OK;
+    {
+        size_t n = 0;
+        ZK_TRY(rows_n_values(values_hex, values_len, &n));
+    }
+    CtxScope _scope(pk_handle ? hentry(pk_handle) : current_entry());
+    if (_scope.rc != ZK_OK) return _scope.rc;
+    std::vector<HFr> r(rows), s(rows);
+    {
+        std::vector<HFr> drawn;
+        if (!rs) {
+            drawn.resize(2 * rows);
+            for (size_t i = 0; i < drawn.size(); i += 1024) ZK_TRY(random_frs(drawn.data() + i, (int)std::min<size_t>(1024, drawn.size() - i), false));
+        }
+        const HFr* src = rs ? (const HFr*)rs : drawn.data();
+        for (size_t v = 0; v < rows; v++) { r[v] = src[2 * v]; s[v] = src[2 * v + 1]; }
+    }
+    std::shared_ptr<RawCircuit> C;
+    ZK_TRY(raw_circuit_for_rows(raw_json, raw_len, values_len, &C));
+    ZK_TRY(ensure_init());
+    Phase ph;
+    uint64_t h = pk_handle;
+    bool cached = false;
+    std::unique_lock<std::mutex> work(C->work);  // around the circuit's upload and the key's residency only
+    ZK_TRY(C->device_buffers());
+    if (pk_hex) ZK_TRY(g16_key_get(pk_hex, pk_len, nullptr, &h, &cached));
+    struct Done {
+        uint64_t h; bool from_text, cached;
+        ~Done() { if (from_text) { if (cached) g16_key_release(h); else (void)zk_bn254_groth16_pk_free(h); } }
+    } done{h, pk_hex != nullptr, cached};
+    ph.lap("export.pk_resident");
+    {   // the key must be the key of THIS circuit's shape (g16_prove_resident): once per call
+        size_t kw = 0, kp = 0;
+        uint32_t lg = 0;
+        ZK_TRY(zk_bn254_groth16_pk_info(h, &kw, &kp, &lg, nullptr));
+        if (kw != C->n_wires || kp != C->n_public || C->n_constraints > ((size_t)1 << lg))
+            return set_err(ZK_ERR_ARG, "proving key is for %zu wires / %zu public / 2^%u constraints, the circuit has %zu / %zu / %zu", kw, kp, lg, C->n_wires, C->n_public, C->n_constraints);
+    }
+    if (cached) {  // a key that proves again gets its window tables in the background, as in the single entry; this call runs with what the key has
+        bool build = false;
+        {
+            std::lock_guard<std::mutex> lk(g_cache_mu);
+            for (auto& k : g_g16_keys)
+                if (k.handle == h) {
+                    build = k.proofs < kG16TablesAtProof && k.proofs + rows >= kG16TablesAtProof;
+                    k.proofs = (unsigned)std::min<size_t>(k.proofs + rows, 1u << 30);
+                    break;
+                }
+        }
+        if (build) g16_tables_in_background(h);
+    }
+    work.unlock();
+    size_t chunk = 1;
+    ZK_TRY(zk_bn254_groth16_batch_info(h, &chunk, nullptr));
+    if (chunk_rows) chunk = std::min(chunk, chunk_rows);
+    chunk = std::min(chunk, rows);
+    RowStage S;
+    ZK_TRY(S.make(chunk, C->n_values));
+    void* d_w = nullptr;
+    struct Free { void** p; ~Free() { if (*p) (void)hipFree(*p); } } guard{&d_w};
+    ZK_HIP(hipMalloc(&d_w, chunk * C->n_wires * 32));
+    std::vector<uint8_t> proofs(chunk * 128);
+    ph.lap("export.batch_staging");
+    for (size_t first = 0; first < rows; first += chunk) {
+        const size_t R = std::min(chunk, rows - first);
+        int* status = status_out + first;
+        ZK_TRY(raw_wires_chunk(*C, S, values_hex + first * values_stride, values_len, values_stride, R, d_w, C->n_wires, status));  // (its slot is back)
+        ZK_TRY(zk_bn254_groth16_prove_r1cs_batch(C->r1cs, h, d_w, C->n_wires, (const zk_fr*)r.data() + first, (const zk_fr*)s.data() + first, R, 1, proofs.data()));
+        proofs_hex_rows(proofs.data(), 128, status, R, proofs_hex_out + 256 * first);
+        ph.lap("export.batch_groth16_prove");
+    }
+    return ZK_OK;
 }
 
 // Releases everything the export path keeps resident between calls (lowered circuits, decoded proving keys; PLONK and Groth16).  Keys in use by a running proof stay.

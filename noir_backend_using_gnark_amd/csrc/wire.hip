@@ -55,6 +55,31 @@ __global__ __launch_bounds__(256) void k_felts_decode_hex(const uint4* __restric
     out[i] = to_mont ? x.to_mont() : x;
 }
 
+// The same with the row as blockIdx.y: `rows` texts of n felts each, row z's felts at text + z * pitch bytes (16-byte aligned: pitch is a multiple of 16), its
+// elements at out + z * out_stride, its verdict in status[z].  A lane that rejects its felt still writes an element (zero): the stage behind (the witness
+// gathers of frontend.hip) reads every element of every row, whatever the row's verdict.
+__global__ __launch_bounds__(256) void k_felts_decode_hex_rows(const char* __restrict__ text, size_t pitch, size_t n, int to_mont, Fr* __restrict__ out, size_t out_stride,
+                                                               int* __restrict__ status) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t row = blockIdx.y;
+    const uint4* __restrict__ felts = reinterpret_cast<const uint4*>(text + row * pitch);
+    uint32_t bad = 0;
+    Fr x;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {  // as above
+        uint4 t = felts[i * 4 + q];
+        uint32_t h0 = hex4(t.x, &bad), h1 = hex4(t.y, &bad), h2 = hex4(t.z, &bad), h3 = hex4(t.w, &bad);
+        x.l[7 - 2 * q] = (__builtin_bswap32(h0) >> 16 << 16) | (__builtin_bswap32(h1) >> 16);
+        x.l[6 - 2 * q] = (__builtin_bswap32(h2) >> 16 << 16) | (__builtin_bswap32(h3) >> 16);
+    }
+    Fr y = Fr::zero();
+    if (bad) atomicMax(status + row, (int)WIRE_BAD_HEX);
+    else if (geq_mod_r(x.l)) atomicMax(status + row, (int)WIRE_NOT_CANONICAL);
+    else y = to_mont ? x.to_mont() : x;
+    out[row * out_stride + i] = y;
+}
+
 // raw bytes (already hex-decoded): 32 big-endian bytes per felt
 __global__ __launch_bounds__(256) void k_felts_decode_bytes(const uint4* __restrict__ raw, size_t n, int to_mont, Fr* __restrict__ out, int* __restrict__ status) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -142,8 +167,39 @@ int felts_decode_hex_on_slot(Slot* s, hipStream_t st, const void* d_text, size_t
     ZK_TRY(slot_sync(s, st));
     return status_to_rc(h_status);
 }
+// what the row form asks of its arguments (decided before a device is looked for)
+static int decode_rows_args(const void* d_text, size_t pitch, size_t rows, size_t n, const void* d_out, size_t out_stride, const int* d_status) {
+    if (!d_text || !d_out || !d_status) return set_err(ZK_ERR_ARG, "null pointer");
+    if (rows > 65535) return set_err(ZK_ERR_ARG, "%zu rows in one call, at most 65535 (the row is a grid dimension)", rows);
+    if ((pitch & 15) || pitch < 8 + 64 * n) return set_err(ZK_ERR_ARG, "pitch = %zu must be a multiple of 16 and at least the %zu characters of a row", pitch, 8 + 64 * n);
+    if (out_stride < n) return set_err(ZK_ERR_ARG, "out_stride = %zu is below the %zu felts of a row", out_stride, n);
+    if ((((uintptr_t)d_text) + 8) & 15) return set_err(ZK_ERR_ARG, "hex text must start 8 bytes before a 16-byte boundary");
+    return ZK_OK;
+}
+// `rows` texts of n felts each in ONE launch, on a slot the caller holds: row z's count header at d_text + z * pitch (8 bytes before a 16-byte boundary), its
+// elements at d_out + z * out_stride, its WIRE_* verdict in d_status[z].  Enqueues only: the caller synchronises and reads the verdicts when it wants them.
+int felts_decode_hex_rows_on_slot(Slot* s, hipStream_t st, const void* d_text, size_t pitch, size_t rows, size_t n, void* d_out, size_t out_stride, int to_mont,
+                                  int* d_status) {
+    if (rows == 0 || n == 0) return ZK_OK;
+    ZK_TRY(decode_rows_args(d_text, pitch, rows, n, d_out, out_stride, d_status));
+    ZK_HIP(hipMemsetAsync(d_status, 0, rows * sizeof(int), st));
+    ZK_LAUNCH(s, st, "felts_decode_hex_rows", k_felts_decode_hex_rows, dim3((unsigned)((n + 255) / 256), (unsigned)rows), dim3(256), 0, (const char*)d_text + 8, pitch, n,
+              to_mont, (Fr*)d_out, out_stride, d_status);
+    return ZK_OK;
+}
 }  // namespace zkmi
 extern "C" {
+
+int zk_bn254_felts_decode_hex_rows_dev(const void* d_text, size_t pitch, size_t rows, size_t n, void* d_out, size_t out_stride, int to_mont, int* d_status, void* stream) {
+    if (rows == 0 || n == 0) return ZK_OK;
+    ZK_TRY(decode_rows_args(d_text, pitch, rows, n, d_out, out_stride, d_status));
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    ZK_TRY(felts_decode_hex_rows_on_slot(g.s, st, d_text, pitch, rows, n, d_out, out_stride, to_mont, d_status));
+    if (!stream || profiling_on()) ZK_TRY(slot_sync(g.s, st));
+    return ZK_OK;
+}
 
 // DeserializeFelts: hex string on the host -> Montgomery fr.Element vector in HBM (d_out, capacity cap); *n_out = count.
 int zk_bn254_felts_decode_hex(const char* hex, size_t hex_len, void* d_out, size_t cap, size_t* n_out) {

@@ -166,6 +166,79 @@ def groth16_public_inputs(raw_json: str) -> np.ndarray:
     return out[:n.value]
 
 
+def _rows_text(encoded_values) -> tuple[bytes, int, int]:
+    """a list of felt-vector texts of one length -> (contiguous buffer, characters per row, rows)"""
+    rows = [_b(v) for v in encoded_values]
+    if rows and any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("the values texts of a batch must all have the same length")
+    return b"".join(rows), (len(rows[0]) if rows else 0), len(rows)
+
+
+def _raise_arg(rc: int) -> None:
+    if rc in (_lib.ZK_ERR_LEN, _lib.ZK_ERR_ARG):
+        raise ValueError((lib().zk_last_error() or b"").decode())
+    check(rc)
+
+
+def plonk_solutions_rows(acir_json: str, encoded_values: list, layout: int = LAYOUT_REFERENCE):
+    """HandleValues of many witness-value texts of one circuit, on the device -> ((rows, n_vars, 4) Montgomery limbs, [status per row])."""
+    a = _b(acir_json)
+    text, vlen, rows = _rows_text(encoded_values)
+    n_vars = acir_to_sparse_r1cs(acir_json, (vlen - 8) // 64, layout)["n_vars"] if rows else 0
+    buf = _lib.DeviceBuffer(max(rows * n_vars, 1) * 32)
+    status = np.zeros(max(rows, 1), np.int32)
+    _raise_arg(lib().zk_plonk_solutions_rows(a, len(a), layout, text, vlen, vlen, rows, buf.ptr, n_vars, vp(status)))
+    return buf.to_numpy(np.uint64, (rows, n_vars, 4)), [int(x) for x in status[:rows]]
+
+
+def groth16_wires_rows(raw_json: str, encoded_values: list, n_wires: int):
+    """buildR1CS' wire vectors [ONE, public, secret, products] of many witness-value texts of one circuit, on the device (the text's own values string only
+    identifies the circuit) -> ((rows, n_wires, 4) Montgomery limbs, [status per row]).  n_wires: as groth16_r1cs_from_raw reports it."""
+    a = _b(raw_json)
+    text, vlen, rows = _rows_text(encoded_values)
+    buf = _lib.DeviceBuffer(max(rows * n_wires, 1) * 32)
+    status = np.zeros(max(rows, 1), np.int32)
+    _raise_arg(lib().zk_groth16_wires_rows(a, len(a), text, vlen, vlen, rows, buf.ptr, n_wires, vp(status)))
+    return buf.to_numpy(np.uint64, (rows, n_wires, 4)), [int(x) for x in status[:rows]]
+
+
+def _proof_rows(out, width: int, status) -> list:
+    raw = out.raw
+    return [raw[v * width:(v + 1) * width].decode() if st == _lib.ROW_OK else None for v, st in enumerate(status)]
+
+
+def plonk_prove_batch_with_pk(acir_json: str, encoded_values: list, encoded_pk: str | None, srs, blinders=None, pk_handle: int = 0, layout: int = LAYOUT_REFERENCE,
+                              chunk_rows: int = 0):
+    """PlonkProveWithPK for many witness-value texts of one circuit in one call -> ([hex proof, or None where the row has none], [status per row: _lib.ROW_*]).
+    Row v's proof is what plonk_prove_with_pk gives for encoded_values[v] with blinders[v] ((rows, 9, 4) Montgomery limbs; None draws them)."""
+    a = _b(acir_json)
+    text, vlen, rows = _rows_text(encoded_values)
+    k = _b(encoded_pk) if encoded_pk is not None else None
+    bl = None if blinders is None else np.ascontiguousarray(blinders, dtype=np.uint64).reshape(rows * 9, 4)
+    width = 2 * _lib.PLONK_PROOF_BYTES
+    out = C.create_string_buffer(max(rows, 1) * width)
+    status = np.zeros(max(rows, 1), np.int32)
+    _raise_arg(lib().zk_plonk_prove_batch_with_pk(a, len(a), layout, text, vlen, vlen, rows, k, len(k) if k is not None else 0, pk_handle, srs.handle, vp(bl), chunk_rows,
+                                                  C.addressof(out), vp(status)))
+    st = [int(x) for x in status[:rows]]
+    return _proof_rows(out, width, st), st
+
+
+def groth16_prove_batch_with_pk(raw_json: str, encoded_values: list, encoded_pk: str | None, rs=None, pk_handle: int = 0, chunk_rows: int = 0):
+    """ProveWithPK for many witness-value texts of one RawR1CS circuit in one call -> ([hex proof or None], [status per row]).  rs: (rows, 2, 4) Montgomery limbs,
+    row v's (r, s); None draws them."""
+    a = _b(raw_json)
+    text, vlen, rows = _rows_text(encoded_values)
+    k = _b(encoded_pk) if encoded_pk is not None else None
+    r2 = None if rs is None else np.ascontiguousarray(rs, dtype=np.uint64).reshape(rows * 2, 4)
+    out = C.create_string_buffer(max(rows, 1) * 256)
+    status = np.zeros(max(rows, 1), np.int32)
+    _raise_arg(lib().zk_groth16_prove_batch_with_pk(a, len(a), text, vlen, vlen, rows, k, len(k) if k is not None else 0, pk_handle, vp(r2), chunk_rows, C.addressof(out),
+                                                    vp(status)))
+    st = [int(x) for x in status[:rows]]
+    return _proof_rows(out, 256, st), st
+
+
 def export_cache_info() -> dict:
     """What the export path keeps resident between calls (PLONK and Groth16 entries together)."""
     nc, nk, by = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)

@@ -33,6 +33,37 @@ def serialize_felts(d_vec, n: int) -> str:
     return buf.raw.decode("ascii")
 
 
+def decode_hex_rows(texts: list, to_mont: bool = True, out_stride: int | None = None, fill: int | None = None) -> tuple[np.ndarray, list]:
+    """DeserializeFelts of many texts of the same count in one launch (zk_bn254_felts_decode_hex_rows_dev) -> ((rows, out_stride, 4) limbs, [status per row]).
+    The rows are staged at the pitch the kernel asks for (64 n + 16: every row's felts 16-byte aligned).  Status: _lib.ROW_OK / ROW_BAD_HEX / ROW_NOT_CANONICAL /
+    ROW_BAD_COUNT (the header is checked here, on the host, as the entry leaves it to its caller); a rejected felt decodes to zero.  out_stride > n leaves a gap
+    behind every row that the kernel does not write: it keeps `fill` (every limb), with which the output is filled first when given."""
+    rows = [t.encode("ascii") if isinstance(t, str) else bytes(t) for t in texts]
+    if not rows:
+        return np.zeros((0, 0, 4), np.uint64), []
+    if any(len(r) != len(rows[0]) for r in rows) or len(rows[0]) < 8 or (len(rows[0]) - 8) % 64:
+        raise ValueError("the texts of a batch must all be 8 + 64 n characters long")
+    n = (len(rows[0]) - 8) // 64
+    stride = n if out_stride is None else out_stride
+    pitch = 64 * n + 16
+    staged = b"\0" * 8 + b"".join(r + b"\0" * 8 for r in rows)  # row z's header at 8 + z * pitch
+    d_text = _lib.DeviceBuffer.from_numpy(np.frombuffer(staged, dtype=np.uint8))
+    init = np.zeros((len(rows), max(stride, 1), 4), np.uint64) if fill is None else np.full((len(rows), max(stride, 1), 4), fill, np.uint64)
+    d_out = _lib.DeviceBuffer.from_numpy(init)
+    d_status = _lib.DeviceBuffer.from_numpy(np.zeros(len(rows), np.int32))
+    check(lib().zk_bn254_felts_decode_hex_rows_dev(d_text.ptr + 8, pitch, len(rows), n, d_out.ptr, stride, int(to_mont), d_status.ptr, None))
+    out = d_out.to_numpy(np.uint64, init.shape)
+    wire_status = d_status.to_numpy(np.int32, (len(rows),))  # 0, 1 = invalid hex character, 2 = not canonical
+    status = []
+    for r, ws in zip(rows, wire_status):
+        try:
+            header_ok = int(r[:8], 16) == n and not r[:8].strip(b"0123456789abcdefABCDEF")
+        except ValueError:
+            header_ok = False
+        status.append(_lib.ROW_BAD_COUNT if not header_ok else (_lib.ROW_OK, _lib.ROW_BAD_HEX, _lib.ROW_NOT_CANONICAL)[int(ws)])
+    return out[:, :stride] if stride else out[:, :0], status
+
+
 def deserialize_felts_to_numpy(encoded) -> np.ndarray:
     d, n = deserialize_felts(encoded)
     return d.to_numpy(np.uint64, (max(n, 1), 4))[:n]

@@ -24,12 +24,15 @@ def _splitmix(seed):
         yield z ^ (z >> 31)
 
 
-def synth(n_opcodes: int, n_public: int = 8, seed: int = 1, compact: bool = True):
-    """-> (acir_json: str, values: list[int]) ; values[w - 1] is witness w, n_opcodes + 2 witnesses in all."""
+def synth(n_opcodes: int, n_public: int = 8, seed: int = 1, compact: bool = True, first=None):
+    """-> (acir_json: str, values: list[int]) ; values[w - 1] is witness w, n_opcodes + 2 witnesses in all.  first = (v1, v2): other values for the first two
+    witnesses -- the same circuit text (the coefficients do not depend on the values) and another satisfying assignment."""
     g = _splitmix(seed)
     hx = lambda v: "%064x" % (v % R)
     one, minus_one = hx(1), hx(-1)
     w = [next(g) % R, next(g) % R]  # witnesses 1 and 2
+    if first:
+        w = [first[0] % R, first[1] % R]
     ops = []
     sep = (",", ":") if compact else (", ", ": ")
     for i in range(n_opcodes):
