@@ -425,6 +425,34 @@ int zk_bn254_plonk_verify_batch(const uint8_t *proofs, size_t n_proofs, const vo
                                 const zk_g2_affine srs_g2[2], const zk_fr *public_inputs, size_t n_public,
                                 uint8_t *accepted, size_t *n_accepted);
 
+/* The two batch verifiers for proofs and public inputs that already lie in HBM: nothing of them comes down but 32 bytes per row.
+ *   d_proofs           device: row v's 128 (548) bytes at d_proofs + v * proof_stride bytes; any stride >= the row (the gap is not read), any alignment.
+ *   d_public_inputs    device: row v's n_public Montgomery fr.Elements at element v * pub_stride (pub_stride >= n_public; 4-byte aligned); may be NULL when
+ *                      n_public == 0.
+ *   vk, srs_g2, accepted, n_accepted   host, as in the entries above.
+ * accepted[i] equals what zk_bn254_groth16_verify_batch / zk_bn254_plonk_verify_batch says for the same bytes: a malformed proof encoding is a 0 and does not
+ * touch its neighbours; a malformed key and a wrong n_public give the same codes and messages, decided before a device is looked for, as are a null pointer and
+ * a stride below its row with more than one row (ZK_ERR_ARG).  The checks, the chunks and the fallback are those of the entries above -- one core serves both
+ * forms -- and only the coefficients' derivation differs, because the host never sees the rows:
+ *   d_v    = SHA-256(row v's proof bytes || row v's 32 * n_public public-input bytes AS THEY LIE IN MEMORY -- the Montgomery images, little-endian limbs),
+ *            one lane per row on the device (zk_bn254_rows_sha256_dev below);
+ *   D      = SHA-256(d_0 || d_1 || ... || d_{n-1}) over ALL n_proofs rows of the call (not per chunk), on the host;
+ *   r_i    = the low 128 bits of SHA-256("zkmi-groth16-batch-rows" || SHA-256(vk bytes) || D || u64 i little-endian), forced non-zero;
+ *   rho_i, rho'_i = the low 128 bits of SHA-256("zkmi-plonk-batch-rows" || SHA-256(vk bytes) || SHA-256(srs_g2) || D || u64 i little-endian || 0 / 1), forced
+ *            non-zero -- i counts over the whole call; "low 128 bits": the digest read as a big-endian integer, as above.
+ * The host-input entries keep their derivation: the same proofs get other coefficients there and the same verdicts.
+ *   zk_bn254_rows_sha256_dev : d_out[32 v ..] = SHA-256(a_v || b_v), a_v the a_len bytes at d_a + v * a_stride, b_v the b_len bytes at d_b + v * b_stride;
+ *            either span may be empty (its pointer is then not read and may be NULL).  Everything in HBM, any alignment.  With `stream` the call only
+ *            enqueues; stream == NULL runs on a stream of the library's and returns when the launch is complete.  A null pointer of a span that is read, a
+ *            stride below its span with more than one row: ZK_ERR_ARG before a device is looked for; rows == 0: ZK_OK, nothing launched. */
+int zk_bn254_groth16_verify_batch_dev(const void *d_proofs, size_t proof_stride, size_t n_proofs, const void *vk, size_t vk_len, int vk_is_hex,
+                                      const void *d_public_inputs, size_t pub_stride, size_t n_public, uint8_t *accepted, size_t *n_accepted);
+int zk_bn254_plonk_verify_batch_dev(const void *d_proofs, size_t proof_stride, size_t n_proofs, const void *vk, size_t vk_len, int vk_is_hex,
+                                    const zk_g2_affine srs_g2[2], const void *d_public_inputs, size_t pub_stride, size_t n_public,
+                                    uint8_t *accepted, size_t *n_accepted);
+int zk_bn254_rows_sha256_dev(const void *d_a, size_t a_len, size_t a_stride, const void *d_b, size_t b_len, size_t b_stride, size_t rows,
+                             void *d_out /* rows x 32 */, void *stream);
+
 /* The two halves of zk_bn254_groth16_prove, exposed so that one proof can be range-sharded over several GPUs
  * (one process per GPU): every rank runs the five MSMs on ITS slice of the bases / wire values / h, the un-normalised
  * XYZZ sums (4 x G1 = 64 limbs, then G2 = 32 limbs; order A, B1, K, Z, B2) are all-gathered, and any rank finishes.
@@ -790,7 +818,8 @@ enum {
     ZK_ROW_UNSATISFIED = 1,   /* the batch prover's verdict: the solution violates the circuit (PLONK only) */
     ZK_ROW_BAD_HEX = 2,       /* invalid hex character in the row's felts */
     ZK_ROW_NOT_CANONICAL = 3, /* a felt >= r */
-    ZK_ROW_BAD_COUNT = 4      /* the row's count header is not n_values */
+    ZK_ROW_BAD_COUNT = 4,     /* the row's count header is not n_values */
+    ZK_ROW_BAD_PROOF_HEX      /* (the next value: five) the verify-batch entries below: an invalid hex character in the row's proof text */
 };
 int zk_plonk_solutions_rows(const char *acir_json, size_t acir_len, int layout, const char *values_hex, size_t values_len, size_t values_stride,
                             size_t rows, void *d_solutions /* rows x n_vars, device */, size_t sol_stride, int *status_out /* rows, host */);
@@ -803,6 +832,39 @@ int zk_plonk_prove_batch_with_pk(const char *acir_json, size_t acir_len, int lay
 int zk_groth16_prove_batch_with_pk(const char *raw_json, size_t raw_len, const char *values_hex, size_t values_len, size_t values_stride, size_t rows,
                                    const char *pk_hex, size_t pk_len, uint64_t pk_handle, const zk_fr *rs /* NULL or rows x 2 */,
                                    size_t chunk_rows, char *proofs_hex_out /* rows x 256 */, int *status_out /* rows */);
+
+/* MANY PROOF TEXTS OF ONE CIRCUIT PER CALL: the verifying counterpart of the two entries above.  What the export shim's PlonkVerifyWithVK / VerifyWithVK do per
+ * proof -- hex-decode the proof, find the public values in the values text, convert them to Montgomery form, verify -- for `rows` proofs against ONE verifying
+ * key, without a host loop: per chunk the proof texts and the values texts go up in two pitched copies, one launch decodes the proofs
+ * (zk_bn254_bytes_decode_hex_rows_dev), one checks the values texts and decodes the public values (zk_bn254_felts_public_hex_rows_dev), and the rows go to
+ * zk_bn254_plonk_verify_batch_dev / zk_bn254_groth16_verify_batch_dev where they lie.
+ *   proofs_hex     host: row v is the 1096 (256) characters at proofs_hex + v * proofs_stride -- hex of Proof.WriteTo, either letter case.
+ *   values_hex     host, as in the entries above: row v's values_len characters at values_hex + v * values_stride.  The circuit is found or made resident by
+ *                  content as there (host side only: no circuit buffer goes to the device).  The public positions come from the lowering: for PLONK
+ *                  zk_acir_public_witnesses' positions; for Groth16 the public wires after ONE in wire order -- what zk_groth16_public_inputs reads.  The
+ *                  RawR1CS text's own embedded values string only identifies the circuit and is NOT a row.
+ *   vk_hex         the verifying key's hex text; srs_g2: the SRS's ([1]2, [alpha]2) as in zk_bn254_plonk_verify.
+ *   status_out     host, one per row: ZK_ROW_OK, or why the row was not verified -- ZK_ROW_BAD_PROOF_HEX (decided first, as the shim decodes the proof first),
+ *                  ZK_ROW_BAD_COUNT, ZK_ROW_BAD_HEX (EVERY character of the values text is checked: hex.DecodeString sees the whole text),
+ *                  ZK_ROW_NOT_CANONICAL (a PUBLIC felt >= r; a felt >= r at a position that is not public is not an error, as the shim never decodes it).
+ *   accepted       host, one per row.  For any status but ZK_ROW_OK accepted[v] = 0: the row fails neither the call nor its neighbours (it goes through the
+ *                  verifier as zeros, which is a rejected lane).  For a row with ZK_ROW_OK accepted[v] is what the shim's sequence -- hex-decode the proof, take
+ *                  the public values, zk_bn254_plonk_verify / zk_bn254_groth16_verify -- returns for that row's texts; a proof encoding that call refuses
+ *                  with ZK_ERR_ARG is a 0 here.  *n_accepted = the number of ones.
+ *   CHUNKS         at most 2^16 - 1 rows at a time and no more than keeps the staging within 256 MiB, capped by chunk_rows (0 = no cap; it never changes a
+ *                  verdict: the coefficients are derived over the chunk handed to the verifier, and a verdict does not depend on them).  The staging is the
+ *                  call's own and never exceeds one chunk.  No stream slot is held while another is acquired.
+ * The number of public values not matching the key is ZK_ERR_LEN for the call, with upstream's message ("invalid witness size").  ARGUMENT ERRORS, decided
+ * before a device is looked for: a null pointer, a stride below its row with more than one row -> ZK_ERR_ARG; values_len != 8 + 64 * (row 0's count) ->
+ * ZK_ERR_LEN; rows == 0 -> ZK_OK, nothing written.  A malformed key: ZK_ERR_ARG / ZK_ERR_LEN as in the host verifier.  Without a GPU: ZK_ERR_NO_DEVICE after
+ * all of these. */
+int zk_plonk_verify_batch_with_vk(const char *acir_json, size_t acir_len, int layout, const char *proofs_hex, size_t proofs_stride,
+                                  const char *values_hex, size_t values_len, size_t values_stride, size_t rows, const char *vk_hex, size_t vk_len,
+                                  const zk_g2_affine srs_g2[2], size_t chunk_rows, uint8_t *accepted /* rows */, int *status_out /* rows */,
+                                  size_t *n_accepted);
+int zk_groth16_verify_batch_with_vk(const char *raw_json, size_t raw_len, const char *proofs_hex, size_t proofs_stride, const char *values_hex,
+                                    size_t values_len, size_t values_stride, size_t rows, const char *vk_hex, size_t vk_len, size_t chunk_rows,
+                                    uint8_t *accepted /* rows */, int *status_out /* rows */, size_t *n_accepted);
 
 /* What the MSM planner picks for n points (with / without resident window tables): window width c and the number of c-bit
  * digits per scalar, i.e. mixed additions per scalar multiplication -- used by bench.py to turn launches into work. */
@@ -920,6 +982,21 @@ int zk_bn254_felts_decode_bytes_dev(const void *d_raw, size_t raw_len, void *d_o
 int zk_bn254_felts_encode_hex(const void *d_in, size_t n, char *hex_out, size_t cap);
 int zk_bn254_felts_decode_hex_rows_dev(const void *d_text, size_t pitch, size_t rows, size_t n, void *d_out, size_t out_stride,
                                        int to_mont, int *d_status /* rows */, void *stream);
+/* Text rows for the verifiers (zk_plonk_verify_batch_with_vk / zk_groth16_verify_batch_with_vk), everything in HBM, the row a grid dimension (at most 65,535
+ * rows per call), any pitch that holds a row and any alignment of d_text:
+ *   bytes_decode_hex_rows_dev : 2 * n_bytes hex characters per row (row v at d_text + v * pitch) -> n_bytes bytes per row (at d_out + v * out_stride bytes).
+ *                     Both letter cases, as Go's hex.DecodeString.  d_status[v] = ZK_ROW_OK or ZK_ROW_BAD_HEX; a rejected row's bytes are all zero.
+ *   felts_public_hex_rows_dev : row v is a felt-vector text of 8 + 64 * n_values characters.  Its count header is compared with n_values, EVERY character
+ *                     after it is checked for being hex, and only the felts at d_where[0 .. n_public) (device, 0-based positions < n_values; NULL when
+ *                     n_public == 0) are decoded, into Montgomery form, at d_pub + v * pub_stride elements.  d_status[v] = ZK_ROW_OK, ZK_ROW_BAD_COUNT,
+ *                     ZK_ROW_BAD_HEX or ZK_ROW_NOT_CANONICAL (a decoded felt >= r), the first of these that applies; a felt >= r at a position that is not
+ *                     in d_where is not an error.  A rejected row's n_public elements are zeros.
+ * With `stream` the calls only enqueue; stream == NULL runs on a stream of the library's and returns when the launch is complete.  A null pointer, more than
+ * 65,535 rows, a pitch or stride that does not hold a row: ZK_ERR_ARG before a device is looked for; rows == 0: ZK_OK, nothing launched. */
+int zk_bn254_bytes_decode_hex_rows_dev(const void *d_text, size_t pitch, size_t rows, size_t n_bytes, void *d_out, size_t out_stride,
+                                       int *d_status /* rows */, void *stream);
+int zk_bn254_felts_public_hex_rows_dev(const void *d_text, size_t pitch, size_t rows, size_t n_values, const uint32_t *d_where, size_t n_public,
+                                       void *d_pub, size_t pub_stride, int *d_status /* rows */, void *stream);
 
 /* ---- synthetic data on the device (bench / tests; deterministic SplitMix64 streams) -------------- */
 int zk_bn254_fr_random_dev(void *d_out, size_t n, uint64_t seed, int mont, int witness_like, void *stream);

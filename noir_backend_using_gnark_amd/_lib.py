@@ -134,6 +134,8 @@ SYMBOLS = [
     "zk_bn254_msm_bases_rows", "zk_bn254_msm_bases_rows_dev", "zk_bn254_msm_rows_info", "zk_bn254_plonk_commit_batch_dev",
     "zk_bn254_plonk_prove_batch", "zk_bn254_plonk_prove_batch_info", "zk_bn254_plonk_challenges_batch_dev",
     "zk_bn254_felts_decode_hex_rows_dev", "zk_plonk_solutions_rows", "zk_groth16_wires_rows", "zk_plonk_prove_batch_with_pk", "zk_groth16_prove_batch_with_pk",
+    "zk_bn254_groth16_verify_batch_dev", "zk_bn254_plonk_verify_batch_dev", "zk_bn254_rows_sha256_dev", "zk_bn254_bytes_decode_hex_rows_dev",
+    "zk_bn254_felts_public_hex_rows_dev", "zk_plonk_verify_batch_with_vk", "zk_groth16_verify_batch_with_vk",
     "zk_bn254_kzg_open", "zk_bn254_kzg_batch_open_single_point", "zk_bn254_kzg_verify", "zk_bn254_kzg_fold_proof", "zk_bn254_kzg_batch_verify_single_point", "zk_bn254_kzg_verify_batch",
 ]
 
@@ -145,9 +147,17 @@ ARGTYPES = {
     "zk_groth16_wires_rows": [_CP, _SZ, _CP, _SZ, _SZ, _SZ, _VP, _SZ, _VP],
     "zk_plonk_prove_batch_with_pk": [_CP, _SZ, C.c_int, _CP, _SZ, _SZ, _SZ, _CP, _SZ, C.c_uint64, C.c_uint64, _VP, _SZ, _VP, _VP],
     "zk_groth16_prove_batch_with_pk": [_CP, _SZ, _CP, _SZ, _SZ, _SZ, _CP, _SZ, C.c_uint64, _VP, _SZ, _VP, _VP],
+    # the verifying side: device forms of the batch verifiers, the rows' digests, the text rows, the export-path entries
+    "zk_bn254_groth16_verify_batch_dev": [_VP, _SZ, _SZ, _CP, _SZ, C.c_int, _VP, _SZ, _SZ, _VP, _VP],
+    "zk_bn254_plonk_verify_batch_dev": [_VP, _SZ, _SZ, _CP, _SZ, C.c_int, _VP, _VP, _SZ, _SZ, _VP, _VP],
+    "zk_bn254_rows_sha256_dev": [_VP, _SZ, _SZ, _VP, _SZ, _SZ, _SZ, _VP, _VP],
+    "zk_bn254_bytes_decode_hex_rows_dev": [_VP, _SZ, _SZ, _SZ, _VP, _SZ, _VP, _VP],
+    "zk_bn254_felts_public_hex_rows_dev": [_VP, _SZ, _SZ, _SZ, _VP, _SZ, _VP, _SZ, _VP, _VP],
+    "zk_plonk_verify_batch_with_vk": [_CP, _SZ, C.c_int, _CP, _SZ, _CP, _SZ, _SZ, _SZ, _CP, _SZ, _VP, _SZ, _VP, _VP, _VP],
+    "zk_groth16_verify_batch_with_vk": [_CP, _SZ, _CP, _SZ, _CP, _SZ, _SZ, _SZ, _CP, _SZ, _SZ, _VP, _VP, _VP],
 }
 # status of a row of those entries (include/zkmi.h: ZK_ROW_*)
-ROW_OK, ROW_UNSATISFIED, ROW_BAD_HEX, ROW_NOT_CANONICAL, ROW_BAD_COUNT = 0, 1, 2, 3, 4
+ROW_OK, ROW_UNSATISFIED, ROW_BAD_HEX, ROW_NOT_CANONICAL, ROW_BAD_COUNT, ROW_BAD_PROOF_HEX = 0, 1, 2, 3, 4, 5
 
 _lib = None
 

@@ -566,3 +566,29 @@ def fr_batch_invert(a, n: int | None = None):
         return d.to_numpy(np.uint64, a.shape)
     finally:
         d.free()
+
+
+def rows_sha256(a, b=None, a_stride: int | None = None, b_stride: int | None = None, fill: int = 0) -> np.ndarray:
+    """SHA-256(a_v || b_v) for every row v, one lane per row on the device (zk_bn254_rows_sha256_dev) -> (rows, 32) uint8.  a, b: (rows, len) uint8 arrays
+    (either may be None or of length 0); they are staged a_stride / b_stride bytes apart (default: packed), the gaps filled with `fill`, which no digest sees."""
+    a = np.zeros((0, 0), np.uint8) if a is None else np.ascontiguousarray(a, dtype=np.uint8)
+    b = np.zeros((len(a), 0), np.uint8) if b is None else np.ascontiguousarray(b, dtype=np.uint8)
+    if a.shape[1] == 0 and len(a) != len(b):
+        a = np.zeros((len(b), 0), np.uint8)
+    if len(a) != len(b):
+        raise ValueError("as many rows of a as of b")
+    rows = len(a)
+
+    def stage(x, stride):
+        stride = x.shape[1] if stride is None else stride
+        if stride < x.shape[1]:
+            raise ValueError("stride below a row")
+        buf = np.full((max(rows, 1), max(stride, 1)), fill, np.uint8)
+        buf[:rows, :x.shape[1]] = x
+        return _lib.DeviceBuffer.from_numpy(buf), stride
+
+    d_a, sa = stage(a, a_stride)
+    d_b, sb = stage(b, b_stride)
+    d_out = _lib.DeviceBuffer(max(rows, 1) * 32)
+    check(lib().zk_bn254_rows_sha256_dev(d_a.ptr if a.shape[1] else None, a.shape[1], sa, d_b.ptr if b.shape[1] else None, b.shape[1], sb, rows, d_out.ptr, None))
+    return d_out.to_numpy(np.uint8, (rows, 32))

@@ -1643,6 +1643,179 @@ int zk_groth16_prove_batch_with_pk(const char* raw_json, size_t raw_len, const c
     return ZK_OK;
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ many proof texts of ONE circuit per call
+// The verifying counterpart (zkmi.h): what goffi.cpp's PlonkVerifyWithVK / VerifyWithVK do per proof on the host -- hex-decode the proof, find the public values
+// in the values text, convert them -- as two launches per chunk (wire.hip), the rows then verified where they lie (verify_batch.hip's device forms).  Of the
+// resident circuit only the host list of public positions is read: nothing of it goes to the device, no mutex of it is taken.
+namespace zkmi {
+
+int bytes_decode_hex_rows_on_slot(Slot* s, hipStream_t st, const void* d_text, size_t pitch, size_t rows, size_t n_bytes, void* d_out, size_t out_stride, int* d_status);  // wire.hip
+int felts_public_hex_rows_on_slot(Slot* s, hipStream_t st, const void* d_text, size_t pitch, size_t rows, size_t n_values, const uint32_t* d_where, size_t n_public,
+                                  void* d_pub, size_t pub_stride, int* d_status);  // wire.hip
+
+// the staging of one chunk: both texts (the values at RowStage's pitch: every row's felts on a 16-byte boundary), the decoded proofs at a stride that keeps
+// them word-aligned, the public inputs, the rows' verdicts, the public positions
+struct VerifyStage {
+    char *d_ptext = nullptr, *d_vtext = nullptr;
+    uint8_t* d_proofs = nullptr;
+    void* d_pub = nullptr;
+    int* d_status = nullptr;  // cap for the proofs, cap for the values
+    uint32_t* d_where = nullptr;
+    size_t cap = 0, proof_bytes = 0, proof_stride = 0, n_values = 0, n_public = 0, vpitch = 0;
+    std::vector<int> st;
+    VerifyStage() = default;
+    VerifyStage(const VerifyStage&) = delete;
+    VerifyStage& operator=(const VerifyStage&) = delete;
+    ~VerifyStage() {
+        for (void* q : {(void*)d_ptext, (void*)d_vtext, (void*)d_proofs, d_pub, (void*)d_status, (void*)d_where})
+            if (q) (void)hipFree(q);
+    }
+    static size_t bytes_per_row(size_t pb, size_t n, size_t np) { return 2 * pb + (64 * n + 16) + (pb + 15) / 16 * 16 + 32 * np + 8; }
+    int make(size_t rows, size_t pb, size_t n, const std::vector<uint32_t>& where) {
+        cap = rows;
+        proof_bytes = pb;
+        proof_stride = (pb + 15) / 16 * 16;
+        n_values = n;
+        n_public = where.size();
+        vpitch = 64 * n + 16;
+        st.assign(2 * rows, 0);
+        ZK_HIP(hipMalloc((void**)&d_ptext, rows * 2 * pb));
+        ZK_HIP(hipMalloc((void**)&d_vtext, rows * vpitch + 16));
+        ZK_HIP(hipMalloc((void**)&d_proofs, rows * proof_stride));
+        ZK_HIP(hipMalloc(&d_pub, (rows * n_public ? rows * n_public : 1) * 32));
+        ZK_HIP(hipMalloc((void**)&d_status, 2 * rows * sizeof(int)));
+        ZK_HIP(hipMalloc((void**)&d_where, (n_public ? n_public : 1) * 4));
+        if (n_public) ZK_HIP(hipMemcpy(d_where, where.data(), n_public * 4, hipMemcpyHostToDevice));
+        return ZK_OK;
+    }
+    // R <= cap rows: both texts up, both decoders, the verdicts down; status[v] = ZK_ROW_*.  Takes one stream slot and gives it back.
+    int rows_to_device(const char* proofs, size_t proofs_stride, const char* values, size_t values_len, size_t values_stride, size_t R, int* status) {
+        Phase ph;
+        {
+            SlotGuard g;
+            ZK_TRY(acquire_slot(&g.s));
+            hipStream_t s = g.s->stream;
+            int rc = ZK_OK;
+            auto up = [&](char* dst, size_t pitch, const char* src, size_t src_stride, size_t width) -> int {
+                if (R == 1) ZK_HIP(hipMemcpyAsync(dst, src, width, hipMemcpyHostToDevice, s));  // (one row's stride may be anything)
+                else ZK_HIP(hipMemcpy2DAsync(dst, pitch, src, src_stride, width, R, hipMemcpyHostToDevice, s));
+                return ZK_OK;
+            };
+            rc = up(d_ptext, 2 * proof_bytes, proofs, proofs_stride, 2 * proof_bytes);
+            if (rc == ZK_OK) rc = up(d_vtext + 8, vpitch, values, values_stride, values_len);
+            if (rc == ZK_OK) rc = bytes_decode_hex_rows_on_slot(g.s, s, d_ptext, 2 * proof_bytes, R, proof_bytes, d_proofs, proof_stride, d_status);
+            if (rc == ZK_OK) rc = felts_public_hex_rows_on_slot(g.s, s, d_vtext + 8, vpitch, R, n_values, d_where, n_public, d_pub, n_public, d_status + cap);
+            if (rc == ZK_OK && hipMemcpyAsync(st.data(), d_status, 2 * cap * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess)
+                rc = set_err(ZK_ERR_HIP, "download of the rows' verdicts failed");
+            const int rs = slot_sync(g.s, s);  // also on an error: what was enqueued drains before the caller's texts go
+            ZK_TRY(rc);
+            ZK_TRY(rs);
+        }
+        for (size_t v = 0; v < R; v++) status[v] = st[v] != ZK_ROW_OK ? (int)ZK_ROW_BAD_PROOF_HEX : st[cap + v];  // (the shim decodes the proof first)
+        ph.lap("export.batch_verify_rows");
+        return ZK_OK;
+    }
+};
+
+static int verify_rows_args(const void* circuit, const char* proofs_hex, size_t proofs_stride, size_t proof_chars, const char* values_hex, size_t values_len,
+                            size_t values_stride, size_t rows, const void* vk_hex, const void* accepted, const int* status_out, const size_t* n_accepted) {
+    if (!circuit || !proofs_hex || !values_hex || !vk_hex || !accepted || !status_out || !n_accepted) return set_err(ZK_ERR_ARG, "null pointer");
+    if (rows > 1 && values_stride < values_len) return set_err(ZK_ERR_ARG, "values_stride = %zu is below the %zu characters of a row", values_stride, values_len);
+    if (rows > 1 && proofs_stride < proof_chars) return set_err(ZK_ERR_ARG, "proofs_stride = %zu is below the %zu characters of a proof", proofs_stride, proof_chars);
+    return ZK_OK;
+}
+// rows per chunk: what keeps the staging within 256 MiB, and the row a grid dimension
+static size_t verify_chunk(size_t rows, size_t chunk_rows, size_t pb, size_t n_values, size_t n_public) {
+    const size_t fit = ((size_t)256 << 20) / VerifyStage::bytes_per_row(pb, n_values, n_public);
+    size_t chunk = std::max<size_t>(1, std::min(rows, std::min<size_t>(fit, 65535)));
+    if (chunk_rows) chunk = std::min(chunk, chunk_rows);
+    return chunk;
+}
+// a row that was not verified is not accepted, whatever its zero-filled form made of the verifier
+static void verdicts_of_chunk(const int* status, size_t R, uint8_t* accepted, size_t* n_accepted) {
+    for (size_t v = 0; v < R; v++) {
+        if (status[v] != ZK_ROW_OK) accepted[v] = 0;
+        *n_accepted += accepted[v] ? 1 : 0;
+    }
+}
+
+}  // namespace zkmi
+
+extern "C" {
+
+int zk_plonk_verify_batch_with_vk(const char* acir_json, size_t acir_len, int layout, const char* proofs_hex, size_t proofs_stride, const char* values_hex,
+                                  size_t values_len, size_t values_stride, size_t rows, const char* vk_hex, size_t vk_len, const zk_g2_affine srs_g2[2],
+                                  size_t chunk_rows, uint8_t* accepted, int* status_out, size_t* n_accepted) {
+    InFlight _in_flight;
+    ZK_TRY(verify_rows_args(acir_json, proofs_hex, proofs_stride, 2 * ZK_PLONK_PROOF_BYTES, values_hex, values_len, values_stride, rows, vk_hex, accepted, status_out,
+                            n_accepted));
+    if (!srs_g2) return set_err(ZK_ERR_ARG, "null pointer");
+    if (rows == 0) return ZK_OK;
+    size_t n_values = 0;
+    ZK_TRY(rows_n_values(values_hex, values_len, &n_values));
+    std::shared_ptr<Lowered> L;
+    ZK_TRY(lowered_get(acir_json, acir_len, n_values, layout, &L, nullptr));
+    const std::vector<uint32_t> where(L->order_public.begin(), L->order_public.begin() + L->n_public);
+    for (uint32_t at : where)
+        if (at >= n_values) return set_err(ZK_ERR_ARG, "public witness %u is outside the %zu values of a row", at + 1, n_values);
+    size_t total = 0;
+    // the key and the number of public values against it, with the verifier's own codes and messages (no proofs: it stops before it looks for a device)
+    ZK_TRY(zk_bn254_plonk_verify_batch_dev(nullptr, 0, 0, vk_hex, vk_len, 1, srs_g2, nullptr, 0, where.size(), nullptr, &total));
+    ZK_TRY(ensure_init());
+    const size_t chunk = verify_chunk(rows, chunk_rows, ZK_PLONK_PROOF_BYTES, n_values, where.size());
+    VerifyStage S;
+    ZK_TRY(S.make(chunk, ZK_PLONK_PROOF_BYTES, n_values, where));
+    for (size_t first = 0; first < rows; first += chunk) {
+        const size_t R = std::min(chunk, rows - first);
+        ZK_TRY(S.rows_to_device(proofs_hex + first * proofs_stride, proofs_stride, values_hex + first * values_stride, values_len, values_stride, R,
+                                status_out + first));  // (its slot is back)
+        Phase ph;
+        size_t n_ok = 0;
+        ZK_TRY(zk_bn254_plonk_verify_batch_dev(S.d_proofs, S.proof_stride, R, vk_hex, vk_len, 1, srs_g2, S.d_pub, S.n_public, S.n_public, accepted + first, &n_ok));
+        verdicts_of_chunk(status_out + first, R, accepted + first, &total);
+        ph.lap("export.batch_plonk_verify");
+    }
+    *n_accepted = total;
+    return ZK_OK;
+}
+
+int zk_groth16_verify_batch_with_vk(const char* raw_json, size_t raw_len, const char* proofs_hex, size_t proofs_stride, const char* values_hex, size_t values_len,
+                                    size_t values_stride, size_t rows, const char* vk_hex, size_t vk_len, size_t chunk_rows, uint8_t* accepted, int* status_out,
+                                    size_t* n_accepted) {
+    InFlight _in_flight;
+    ZK_TRY(verify_rows_args(raw_json, proofs_hex, proofs_stride, 256, values_hex, values_len, values_stride, rows, vk_hex, accepted, status_out, n_accepted));
+    if (rows == 0) return ZK_OK;
+    {
+        size_t n = 0;
+        ZK_TRY(rows_n_values(values_hex, values_len, &n));
+    }
+    std::shared_ptr<RawCircuit> C;
+    ZK_TRY(raw_circuit_for_rows(raw_json, raw_len, values_len, &C));
+    const std::vector<uint32_t> where(C->public_order.begin(), C->public_order.end());
+    for (uint32_t at : where)
+        if (at >= C->n_values) return set_err(ZK_ERR_ARG, "public witness %u is outside the %zu values of a row", at + 1, C->n_values);
+    size_t total = 0;
+    ZK_TRY(zk_bn254_groth16_verify_batch_dev(nullptr, 0, 0, vk_hex, vk_len, 1, nullptr, 0, where.size(), nullptr, &total));  // as above
+    ZK_TRY(ensure_init());
+    const size_t chunk = verify_chunk(rows, chunk_rows, 128, C->n_values, where.size());
+    VerifyStage S;
+    ZK_TRY(S.make(chunk, 128, C->n_values, where));
+    for (size_t first = 0; first < rows; first += chunk) {
+        const size_t R = std::min(chunk, rows - first);
+        ZK_TRY(S.rows_to_device(proofs_hex + first * proofs_stride, proofs_stride, values_hex + first * values_stride, values_len, values_stride, R,
+                                status_out + first));  // (its slot is back)
+        Phase ph;
+        size_t n_ok = 0;
+        ZK_TRY(zk_bn254_groth16_verify_batch_dev(S.d_proofs, S.proof_stride, R, vk_hex, vk_len, 1, S.d_pub, S.n_public, S.n_public, accepted + first, &n_ok));
+        verdicts_of_chunk(status_out + first, R, accepted + first, &total);
+        ph.lap("export.batch_groth16_verify");
+    }
+    *n_accepted = total;
+    return ZK_OK;
+}
+
 // Releases everything the export path keeps resident between calls (lowered circuits, decoded proving keys; PLONK and Groth16).  Keys in use by a running proof stay.
 int zk_export_cache_clear(void) {
     (void)zk_background_wait(-1);  // a background table build pins its key: let it finish so that the key can go

@@ -5,8 +5,12 @@
 //   combine        the lanes' points times their coefficients, summed by halving folds (k_g1_fold / k_fr_fold); the host adds the fixed-key terms
 //   check          Miller loops over the folded points, the product tree, one final exponentiation: a product of one accepts every valid lane
 //   fallback       (only when the check fails) each valid lane's own Miller loops, a final exponentiation and a verdict per lane
+// The Groth16 and PLONK verifiers have two forms over one core each (groth16_verify_rows, plonk_verify_rows; RowsIn says where the rows are): the host-input
+// entries, whose chunks go up into the workspace, and the _dev entries, which read proofs and public inputs where they lie in HBM, a stride apart.  The core takes
+// the coefficients' prefix from its entry: the host form hashes proofs || public inputs on the host as it always did, the device form hashes one digest per row on
+// the device (k_rows_digest) and the digests on the host -- under another tag, so the two derivations never meet.
 // What each adds (the kernels say the rest):
-//   groth16 (one lane per proof)   k_g1_decompress / k_g2_decompress with a flag per invalid point; k_vb_prep: r_i Ar_i, r_i Krs_i, r_i (1, w_i1, ..); check: n' + 3
+//   groth16 (one lane per proof)   k_vb_gather (the proof's three slots into the decompressors' arrays); k_g1_decompress / k_g2_decompress with a flag per invalid point; k_vb_prep: r_i Ar_i, r_i Krs_i, r_i (1, w_i1, ..); check: n' + 3
 //       lanes, prod e(r_i Ar_i, Bs_i) e(-c_0 alpha, beta) e(-sum c_j K_j, gamma) e(-sum r_i Krs_i, delta) == 1; fallback: k_vb_single, 3 n + 1 lanes (the last: e(alpha, beta))
 //   plonk (one lane per proof)   k_pv_gather, k_g1_decompress, k_pv_transcript, k_pv_scalars, k_pv_smul + k_pv_digests, k_pv_kzg, k_pv_smul +
 //       k_pv_combine (A_i, B_i); check: 2 lanes, e(sum A + the G, S1, S2 terms, [1]2) e(-sum B, [alpha]2) == 1; fallback: k_pv_smul + k_pv_single, 2 n lanes
@@ -129,10 +133,48 @@ __global__ __launch_bounds__(256) void k_fr_fold(const Fr* __restrict__ in, size
     out[t] = a;
 }
 
+// The rows of a call as the kernels below read them: row i's proof bytes at proofs + i * stride (any alignment), its public inputs at pub + i * ps elements.
+// A little-endian word of a row:
+ZK_D uint32_t row_word(const uint8_t* p, bool aligned) {
+    if (aligned) return *reinterpret_cast<const uint32_t*>(p);
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+// d_v = SHA-256(a_v || b_v), one lane per row (zkmi.h: zk_bn254_rows_sha256_dev; the device forms of the verifiers derive their coefficients from these)
+__global__ __launch_bounds__(64) void k_rows_digest(const uint8_t* __restrict__ a, size_t a_len, size_t a_stride, const uint8_t* __restrict__ b, size_t b_len,
+                                                    size_t b_stride, size_t rows, uint8_t* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    Sha256Dev h;
+    h.reset();
+    if (a_len) h.update(a + i * a_stride, a_len);
+    if (b_len) h.update(b + i * b_stride, b_len);
+    uint32_t d[8];
+    h.final(d);
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) out[32 * i + 4 * k + j] = (uint8_t)(d[k] >> (24 - 8 * j));
+}
+
+// the 128-byte Groth16 proof into the arrays the decompressors read: raw = Ar (n x 32 bytes) | Bs (n x 64) | Krs (n x 32), as words
+__global__ __launch_bounds__(256) void k_vb_gather(const uint8_t* __restrict__ proofs, size_t stride, size_t n, uint32_t* __restrict__ raw) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t* p = proofs + i * stride;
+    const bool al = ((uintptr_t)p & 3) == 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) raw[i * 8 + j] = row_word(p + 4 * j, al);
+#pragma unroll
+    for (int j = 0; j < 16; j++) raw[n * 8 + i * 16 + j] = row_word(p + 32 + 4 * j, al);
+#pragma unroll
+    for (int j = 0; j < 8; j++) raw[n * 24 + i * 8 + j] = row_word(p + 96 + 4 * j, al);
+}
+
 // per proof: valid = no invalid point; r_i Ar_i (affine; infinity when invalid), r_i Krs_i, and the row r_i (1, w_i1, .., w_i,np) of the mat-vec
 __global__ __launch_bounds__(128) void k_vb_prep(const Affine<Fp>* __restrict__ ar, const Affine<Fp>* __restrict__ krs, const uint8_t* __restrict__ bad,
-                                                 const uint32_t* __restrict__ rr, const Fr* __restrict__ pub, size_t n, size_t np, uint8_t* __restrict__ valid,
-                                                 Affine<Fp>* __restrict__ p_out, XYZZ<Fp>* __restrict__ rk_out, Fr* __restrict__ terms) {
+                                                 const uint32_t* __restrict__ rr, const Fr* __restrict__ pub, size_t ps, size_t n, size_t np,
+                                                 uint8_t* __restrict__ valid, Affine<Fp>* __restrict__ p_out, XYZZ<Fp>* __restrict__ rk_out, Fr* __restrict__ terms) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const bool ok = !(bad[i] | bad[n + i] | bad[2 * n + i]);
@@ -142,7 +184,7 @@ __global__ __launch_bounds__(128) void k_vb_prep(const Affine<Fp>* __restrict__ 
     for (int j = 0; j < 4; j++) rm.l[j] = k[j];
     rm = ok ? rm.to_mont() : Fr::zero();
     terms[i * (np + 1)] = rm;
-    for (size_t j = 0; j < np; j++) terms[i * (np + 1) + 1 + j] = rm * pub[i * np + j];
+    for (size_t j = 0; j < np; j++) terms[i * (np + 1) + 1 + j] = rm * pub[i * ps + j];
     if (!ok) {
         p_out[i] = Affine<Fp>::inf();
         rk_out[i] = XYZZ<Fp>::inf();
@@ -153,7 +195,7 @@ __global__ __launch_bounds__(128) void k_vb_prep(const Affine<Fp>* __restrict__ 
 }
 // fallback, per proof: P[i] = -Ar_i, P[n + i] = IC_i = K_0 + sum_j w_ij K_j, P[2 n + i] = Krs_i (all infinity when the proof is invalid)
 __global__ __launch_bounds__(128) void k_vb_single(const Affine<Fp>* __restrict__ ar, const Affine<Fp>* __restrict__ krs, const uint8_t* __restrict__ valid,
-                                                   const Fr* __restrict__ pub, const Affine<Fp>* __restrict__ kpts, size_t n, size_t np,
+                                                   const Fr* __restrict__ pub, size_t ps, const Affine<Fp>* __restrict__ kpts, size_t n, size_t np,
                                                    Affine<Fp>* __restrict__ P) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -165,7 +207,7 @@ __global__ __launch_bounds__(128) void k_vb_single(const Affine<Fp>* __restrict_
     P[2 * n + i] = krs[i];
     XYZZ<Fp> ic = XYZZ<Fp>::from_affine(kpts[0]);
     for (size_t j = 0; j < np; j++) {
-        const Fr w = pub[i * np + j].from_mont();
+        const Fr w = pub[i * ps + j].from_mont();
         ic.add(scalar_mul(kpts[1 + j], w.l));
     }
     P[n + i] = ic.to_affine();
@@ -206,25 +248,31 @@ ZK_D Fr fr_from_be_words(const uint32_t* p) {
 }
 
 // header (bytes 256..259 = 00 00 00 07), the nine compressed points into their own arrays, the eight values reduced mod r
-__global__ __launch_bounds__(256) void k_pv_gather(const uint32_t* __restrict__ proofs, size_t n, uint32_t* __restrict__ praw, Fr* __restrict__ sc,
+__global__ __launch_bounds__(256) void k_pv_gather(const uint8_t* __restrict__ proofs, size_t stride, size_t n, uint32_t* __restrict__ praw, Fr* __restrict__ sc,
                                                    uint8_t* __restrict__ hdr_bad) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint32_t* p = proofs + i * (548 / 4);
+    const uint8_t* p = proofs + i * stride;
+    const bool al = ((uintptr_t)p & 3) == 0;
     const int off[PV_NPTS] = {0, 8, 16, 24, 32, 40, 48, 56, 121};
 #pragma unroll
     for (int k = 0; k < PV_NPTS; k++)
 #pragma unroll
-        for (int j = 0; j < 8; j++) praw[(k * n + i) * 8 + j] = p[off[k] + j];
-    hdr_bad[i] = p[64] != 0x07000000u;  // little-endian read of 00 00 00 07
+        for (int j = 0; j < 8; j++) praw[(k * n + i) * 8 + j] = row_word(p + 4 * (off[k] + j), al);
+    hdr_bad[i] = row_word(p + 4 * 64, al) != 0x07000000u;  // little-endian read of 00 00 00 07
 #pragma unroll 1
-    for (int k = 0; k < 8; k++) sc[(PV_CLAIM + k) * n + i] = fr_from_be_words(p + (k < 7 ? 65 + 8 * k : 129));
+    for (int k = 0; k < 8; k++) {
+        uint32_t w[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) w[j] = row_word(p + 4 * ((k < 7 ? 65 + 8 * k : 129) + j), al);
+        sc[(PV_CLAIM + k) * n + i] = fr_from_be_words(w);
+    }
 }
 
 // gamma, beta, alpha, zeta as FsTranscript derives them.  gamma's prefix ("gamma" || S1..Qk) is the same for every lane: the host hashed its whole blocks
 // (mid = the chaining value after mid_len bytes) and pre holds the rest, then "beta", "alpha", "zeta"
 __global__ __launch_bounds__(64) void k_pv_transcript(const Affine<Fp>* __restrict__ pts, const uint8_t* __restrict__ bad, const uint8_t* __restrict__ hdr_bad,
-                                                      const Fr* __restrict__ pub, size_t n, size_t np, const uint32_t* __restrict__ mid, uint64_t mid_len,
+                                                      const Fr* __restrict__ pub, size_t ps, size_t n, size_t np, const uint32_t* __restrict__ mid, uint64_t mid_len,
                                                       const uint8_t* __restrict__ pre, uint32_t tail_len, uint8_t* __restrict__ valid, Fr* __restrict__ sc) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -247,7 +295,7 @@ __global__ __launch_bounds__(64) void k_pv_transcript(const Affine<Fp>* __restri
         for (size_t j = 0; j < items; j++) {
             uint32_t l[8];
             if (c == 0 && j < np) {
-                const Fr w = pub[i * np + j].from_mont();
+                const Fr w = pub[i * ps + j].from_mont();
 #pragma unroll
                 for (int k = 0; k < 8; k++) l[k] = w.l[k];
             } else {
@@ -266,7 +314,7 @@ __global__ __launch_bounds__(64) void k_pv_transcript(const Affine<Fp>* __restri
 
 // zeta^n, PI(zeta), L1(zeta) and the quotient identity (a lane that fails it is invalid from here on); the digests' scalars.
 // PI(zeta) = sum_j w^j / n (zeta^n - 1) w_j / (zeta - w^j) accumulates as one fraction N / D: one inversion for all denominators
-__global__ __launch_bounds__(64) void k_pv_scalars(const Fr* __restrict__ pub, size_t n, size_t np, PvKey K, uint8_t* __restrict__ valid, Fr* __restrict__ sc) {
+__global__ __launch_bounds__(64) void k_pv_scalars(const Fr* __restrict__ pub, size_t ps, size_t n, size_t np, PvKey K, uint8_t* __restrict__ valid, Fr* __restrict__ sc) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || !valid[i]) return;
     const Fr one = Fr::one();
@@ -277,7 +325,7 @@ __global__ __launch_bounds__(64) void k_pv_scalars(const Fr* __restrict__ pub, s
     Fr num = Fr::zero(), den = one, wi = one;
     for (size_t j = 0; j < np; j++) {
         const Fr d = zeta - wi;
-        num = num * d + wi * szz * pub[i * np + j] * den;
+        num = num * d + wi * szz * pub[i * ps + j] * den;
         den = den * d;
         wi = wi * K.gen;
     }
@@ -286,7 +334,7 @@ __global__ __launch_bounds__(64) void k_pv_scalars(const Fr* __restrict__ pub, s
         pi = Fr::zero();
         wi = one;
         for (size_t j = 0; j < np; j++) {
-            pi = pi + wi * szz * (zeta - wi).inv() * pub[i * np + j];
+            pi = pi + wi * szz * (zeta - wi).inv() * pub[i * ps + j];
             wi = wi * K.gen;
         }
     }
@@ -336,10 +384,10 @@ __global__ __launch_bounds__(64) void k_pv_digests(const Affine<Fp>* __restrict_
 }
 
 // kzg.deriveGamma over zeta, the seven digests and the claimed values, then the lane's coefficients rho, rho' (SHA-256 of the host's prefix -- mid after 64
-// bytes, then rtail -- || u64 index || tag byte) and the scalars of  rho (D - e G + zeta W) + rho' (Z - zu G + zeta omega W')  and  rho W + rho' W':
+// bytes, then rtail's rtail_len -- || u64 index || tag byte) and the scalars of  rho (D - e G + zeta W) + rho' (Z - zu G + zeta omega W')  and  rho W + rho' W':
 // per-lane terms into PV_T.., the fixed points' coefficients (G, S1, S2) into fix (columns) and fold (rows, k_fr_fold's input)
 __global__ __launch_bounds__(64) void k_pv_kzg(const Affine<Fp>* __restrict__ pts, const Affine<Fp>* __restrict__ dig, const Affine<Fp>* __restrict__ kpts, size_t n,
-                                               size_t c0, PvKey K, const uint32_t* __restrict__ rmid, const uint8_t* __restrict__ rtail,
+                                               size_t c0, PvKey K, const uint32_t* __restrict__ rmid, const uint8_t* __restrict__ rtail, uint32_t rtail_len,
                                                const uint8_t* __restrict__ valid, Fr* __restrict__ sc, Fr* __restrict__ fix, Fr* __restrict__ fold) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -385,7 +433,8 @@ __global__ __launch_bounds__(64) void k_pv_kzg(const Affine<Fp>* __restrict__ pt
         Sha256Dev h;
         h.resume(rmid, 64);
 #pragma unroll 1
-        for (int k = 0; k < 48 + 8 + 1; k++) h.put_byte(k < 48 ? rtail[k] : k < 56 ? (uint32_t)(idx >> (8 * (k - 48))) : (uint32_t)tag);
+        for (uint32_t k = 0; k < rtail_len + 8 + 1; k++)
+            h.put_byte(k < rtail_len ? rtail[k] : k < rtail_len + 8 ? (uint32_t)(idx >> (8 * (k - rtail_len))) : (uint32_t)tag);
         uint32_t dg[8];
         h.final(dg);
         uint32_t l[8];
@@ -589,6 +638,150 @@ struct PairCheck {
     }
 };
 
+// Where the rows of a Groth16 / PLONK batch are.  on_device: read where they lie, row i's proof at proofs + i * proof_stride bytes and its public inputs at
+// pub + i * pub_stride elements.  Otherwise host memory, packed (the strides are the rows): each chunk goes up into the call's workspace first.
+struct RowsIn {
+    const uint8_t* proofs;
+    size_t proof_stride;
+    const Fr* pub;
+    size_t pub_stride;
+    bool on_device;
+};
+// a chunk's rows in HBM: d_stage / d_pub are the workspace's (proof_bytes and np elements per row)
+int rows_of_chunk(const RowsIn& in, hipStream_t st, size_t c0, size_t n, size_t proof_bytes, size_t np, uint8_t* d_stage, Fr* d_pub, RowsIn* at) {
+    if (in.on_device) {
+        *at = RowsIn{in.proofs + c0 * in.proof_stride, in.proof_stride, np ? in.pub + c0 * in.pub_stride : nullptr, in.pub_stride, true};
+        return ZK_OK;
+    }
+    ZK_HIP(hipMemcpyAsync(d_stage, in.proofs + c0 * proof_bytes, n * proof_bytes, hipMemcpyHostToDevice, st));
+    if (np) ZK_HIP(hipMemcpyAsync(d_pub, in.pub + c0 * np, n * np * 32, hipMemcpyHostToDevice, st));
+    *at = RowsIn{d_stage, proof_bytes, d_pub, np, true};
+    return ZK_OK;
+}
+int rows_in_args(const void* d_proofs, size_t proof_stride, size_t proof_bytes, size_t n_proofs, const void* d_pub, size_t pub_stride, size_t n_public) {
+    if (n_proofs > 1 && proof_stride < proof_bytes) return set_err(ZK_ERR_ARG, "proof_stride = %zu is below the %zu bytes of a proof", proof_stride, proof_bytes);
+    if (n_proofs > 1 && pub_stride < n_public) return set_err(ZK_ERR_ARG, "pub_stride = %zu is below the %zu public inputs of a row", pub_stride, n_public);
+    return ZK_OK;
+}
+
+// d_out[32 v ..] = SHA-256(a_v || b_v) for `rows` rows, enqueued on st
+void rows_digest_launch(Slot* s, hipStream_t st, const void* d_a, size_t a_len, size_t a_stride, const void* d_b, size_t b_len, size_t b_stride, size_t rows,
+                        void* d_out) {
+    ZK_LAUNCH(s, st, "rows_digest", k_rows_digest, dim3(blocks(rows, 64)), dim3(64), 0, (const uint8_t*)d_a, a_len, a_stride, (const uint8_t*)d_b, b_len, b_stride, rows,
+              (uint8_t*)d_out);
+}
+// D = SHA-256(d_0 || .. || d_{n-1}), d_v = SHA-256(row v's proof bytes || its public inputs as they lie in memory): what stands for the host entries'
+// SHA-256(proofs || public inputs) in the device forms (zkmi.h).  A slot of its own, given back before the verifier takes one; 32 bytes per row come down.
+int rows_digest_of_call(const RowsIn& in, size_t proof_bytes, size_t n, size_t np, uint8_t D[32]) {
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    Slot* s = g.s;
+    hipStream_t st = s->stream;
+    uint8_t* d_dig;
+    ZK_TRY(plan_workspace(s, "rows_digest", [&](ArenaPlan& p) { p.take(n * 32, d_dig); }));
+    rows_digest_launch(s, st, in.proofs, proof_bytes, in.proof_stride, in.pub, np * 32, in.pub_stride * 32, n, d_dig);
+    std::vector<uint8_t> dig(n * 32);
+    ZK_HIP(hipMemcpyAsync(dig.data(), d_dig, n * 32, hipMemcpyDeviceToHost, st));
+    ZK_TRY(slot_sync(s, st));
+    sha(D, dig.data(), dig.size());
+    return ZK_OK;
+}
+
+// groth16.Verify for the rows `in` against the parsed key.  pre: the coefficients' prefix, tag || SHA-256(vk) || the call's data digest || 8 bytes for the index:
+// r_i = batch_coeff(SHA-256(pre with i)) -- the entry's to derive (zkmi.h states both derivations), so that one core serves the host and the device form
+int groth16_verify_rows(const Groth16Vk& v, const RowsIn& in, size_t n_proofs, size_t np, std::vector<uint8_t>& pre, uint8_t* accepted, size_t* n_accepted) {
+    const PairConsts K = pair_consts();
+    const size_t nk = v.K.size(), cols = np + 1;
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    Slot* s = g.s;
+    hipStream_t st = s->stream;
+    const size_t ch = std::min(n_proofs, CHUNK);
+    PairCheck pc(s, K, ch);
+    uint8_t *d_stage, *d_bad;
+    uint32_t* d_raw;  // Ar | Bs | Krs, each contiguous
+    Affine<Fp> *d_ar, *d_krs, *d_p, *d_kpts;
+    Affine<Fp2> *d_bs, *d_fix;
+    uint32_t* d_rr;
+    Fr* d_pub;
+    FoldPair<XYZZ<Fp>> rk_fold;
+    FoldPair<Fr> terms;
+    int* d_status;
+    ZK_TRY(plan_workspace(s, "groth16_verify_batch", [&](ArenaPlan& p) {
+        p.take(in.on_device ? 1 : ch * 128, d_stage);
+        p.take(ch * 32, d_raw);
+        p.take(ch, d_ar, d_krs, d_bs);
+        p.take(ch * 3, d_bad);
+        p.take(ch * 4, d_rr);
+        p.take(in.on_device ? 1 : std::max(ch * np, (size_t)1), d_pub);
+        rk_fold.layout(p, ch);
+        terms.layout(p, ch, cols);
+        p.take(3 * ch + 3, d_p);
+        pc.layout(p, 3 * ch + 3);
+        p.take(nk, d_kpts);
+        p.take(3, d_fix);
+        p.take(16, d_status);
+        p.later(ch * G2_DECOMPRESS_SCRATCH);  // g2_decompress_dev's, per chunk
+    }));
+    ZK_HIP(hipMemcpyAsync(d_kpts, v.K.data(), nk * 64, hipMemcpyHostToDevice, st));
+    const size_t arena_mark = s->arena_off;  // g2_decompress_dev takes its scratch from the arena per call: give it back per chunk
+
+    std::vector<uint32_t> rr(ch * 4);
+    for (size_t c0 = 0; c0 < n_proofs; c0 += ch) {
+        const size_t n = std::min(ch, n_proofs - c0);
+        s->arena_off = arena_mark;
+        RowsIn at;
+        ZK_TRY(rows_of_chunk(in, st, c0, n, 128, np, d_stage, d_pub, &at));
+        batch_coeffs(pre.data(), pre.size(), pre.size() - 8, c0, n, rr.data());
+        ZK_HIP(hipMemcpyAsync(d_rr, rr.data(), n * 16, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemsetAsync(d_bad, 0, n * 3, st));
+        ZK_HIP(hipMemsetAsync(d_status, 0, 4, st));
+        ZK_LAUNCH(s, st, "vb_gather", k_vb_gather, dim3(blocks(n, 256)), dim3(256), 0, at.proofs, at.proof_stride, n, d_raw);
+        const uint8_t* raw = (const uint8_t*)d_raw;
+        ZK_TRY(g1_decompress_dev(s, st, raw, n, d_ar, d_status, d_bad));
+        ZK_TRY(g2_decompress_dev(s, st, raw + n * 32, n, d_bs, d_status, d_bad + n));
+        ZK_TRY(g1_decompress_dev(s, st, raw + n * 96, n, d_krs, d_status, d_bad + 2 * n));
+        ZK_LAUNCH(s, st, "vb_prep", k_vb_prep, dim3(blocks(n, 128)), dim3(128), 0, (const Affine<Fp>*)d_ar, (const Affine<Fp>*)d_krs, (const uint8_t*)d_bad,
+                  (const uint32_t*)d_rr, at.pub, at.pub_stride, n, np, pc.d_valid, d_p, rk_fold.a, terms.a);
+        const XYZZ<Fp>* rk_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, rk_fold, n, 1);
+        const Fr* c_sum = fold_all(s, st, "fr_fold", k_fr_fold, 256, terms, n, cols);
+        XYZZ<HFp> rk;
+        std::vector<HFr> c(cols);
+        ZK_HIP(hipMemcpyAsync(&rk, rk_sum, 128, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipMemcpyAsync(c.data(), c_sum, cols * 32, hipMemcpyDeviceToHost, st));
+        ZK_TRY(pc.sync_valid(n, accepted + c0));
+        if (pc.decided) continue;
+        // the three fixed-key terms (O(n_public) host work): -c_0 alpha, -sum_j c_j K_j, -sum_i r_i Krs_i
+        Affine<HFp> fixed[3];
+        {
+            uint32_t k[8];
+            to_canonical_u32(c[0], k);
+            fixed[0] = scalar_mul(v.alpha, k).to_affine().neg();
+            XYZZ<HFp> ic = XYZZ<HFp>::inf();
+            for (size_t j = 0; j < cols; j++) {
+                to_canonical_u32(c[j], k);
+                ic.add(scalar_mul(v.K[j], k));
+            }
+            fixed[1] = ic.to_affine().neg();
+            fixed[2] = rk.to_affine().neg();
+        }
+        const Affine<HFp2> qfix_b[3] = {v.beta, v.gamma, v.delta};
+        ZK_HIP(hipMemcpyAsync(d_p + n, fixed, 3 * 64, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemcpyAsync(d_fix, qfix_b, 3 * 128, hipMemcpyHostToDevice, st));
+        ZK_TRY(pc.combined(d_p, n + 3, d_bs, n, d_fix, n, accepted + c0));
+        if (pc.decided) continue;
+        // fallback: every valid proof on its own; the shared lane is e(alpha, beta)'s
+        const Affine<HFp2> qfix_f[3] = {v.gamma, v.delta, v.beta};
+        ZK_HIP(hipMemcpyAsync(d_fix, qfix_f, 3 * 128, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemcpyAsync(d_p + 3 * n, &v.alpha, 64, hipMemcpyHostToDevice, st));
+        ZK_LAUNCH(s, st, "vb_single", k_vb_single, dim3(blocks(n, 128)), dim3(128), 0, (const Affine<Fp>*)d_ar, (const Affine<Fp>*)d_krs,
+                  (const uint8_t*)pc.d_valid, at.pub, at.pub_stride, (const Affine<Fp>*)d_kpts, n, np, d_p);
+        ZK_TRY(pc.per_lane(d_p, n, 3, d_bs, n, d_fix, true, accepted + c0));
+    }
+    *n_accepted = pc.total;
+    return ZK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -638,130 +831,67 @@ int zk_bn254_pair(const zk_g1_affine* p, const zk_g2_affine* q, size_t n, zk_gt*
     return slot_sync(s, st);
 }
 
+// what both forms of the Groth16 entry decide before a device is looked for; pre = tag || SHA-256(vk) || 32 bytes for the data digest || 8 for the index
+static int groth16_batch_head(const void* vk, size_t vk_len, int vk_is_hex, size_t n_public, const char* tag, Groth16Vk* v, std::vector<uint8_t>* pre) {
+    ZK_TRY(groth16_vk_parse(vk, vk_len, vk_is_hex, v));
+    const size_t nk = v->K.size();
+    if (nk != n_public + 1) return set_err(ZK_ERR_LEN, "invalid witness size, got %zu, expected %zu (public - ONE_WIRE)", n_public, nk ? nk - 1 : 0);  // upstream's message
+    const size_t tl = strlen(tag);
+    pre->assign(tl + 32 + 32 + 8, 0);
+    memcpy(pre->data(), tag, tl);
+    sha(pre->data() + tl, v->bytes.data(), v->bytes.size());
+    return ZK_OK;
+}
+
 int zk_bn254_groth16_verify_batch(const uint8_t* proofs, size_t n_proofs, const void* vk, size_t vk_len, int vk_is_hex, const zk_fr* public_inputs,
                                   size_t n_public, uint8_t* accepted, size_t* n_accepted) {
     if (!vk || !n_accepted || (n_proofs && (!proofs || !accepted)) || (n_proofs && n_public && !public_inputs)) return set_err(ZK_ERR_ARG, "null pointer");
     *n_accepted = 0;
     Groth16Vk v;
-    ZK_TRY(groth16_vk_parse(vk, vk_len, vk_is_hex, &v));
-    const size_t nk = v.K.size();
-    if (nk != n_public + 1) return set_err(ZK_ERR_LEN, "invalid witness size, got %zu, expected %zu (public - ONE_WIRE)", n_public, nk ? nk - 1 : 0);  // upstream's message
+    std::vector<uint8_t> pre;
+    ZK_TRY(groth16_batch_head(vk, vk_len, vk_is_hex, n_public, "zkmi-groth16-batch", &v, &pre));
     if (n_proofs == 0) return ZK_OK;
     ZK_TRY(ensure_init());
-    const PairConsts K = pair_consts();
-    const size_t np = n_public, cols = np + 1;
-
     // r_i = low 128 bits of SHA-256(tag || SHA-256(vk) || SHA-256(proofs || public inputs) || u64 i), forced non-zero
-    uint8_t pre[18 + 32 + 32 + 8];
-    memcpy(pre, "zkmi-groth16-batch", 18);
-    sha(pre + 18, v.bytes.data(), v.bytes.size());
-    sha(pre + 50, proofs, n_proofs * 128, public_inputs, n_proofs * np * 32);
+    sha(pre.data() + pre.size() - 40, proofs, n_proofs * 128, public_inputs, n_proofs * n_public * 32);
+    return groth16_verify_rows(v, RowsIn{proofs, 128, (const Fr*)public_inputs, n_public, false}, n_proofs, n_public, pre, accepted, n_accepted);
+}
 
-    SlotGuard g;
-    ZK_TRY(acquire_slot(&g.s));
-    Slot* s = g.s;
-    hipStream_t st = s->stream;
-    const size_t ch = std::min(n_proofs, CHUNK);
-    PairCheck pc(s, K, ch);
-    uint8_t *d_raw, *d_bad;  // d_raw: Ar | Bs | Krs, each contiguous
-    Affine<Fp> *d_ar, *d_krs, *d_p, *d_kpts;
-    Affine<Fp2> *d_bs, *d_fix;
-    uint32_t* d_rr;
-    Fr* d_pub;
-    FoldPair<XYZZ<Fp>> rk_fold;
-    FoldPair<Fr> terms;
-    int* d_status;
-    ZK_TRY(plan_workspace(s, "groth16_verify_batch", [&](ArenaPlan& p) {
-        p.take(ch * 128, d_raw);
-        p.take(ch, d_ar, d_krs, d_bs);
-        p.take(ch * 3, d_bad);
-        p.take(ch * 4, d_rr);
-        p.take(std::max(ch * np, (size_t)1), d_pub);
-        rk_fold.layout(p, ch);
-        terms.layout(p, ch, cols);
-        p.take(3 * ch + 3, d_p);
-        pc.layout(p, 3 * ch + 3);
-        p.take(nk, d_kpts);
-        p.take(3, d_fix);
-        p.take(16, d_status);
-        p.later(ch * G2_DECOMPRESS_SCRATCH);  // g2_decompress_dev's, per chunk
-    }));
-    ZK_HIP(hipMemcpyAsync(d_kpts, v.K.data(), nk * 64, hipMemcpyHostToDevice, st));
-    const size_t arena_mark = s->arena_off;  // g2_decompress_dev takes its scratch from the arena per call: give it back per chunk
+int zk_bn254_groth16_verify_batch_dev(const void* d_proofs, size_t proof_stride, size_t n_proofs, const void* vk, size_t vk_len, int vk_is_hex,
+                                      const void* d_public_inputs, size_t pub_stride, size_t n_public, uint8_t* accepted, size_t* n_accepted) {
+    if (!vk || !n_accepted || (n_proofs && (!d_proofs || !accepted)) || (n_proofs && n_public && !d_public_inputs)) return set_err(ZK_ERR_ARG, "null pointer");
+    *n_accepted = 0;
+    Groth16Vk v;
+    std::vector<uint8_t> pre;
+    ZK_TRY(groth16_batch_head(vk, vk_len, vk_is_hex, n_public, "zkmi-groth16-batch-rows", &v, &pre));
+    ZK_TRY(rows_in_args(d_proofs, proof_stride, 128, n_proofs, d_public_inputs, pub_stride, n_public));
+    if (n_proofs == 0) return ZK_OK;
+    ZK_TRY(ensure_init());
+    const RowsIn in{(const uint8_t*)d_proofs, proof_stride, (const Fr*)d_public_inputs, pub_stride, true};
+    // r_i = low 128 bits of SHA-256(tag || SHA-256(vk) || SHA-256(d_0 || .. || d_{n-1}) || u64 i), d_v the rows' digests made on the device
+    ZK_TRY(rows_digest_of_call(in, 128, n_proofs, n_public, pre.data() + pre.size() - 40));
+    return groth16_verify_rows(v, in, n_proofs, n_public, pre, accepted, n_accepted);
+}
 
-    std::vector<uint8_t> raw(ch * 128);
-    std::vector<uint32_t> rr(ch * 4);
-    for (size_t c0 = 0; c0 < n_proofs; c0 += ch) {
-        const size_t n = std::min(ch, n_proofs - c0);
-        s->arena_off = arena_mark;
-        for (size_t i = 0; i < n; i++) {
-            const uint8_t* pr = proofs + (c0 + i) * 128;
-            memcpy(&raw[i * 32], pr, 32);
-            memcpy(&raw[n * 32 + i * 64], pr + 32, 64);
-            memcpy(&raw[n * 96 + i * 32], pr + 96, 32);
-        }
-        batch_coeffs(pre, sizeof pre, 82, c0, n, rr.data());
-        ZK_HIP(hipMemcpyAsync(d_raw, raw.data(), n * 128, hipMemcpyHostToDevice, st));
-        ZK_HIP(hipMemcpyAsync(d_rr, rr.data(), n * 16, hipMemcpyHostToDevice, st));
-        if (np) ZK_HIP(hipMemcpyAsync(d_pub, public_inputs + c0 * np, n * np * 32, hipMemcpyHostToDevice, st));
-        ZK_HIP(hipMemsetAsync(d_bad, 0, n * 3, st));
-        ZK_HIP(hipMemsetAsync(d_status, 0, 4, st));
-        ZK_TRY(g1_decompress_dev(s, st, d_raw, n, d_ar, d_status, d_bad));
-        ZK_TRY(g2_decompress_dev(s, st, d_raw + n * 32, n, d_bs, d_status, d_bad + n));
-        ZK_TRY(g1_decompress_dev(s, st, d_raw + n * 96, n, d_krs, d_status, d_bad + 2 * n));
-        ZK_LAUNCH(s, st, "vb_prep", k_vb_prep, dim3(blocks(n, 128)), dim3(128), 0, (const Affine<Fp>*)d_ar, (const Affine<Fp>*)d_krs, (const uint8_t*)d_bad,
-                  (const uint32_t*)d_rr, (const Fr*)d_pub, n, np, pc.d_valid, d_p, rk_fold.a, terms.a);
-        const XYZZ<Fp>* rk_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, rk_fold, n, 1);
-        const Fr* c_sum = fold_all(s, st, "fr_fold", k_fr_fold, 256, terms, n, cols);
-        XYZZ<HFp> rk;
-        std::vector<HFr> c(cols);
-        ZK_HIP(hipMemcpyAsync(&rk, rk_sum, 128, hipMemcpyDeviceToHost, st));
-        ZK_HIP(hipMemcpyAsync(c.data(), c_sum, cols * 32, hipMemcpyDeviceToHost, st));
-        ZK_TRY(pc.sync_valid(n, accepted + c0));
-        if (pc.decided) continue;
-        // the three fixed-key terms (O(n_public) host work): -c_0 alpha, -sum_j c_j K_j, -sum_i r_i Krs_i
-        Affine<HFp> fixed[3];
-        {
-            uint32_t k[8];
-            to_canonical_u32(c[0], k);
-            fixed[0] = scalar_mul(v.alpha, k).to_affine().neg();
-            XYZZ<HFp> ic = XYZZ<HFp>::inf();
-            for (size_t j = 0; j < cols; j++) {
-                to_canonical_u32(c[j], k);
-                ic.add(scalar_mul(v.K[j], k));
-            }
-            fixed[1] = ic.to_affine().neg();
-            fixed[2] = rk.to_affine().neg();
-        }
-        const Affine<HFp2> qfix_b[3] = {v.beta, v.gamma, v.delta};
-        ZK_HIP(hipMemcpyAsync(d_p + n, fixed, 3 * 64, hipMemcpyHostToDevice, st));
-        ZK_HIP(hipMemcpyAsync(d_fix, qfix_b, 3 * 128, hipMemcpyHostToDevice, st));
-        ZK_TRY(pc.combined(d_p, n + 3, d_bs, n, d_fix, n, accepted + c0));
-        if (pc.decided) continue;
-        // fallback: every valid proof on its own; the shared lane is e(alpha, beta)'s
-        const Affine<HFp2> qfix_f[3] = {v.gamma, v.delta, v.beta};
-        ZK_HIP(hipMemcpyAsync(d_fix, qfix_f, 3 * 128, hipMemcpyHostToDevice, st));
-        ZK_HIP(hipMemcpyAsync(d_p + 3 * n, &v.alpha, 64, hipMemcpyHostToDevice, st));
-        ZK_LAUNCH(s, st, "vb_single", k_vb_single, dim3(blocks(n, 128)), dim3(128), 0, (const Affine<Fp>*)d_ar, (const Affine<Fp>*)d_krs,
-                  (const uint8_t*)pc.d_valid, (const Fr*)d_pub, (const Affine<Fp>*)d_kpts, n, np, d_p);
-        ZK_TRY(pc.per_lane(d_p, n, 3, d_bs, n, d_fix, true, accepted + c0));
-    }
-    *n_accepted = pc.total;
+// what both forms of the PLONK entry decide before a device is looked for; pre = tag || SHA-256(vk) || SHA-256(srs_g2) || 32 bytes for the data digest
+static int plonk_batch_head(const void* vk, size_t vk_len, int vk_is_hex, const zk_g2_affine srs_g2[2], size_t n_public, const char* tag, PlonkVk* v,
+                            std::vector<uint8_t>* pre) {
+    ZK_TRY(plonk_vk_parse(vk, vk_len, vk_is_hex, v));
+    if (v->npub != n_public) return set_err(ZK_ERR_LEN, "invalid witness size, got %zu, expected %llu", n_public, (unsigned long long)v->npub);  // upstream's message
+    const size_t tl = strlen(tag);
+    pre->assign(tl + 3 * 32, 0);
+    memcpy(pre->data(), tag, tl);
+    sha(pre->data() + tl, v->bytes.data(), v->bytes.size());
+    sha(pre->data() + tl + 32, srs_g2, 2 * sizeof(zk_g2_affine));
     return ZK_OK;
 }
 
-int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const void* vk, size_t vk_len, int vk_is_hex, const zk_g2_affine srs_g2[2],
-                                const zk_fr* public_inputs, size_t n_public, uint8_t* accepted, size_t* n_accepted) {
-    if (!vk || !srs_g2 || !n_accepted || (n_proofs && (!proofs || !accepted)) || (n_proofs && n_public && !public_inputs))
-        return set_err(ZK_ERR_ARG, "null pointer");
-    *n_accepted = 0;
-    PlonkVk v;
-    ZK_TRY(plonk_vk_parse(vk, vk_len, vk_is_hex, &v));
-    if (v.npub != n_public) return set_err(ZK_ERR_LEN, "invalid witness size, got %zu, expected %llu", n_public, (unsigned long long)v.npub);  // upstream's message
-    if (n_proofs == 0) return ZK_OK;
-    ZK_TRY(ensure_init());
+// plonk.Verify for the rows `in` against the parsed key.  pre: the coefficients' prefix, complete (64 to 127 bytes: one whole SHA-256 block, hashed here into the
+// lanes' midstate, and a rest): rho_i, rho'_i = batch_coeff(SHA-256(pre || u64 i || 0 / 1)) -- the entry's to
+// derive (zkmi.h states both derivations), so that one core serves the host and the device form
+static int plonk_verify_rows(const PlonkVk& v, const zk_g2_affine srs_g2[2], const RowsIn& in, size_t n_proofs, size_t np, const std::vector<uint8_t>& pre,
+                             uint8_t* accepted, size_t* n_accepted) {
     const PairConsts PK = pair_consts();
-    const size_t np = n_public;
     PvKey K;
     K.n = v.n;
     K.log_n = 0;
@@ -783,18 +913,14 @@ int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const vo
         tg.update(b, 64);
     }
     const uint32_t tail_len = (uint32_t)tg.fill;
-    // rho_i, rho'_i = the low 128 bits of SHA-256(tag || SHA-256(vk) || SHA-256(srs_g2) || SHA-256(proofs || public inputs) || u64 i || 0 / 1)
-    uint8_t pre[16 + 3 * 32];
-    memcpy(pre, "zkmi-plonk-batch", 16);
-    sha(pre + 16, v.bytes.data(), v.bytes.size());
-    sha(pre + 48, srs_g2, 2 * sizeof(zk_g2_affine));
-    sha(pre + 80, proofs, n_proofs * 548, public_inputs, n_proofs * np * 32);
+    if (pre.size() < 64 || pre.size() >= 128) return set_err(ZK_ERR_ARG, "coefficient prefix of %zu bytes", pre.size());
     Sha256 tr;
-    tr.update(pre, sizeof pre);  // one whole block, 48 bytes left in buf
-    std::vector<uint8_t> hbytes(tail_len + 13 + 48);
+    tr.update(pre.data(), pre.size());  // one whole block, the rest (48 bytes in the host form, 53 in the device form) left in buf
+    const uint32_t rtail_len = (uint32_t)(pre.size() - 64);
+    std::vector<uint8_t> hbytes(tail_len + 13 + rtail_len);
     memcpy(hbytes.data(), tg.buf, tail_len);
     memcpy(hbytes.data() + tail_len, "betaalphazeta", 13);
-    memcpy(hbytes.data() + tail_len + 13, tr.buf, 48);
+    memcpy(hbytes.data() + tail_len + 13, tr.buf, rtail_len);
     uint32_t mids[16];
     memcpy(mids, tg.h, 32);
     memcpy(mids + 8, tr.h, 32);
@@ -805,9 +931,9 @@ int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const vo
     hipStream_t st = s->stream;
     const size_t ch = std::min(n_proofs, CHUNK);
     PairCheck pc(s, PK, ch);
-    uint32_t *d_proofs, *d_praw, *d_mids;
+    uint32_t *d_praw, *d_mids;
     Affine<Fp> *d_pts, *d_dig, *d_p, *d_kpts;
-    uint8_t *d_bad, *d_hdr, *d_hbytes;
+    uint8_t *d_stage, *d_bad, *d_hdr, *d_hbytes;
     Fr *d_sc, *d_pub, *d_fix;
     XYZZ<Fp> *d_t, *d_A, *d_B;
     FoldPair<XYZZ<Fp>> fa, fb;
@@ -816,11 +942,11 @@ int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const vo
     PvTerm* d_terms;
     int* d_status;
     ZK_TRY(plan_workspace(s, "plonk_verify_batch", [&](ArenaPlan& p) {
-        p.take(ch * (548 / 4), d_proofs);
+        p.take(in.on_device ? 1 : ch * 548, d_stage);
         p.take(ch * PV_NPTS * 8, d_praw);
         p.take(ch * PV_NPTS, d_pts, d_bad);
         p.take(ch * PV_NCOL, d_sc);
-        p.take(std::max(ch * np, (size_t)1), d_pub);
+        p.take(in.on_device ? 1 : std::max(ch * np, (size_t)1), d_pub);
         p.take(ch * 10, d_t);
         p.take(ch * 3, d_fix);
         p.take(ch * 2, d_dig, d_p);
@@ -867,21 +993,21 @@ int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const vo
             ZK_HIP(hipMemcpyAsync(d_terms, terms.data(), terms.size() * sizeof(PvTerm), hipMemcpyHostToDevice, st));
             tn = n;
         }
-        ZK_HIP(hipMemcpyAsync(d_proofs, proofs + c0 * 548, n * 548, hipMemcpyHostToDevice, st));
-        if (np) ZK_HIP(hipMemcpyAsync(d_pub, public_inputs + c0 * np, n * np * 32, hipMemcpyHostToDevice, st));
+        RowsIn at;
+        ZK_TRY(rows_of_chunk(in, st, c0, n, 548, np, d_stage, d_pub, &at));
         ZK_HIP(hipMemsetAsync(d_bad, 0, n * PV_NPTS, st));
         ZK_HIP(hipMemsetAsync(d_status, 0, 4, st));
         const dim3 g64(blocks(n, 64)), g256(blocks(n, 256));
-        ZK_LAUNCH(s, st, "pv_gather", k_pv_gather, g256, dim3(256), 0, (const uint32_t*)d_proofs, n, d_praw, d_sc, d_hdr);
+        ZK_LAUNCH(s, st, "pv_gather", k_pv_gather, g256, dim3(256), 0, at.proofs, at.proof_stride, n, d_praw, d_sc, d_hdr);
         ZK_TRY(g1_decompress_dev(s, st, d_praw, PV_NPTS * n, d_pts, d_status, d_bad));
         ZK_LAUNCH(s, st, "pv_transcript", k_pv_transcript, g64, dim3(64), 0, (const Affine<Fp>*)d_pts, (const uint8_t*)d_bad, (const uint8_t*)d_hdr,
-                  (const Fr*)d_pub, n, np, (const uint32_t*)d_mids, (uint64_t)(tg.len - tail_len), (const uint8_t*)d_hbytes, tail_len, d_valid, d_sc);
-        ZK_LAUNCH(s, st, "pv_scalars", k_pv_scalars, g64, dim3(64), 0, (const Fr*)d_pub, n, np, K, d_valid, d_sc);
+                  at.pub, at.pub_stride, n, np, (const uint32_t*)d_mids, (uint64_t)(tg.len - tail_len), (const uint8_t*)d_hbytes, tail_len, d_valid, d_sc);
+        ZK_LAUNCH(s, st, "pv_scalars", k_pv_scalars, g64, dim3(64), 0, at.pub, at.pub_stride, n, np, K, d_valid, d_sc);
         ZK_LAUNCH(s, st, "pv_smul", k_pv_smul, dim3(blocks(n, 64), 8), dim3(64), 0, (const PvTerm*)d_terms, n, (const uint8_t*)d_valid, d_t);
         ZK_LAUNCH(s, st, "pv_digests", k_pv_digests, g64, dim3(64), 0, (const Affine<Fp>*)d_pts, (const XYZZ<Fp>*)d_t, (const Affine<Fp>*)d_kpts, n,
                   (const uint8_t*)d_valid, d_dig);
         ZK_LAUNCH(s, st, "pv_kzg", k_pv_kzg, g64, dim3(64), 0, (const Affine<Fp>*)d_pts, (const Affine<Fp>*)d_dig, (const Affine<Fp>*)d_kpts, n, c0, K,
-                  (const uint32_t*)(d_mids + 8), (const uint8_t*)(d_hbytes + tail_len + 13), (const uint8_t*)d_valid, d_sc, d_fix, fold.a);
+                  (const uint32_t*)(d_mids + 8), (const uint8_t*)(d_hbytes + tail_len + 13), rtail_len, (const uint8_t*)d_valid, d_sc, d_fix, fold.a);
         ZK_LAUNCH(s, st, "pv_smul", k_pv_smul, dim3(blocks(n, 64), 10), dim3(64), 0, (const PvTerm*)(d_terms + 8), n, (const uint8_t*)d_valid, d_t);
         ZK_LAUNCH(s, st, "pv_combine", k_pv_combine, g256, dim3(256), 0, (const XYZZ<Fp>*)d_t, n, d_A, d_B, fa.a, fb.a);
         const XYZZ<Fp>* a_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, fa, n, 1);
@@ -916,6 +1042,52 @@ int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const vo
         ZK_TRY(pc.per_lane(d_p, n, 2, nullptr, 0, d_g2, false, accepted + c0));
     }
     *n_accepted = pc.total;
+    return ZK_OK;
+}
+
+int zk_bn254_plonk_verify_batch(const uint8_t* proofs, size_t n_proofs, const void* vk, size_t vk_len, int vk_is_hex, const zk_g2_affine srs_g2[2],
+                                const zk_fr* public_inputs, size_t n_public, uint8_t* accepted, size_t* n_accepted) {
+    if (!vk || !srs_g2 || !n_accepted || (n_proofs && (!proofs || !accepted)) || (n_proofs && n_public && !public_inputs))
+        return set_err(ZK_ERR_ARG, "null pointer");
+    *n_accepted = 0;
+    PlonkVk v;
+    std::vector<uint8_t> pre;
+    ZK_TRY(plonk_batch_head(vk, vk_len, vk_is_hex, srs_g2, n_public, "zkmi-plonk-batch", &v, &pre));
+    if (n_proofs == 0) return ZK_OK;
+    ZK_TRY(ensure_init());
+    // rho_i, rho'_i = the low 128 bits of SHA-256(tag || SHA-256(vk) || SHA-256(srs_g2) || SHA-256(proofs || public inputs) || u64 i || 0 / 1)
+    sha(pre.data() + pre.size() - 32, proofs, n_proofs * 548, public_inputs, n_proofs * n_public * 32);
+    return plonk_verify_rows(v, srs_g2, RowsIn{proofs, 548, (const Fr*)public_inputs, n_public, false}, n_proofs, n_public, pre, accepted, n_accepted);
+}
+
+int zk_bn254_plonk_verify_batch_dev(const void* d_proofs, size_t proof_stride, size_t n_proofs, const void* vk, size_t vk_len, int vk_is_hex,
+                                    const zk_g2_affine srs_g2[2], const void* d_public_inputs, size_t pub_stride, size_t n_public, uint8_t* accepted,
+                                    size_t* n_accepted) {
+    if (!vk || !srs_g2 || !n_accepted || (n_proofs && (!d_proofs || !accepted)) || (n_proofs && n_public && !d_public_inputs))
+        return set_err(ZK_ERR_ARG, "null pointer");
+    *n_accepted = 0;
+    PlonkVk v;
+    std::vector<uint8_t> pre;
+    ZK_TRY(plonk_batch_head(vk, vk_len, vk_is_hex, srs_g2, n_public, "zkmi-plonk-batch-rows", &v, &pre));
+    ZK_TRY(rows_in_args(d_proofs, proof_stride, 548, n_proofs, d_public_inputs, pub_stride, n_public));
+    if (n_proofs == 0) return ZK_OK;
+    ZK_TRY(ensure_init());
+    const RowsIn in{(const uint8_t*)d_proofs, proof_stride, (const Fr*)d_public_inputs, pub_stride, true};
+    // the same with SHA-256(d_0 || .. || d_{n-1}) for the data digest, d_v the rows' digests made on the device
+    ZK_TRY(rows_digest_of_call(in, 548, n_proofs, n_public, pre.data() + pre.size() - 32));
+    return plonk_verify_rows(v, srs_g2, in, n_proofs, n_public, pre, accepted, n_accepted);
+}
+
+int zk_bn254_rows_sha256_dev(const void* d_a, size_t a_len, size_t a_stride, const void* d_b, size_t b_len, size_t b_stride, size_t rows, void* d_out, void* stream) {
+    if ((a_len && !d_a) || (b_len && !d_b) || (rows && !d_out)) return set_err(ZK_ERR_ARG, "null pointer");
+    if (rows > 1 && (a_stride < a_len || b_stride < b_len))
+        return set_err(ZK_ERR_ARG, "strides %zu / %zu are below the %zu / %zu bytes of a row", a_stride, b_stride, a_len, b_len);
+    if (rows == 0) return ZK_OK;
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    rows_digest_launch(g.s, st, d_a, a_len, a_stride, d_b, b_len, b_stride, rows, d_out);
+    if (!stream || profiling_on()) ZK_TRY(slot_sync(g.s, st));
     return ZK_OK;
 }
 

@@ -80,6 +80,91 @@ __global__ __launch_bounds__(256) void k_felts_decode_hex_rows(const char* __res
     out[row * out_stride + i] = y;
 }
 
+// ---- text rows for the batch verifiers (include/zkmi.h: bytes_decode_hex_rows_dev, felts_public_hex_rows_dev): one workgroup per row (blockIdx.y), which
+// walks the row in strides of its 256 lanes, agrees on the row's verdict (__syncthreads_or) and only then writes -- a rejected row is zeros.  Nothing is assumed
+// of the pitch or of the text's alignment: characters are read as bytes, but for the whole-text check below, which reads the aligned words in between.
+constexpr unsigned ROW_BLOCK = 256;
+static_assert(ZK_ROW_BAD_PROOF_HEX == 5, "the row statuses are part of the interface");
+
+__device__ __forceinline__ int hex_nib(uint32_t c) {  // 0..15, or -1 for a character hex.DecodeString refuses
+    const uint32_t d = c - '0', l = (c | 0x20u) - 'a';
+    return d <= 9 ? (int)d : l <= 5 ? (int)(10 + l) : -1;
+}
+
+__global__ __launch_bounds__(ROW_BLOCK) void k_bytes_decode_hex_rows(const uint8_t* __restrict__ text, size_t pitch, size_t n_bytes, uint8_t* __restrict__ out,
+                                                                    size_t out_stride, int* __restrict__ status) {
+    const size_t row = blockIdx.y;
+    const uint8_t* t = text + row * pitch;
+    uint8_t* o = out + row * out_stride;
+    int bad = 0;
+    for (size_t i = threadIdx.x; i < n_bytes; i += ROW_BLOCK) bad |= (hex_nib(t[2 * i]) | hex_nib(t[2 * i + 1])) < 0;
+    bad = __syncthreads_or(bad);
+    for (size_t i = threadIdx.x; i < n_bytes; i += ROW_BLOCK) o[i] = bad ? 0 : (uint8_t)((hex_nib(t[2 * i]) << 4) | hex_nib(t[2 * i + 1]));
+    if (threadIdx.x == 0) status[row] = bad ? (int)ZK_ROW_BAD_HEX : (int)ZK_ROW_OK;
+}
+
+// 64 characters, big-endian -> limbs (the characters were checked before)
+__device__ __forceinline__ void felt_from_hex_chars(const uint8_t* s, uint32_t l[8]) {
+#pragma unroll 1
+    for (int j = 0; j < 8; j++) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) v = (v << 4) | ((uint32_t)hex_nib(s[8 * j + k]) & 15u);
+        l[7 - j] = v;
+    }
+}
+
+// The verifier's view of a values text (goffi.cpp PlonkVerifyWithVK; zk_groth16_public_inputs): the count header against n_values, every character after it
+// for being hex, and of the felts only those at where[0 .. n_public) -- canonical or the row is refused -- into Montgomery form.
+__global__ __launch_bounds__(ROW_BLOCK) void k_felts_public_hex_rows(const uint8_t* __restrict__ text, size_t pitch, size_t n_values, const uint32_t* __restrict__ where,
+                                                                    size_t n_public, Fr* __restrict__ pub, size_t pub_stride, int* __restrict__ status) {
+    const size_t row = blockIdx.y;
+    const uint8_t* t = text + row * pitch;
+    const uint8_t* f = t + 8;
+    const size_t len = 64 * n_values;
+    Fr* o = pub + row * pub_stride;
+    int st = ZK_ROW_OK;
+    {   // the header (every lane reads the same eight bytes)
+        uint64_t count = 0;
+        int bad = 0;
+        for (int k = 0; k < 8; k++) {
+            const int d = hex_nib(t[k]);
+            bad |= d < 0;
+            count = (count << 4) | (uint32_t)(d & 15);
+        }
+        if (bad || count != n_values) st = ZK_ROW_BAD_COUNT;
+    }
+    if (st == ZK_ROW_OK) {  // (uniform over the workgroup: the barriers below are reached by all of its lanes or by none)
+        // every character: the bytes up to the first 4-byte boundary and behind the last one by themselves, the words between them four characters at a time
+        const size_t to_word = (4 - ((uintptr_t)f & 3)) & 3, head = to_word < len ? to_word : len, words = (len - head) / 4, tail = head + 4 * words;
+        int bad = 0;
+        for (size_t i = threadIdx.x; i < head + (len - tail); i += ROW_BLOCK) bad |= hex_nib(f[i < head ? i : tail + (i - head)]) < 0;
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(f + head);
+        uint32_t badw = 0;
+        for (size_t i = threadIdx.x; i < words; i += ROW_BLOCK) (void)hex4(w[i], &badw);
+        if (__syncthreads_or(bad | (badw != 0))) st = ZK_ROW_BAD_HEX;
+    }
+    if (st == ZK_ROW_OK) {
+        int bad = 0;
+        for (size_t k = threadIdx.x; k < n_public; k += ROW_BLOCK) {
+            const size_t at = where[k];
+            uint32_t l[8];
+            if (at < n_values) felt_from_hex_chars(f + 64 * at, l);
+            bad |= at >= n_values || geq_mod_r(l);  // (a position outside the text is never read: the row is refused)
+        }
+        if (__syncthreads_or(bad)) st = ZK_ROW_NOT_CANONICAL;
+    }
+    for (size_t k = threadIdx.x; k < n_public; k += ROW_BLOCK) {
+        Fr x = Fr::zero();
+        if (st == ZK_ROW_OK) {
+            felt_from_hex_chars(f + 64 * (size_t)where[k], x.l);
+            x = x.to_mont();
+        }
+        o[k] = x;
+    }
+    if (threadIdx.x == 0) status[row] = st;
+}
+
 // raw bytes (already hex-decoded): 32 big-endian bytes per felt
 __global__ __launch_bounds__(256) void k_felts_decode_bytes(const uint4* __restrict__ raw, size_t n, int to_mont, Fr* __restrict__ out, int* __restrict__ status) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -187,8 +272,57 @@ int felts_decode_hex_rows_on_slot(Slot* s, hipStream_t st, const void* d_text, s
               to_mont, (Fr*)d_out, out_stride, d_status);
     return ZK_OK;
 }
+// the text rows of the verifiers: what the entries ask of their arguments (decided before a device is looked for), and their launches on a slot the caller
+// holds -- enqueued only, the status words written by the kernels themselves
+static int text_rows_args(const void* d_text, size_t pitch, size_t rows, size_t row_chars, const void* d_out, size_t out_stride, size_t out_row, const int* d_status) {
+    if (!d_text || (out_row && !d_out) || !d_status) return set_err(ZK_ERR_ARG, "null pointer");
+    if (rows > 65535) return set_err(ZK_ERR_ARG, "%zu rows in one call, at most 65535 (the row is a grid dimension)", rows);
+    if (pitch < row_chars) return set_err(ZK_ERR_ARG, "pitch = %zu is below the %zu characters of a row", pitch, row_chars);
+    if (out_stride < out_row) return set_err(ZK_ERR_ARG, "the output stride %zu is below the %zu of a row", out_stride, out_row);
+    return ZK_OK;
+}
+int bytes_decode_hex_rows_on_slot(Slot* s, hipStream_t st, const void* d_text, size_t pitch, size_t rows, size_t n_bytes, void* d_out, size_t out_stride, int* d_status) {
+    if (rows == 0) return ZK_OK;
+    ZK_TRY(text_rows_args(d_text, pitch, rows, 2 * n_bytes, d_out, out_stride, n_bytes, d_status));
+    ZK_LAUNCH(s, st, "bytes_decode_hex_rows", k_bytes_decode_hex_rows, dim3(1, (unsigned)rows), dim3(ROW_BLOCK), 0, (const uint8_t*)d_text, pitch, n_bytes, (uint8_t*)d_out,
+              out_stride, d_status);
+    return ZK_OK;
+}
+int felts_public_hex_rows_on_slot(Slot* s, hipStream_t st, const void* d_text, size_t pitch, size_t rows, size_t n_values, const uint32_t* d_where, size_t n_public,
+                                  void* d_pub, size_t pub_stride, int* d_status) {
+    if (rows == 0) return ZK_OK;
+    ZK_TRY(text_rows_args(d_text, pitch, rows, 8 + 64 * n_values, d_pub, pub_stride, n_public, d_status));
+    if (n_public && !d_where) return set_err(ZK_ERR_ARG, "null pointer");
+    ZK_LAUNCH(s, st, "felts_public_hex_rows", k_felts_public_hex_rows, dim3(1, (unsigned)rows), dim3(ROW_BLOCK), 0, (const uint8_t*)d_text, pitch, n_values, d_where, n_public,
+              (Fr*)d_pub, pub_stride, d_status);
+    return ZK_OK;
+}
 }  // namespace zkmi
 extern "C" {
+
+int zk_bn254_bytes_decode_hex_rows_dev(const void* d_text, size_t pitch, size_t rows, size_t n_bytes, void* d_out, size_t out_stride, int* d_status, void* stream) {
+    if (rows == 0) return ZK_OK;
+    ZK_TRY(text_rows_args(d_text, pitch, rows, 2 * n_bytes, d_out, out_stride, n_bytes, d_status));
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    ZK_TRY(bytes_decode_hex_rows_on_slot(g.s, st, d_text, pitch, rows, n_bytes, d_out, out_stride, d_status));
+    if (!stream || profiling_on()) ZK_TRY(slot_sync(g.s, st));
+    return ZK_OK;
+}
+
+int zk_bn254_felts_public_hex_rows_dev(const void* d_text, size_t pitch, size_t rows, size_t n_values, const uint32_t* d_where, size_t n_public, void* d_pub,
+                                       size_t pub_stride, int* d_status, void* stream) {
+    if (rows == 0) return ZK_OK;
+    ZK_TRY(text_rows_args(d_text, pitch, rows, 8 + 64 * n_values, d_pub, pub_stride, n_public, d_status));
+    if (n_public && !d_where) return set_err(ZK_ERR_ARG, "null pointer");
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    hipStream_t st = stream ? (hipStream_t)stream : g.s->stream;
+    ZK_TRY(felts_public_hex_rows_on_slot(g.s, st, d_text, pitch, rows, n_values, d_where, n_public, d_pub, pub_stride, d_status));
+    if (!stream || profiling_on()) ZK_TRY(slot_sync(g.s, st));
+    return ZK_OK;
+}
 
 int zk_bn254_felts_decode_hex_rows_dev(const void* d_text, size_t pitch, size_t rows, size_t n, void* d_out, size_t out_stride, int to_mont, int* d_status, void* stream) {
     if (rows == 0 || n == 0) return ZK_OK;

@@ -248,3 +248,41 @@ def export_cache_info() -> dict:
 
 def export_cache_clear() -> None:
     check(lib().zk_export_cache_clear())
+
+
+def _verify_rows(proof_texts, encoded_values, width: int):
+    proofs = [_b(p) for p in proof_texts]
+    if any(len(p) != width for p in proofs):
+        raise ValueError("a proof text is %d hex characters (Proof.WriteTo)" % width)
+    text, vlen, rows = _rows_text(encoded_values)
+    if rows != len(proofs):
+        raise ValueError("as many proof texts as values texts")
+    return b"".join(proofs), text, vlen, rows
+
+
+def plonk_verify_batch_with_vk(acir_json: str, proof_texts: list, encoded_values: list, encoded_vk: str, srs_g2, chunk_rows: int = 0, layout: int = LAYOUT_REFERENCE):
+    """PlonkVerifyWithVK for many (proof text, values text) pairs of one circuit against one verifying key, in one call -> (accepted (rows,) bool, [status per row:
+    _lib.ROW_*]).  accepted[v] is what the single sequence -- hex-decode the proof, take the public values, verify.plonk_verify -- gives for row v; a row whose
+    status is not ROW_OK was not verified and is not accepted.  srs_g2: the SRS's two G2 points, as verify.plonk_verify_batch takes them (kzg.read_srs_g2)."""
+    a, k = _b(acir_json), _b(encoded_vk)
+    ptext, text, vlen, rows = _verify_rows(proof_texts, encoded_values, 2 * _lib.PLONK_PROOF_BYTES)
+    g2 = np.ascontiguousarray(srs_g2, dtype=np.uint64).reshape(2, 16)
+    acc = np.zeros(max(rows, 1), np.uint8)
+    status = np.zeros(max(rows, 1), np.int32)
+    n_acc = C.c_size_t(0)
+    _raise_arg(lib().zk_plonk_verify_batch_with_vk(a, len(a), layout, ptext, 2 * _lib.PLONK_PROOF_BYTES, text, vlen, vlen, rows, k, len(k), vp(g2), chunk_rows, vp(acc), vp(status),
+                                                   C.addressof(n_acc)))
+    return acc[:rows].astype(bool), [int(x) for x in status[:rows]]
+
+
+def groth16_verify_batch_with_vk(raw_json: str, proof_texts: list, encoded_values: list, encoded_vk: str, chunk_rows: int = 0):
+    """VerifyWithVK for many (proof text, values text) pairs of one RawR1CS circuit against one verifying key, in one call -> (accepted (rows,) bool, [status per
+    row]).  The text's own values string only identifies the circuit; row v's public inputs are read from encoded_values[v] (the public wires after ONE, in wire
+    order: what groth16_public_inputs returns for the text with that row's values)."""
+    a, k = _b(raw_json), _b(encoded_vk)
+    ptext, text, vlen, rows = _verify_rows(proof_texts, encoded_values, 256)
+    acc = np.zeros(max(rows, 1), np.uint8)
+    status = np.zeros(max(rows, 1), np.int32)
+    n_acc = C.c_size_t(0)
+    _raise_arg(lib().zk_groth16_verify_batch_with_vk(a, len(a), ptext, 256, text, vlen, vlen, rows, k, len(k), chunk_rows, vp(acc), vp(status), C.addressof(n_acc)))
+    return acc[:rows].astype(bool), [int(x) for x in status[:rows]]

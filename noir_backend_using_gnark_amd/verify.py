@@ -122,3 +122,42 @@ def plonk_verify_batch(proofs, vk, srs_g2, public_inputs) -> np.ndarray:
         raise ValueError((lib().zk_last_error() or b"").decode())
     check(rc)
     return acc[:n].astype(bool)
+
+
+def _dev_rows(proofs, public_inputs, n_public: int | None):
+    """(device pointer or DeviceBuffer, rows) pair of arguments of the device forms -> raw pointers (0 for no public inputs)"""
+    p = proofs.ptr if isinstance(proofs, _lib.DeviceBuffer) else int(proofs)
+    if public_inputs is None or n_public == 0:
+        return p, 0
+    return p, public_inputs.ptr if isinstance(public_inputs, _lib.DeviceBuffer) else int(public_inputs)
+
+
+def _verdicts(rc: int, acc: np.ndarray, n: int) -> np.ndarray:
+    if rc in (_lib.ZK_ERR_LEN, _lib.ZK_ERR_ARG):
+        raise ValueError((lib().zk_last_error() or b"").decode())
+    check(rc)
+    return acc[:n].astype(bool)
+
+
+def groth16_verify_batch_dev(d_proofs, proof_stride: int, n_proofs: int, vk, d_public_inputs, pub_stride: int, n_public: int) -> np.ndarray:
+    """groth16_verify_batch for rows that already lie in HBM (zk_bn254_groth16_verify_batch_dev): proof v is the 128 bytes at d_proofs + v * proof_stride,
+    its public inputs the n_public Montgomery elements at element v * pub_stride of d_public_inputs (DeviceBuffer or raw device pointers).  The verdicts are
+    groth16_verify_batch's for the same bytes; the coefficients come from one SHA-256 per row computed on the device."""
+    k, is_hex = _blob(vk)
+    p, q = _dev_rows(d_proofs, d_public_inputs, n_public)
+    acc = np.zeros(max(n_proofs, 1), np.uint8)
+    n_acc = C.c_size_t(0)
+    rc = lib().zk_bn254_groth16_verify_batch_dev(p, proof_stride, n_proofs, k, len(k), is_hex, q, pub_stride, n_public, vp(acc), C.addressof(n_acc))
+    return _verdicts(rc, acc, n_proofs)
+
+
+def plonk_verify_batch_dev(d_proofs, proof_stride: int, n_proofs: int, vk, srs_g2, d_public_inputs, pub_stride: int, n_public: int) -> np.ndarray:
+    """plonk_verify_batch for rows that already lie in HBM (zk_bn254_plonk_verify_batch_dev): proof v is the 548 bytes at d_proofs + v * proof_stride, its
+    public inputs the n_public Montgomery elements at element v * pub_stride of d_public_inputs.  srs_g2 as in plonk_verify_batch."""
+    k, is_hex = _blob(vk)
+    g2 = np.ascontiguousarray(srs_g2, dtype=np.uint64).reshape(2, 16)
+    p, q = _dev_rows(d_proofs, d_public_inputs, n_public)
+    acc = np.zeros(max(n_proofs, 1), np.uint8)
+    n_acc = C.c_size_t(0)
+    rc = lib().zk_bn254_plonk_verify_batch_dev(p, proof_stride, n_proofs, k, len(k), is_hex, vp(g2), q, pub_stride, n_public, vp(acc), C.addressof(n_acc))
+    return _verdicts(rc, acc, n_proofs)

@@ -67,3 +67,53 @@ def decode_hex_rows(texts: list, to_mont: bool = True, out_stride: int | None = 
 def deserialize_felts_to_numpy(encoded) -> np.ndarray:
     d, n = deserialize_felts(encoded)
     return d.to_numpy(np.uint64, (max(n, 1), 4))[:n]
+
+
+def decode_hex_bytes_rows(texts: list, pitch: int | None = None, out_stride: int | None = None, fill: int = 0, lead: int = 0) -> tuple[np.ndarray, list]:
+    """hex.DecodeString of many texts of one length in one launch (zk_bn254_bytes_decode_hex_rows_dev) -> ((rows, out_stride) bytes, [status per row: _lib.ROW_OK or
+    ROW_BAD_HEX]).  pitch (default: the text's length) is the distance between the rows' texts on the device and `lead` the offset of row 0 from an aligned
+    address: any values will do.  A rejected row's bytes are zeros; the out_stride - n_bytes bytes behind every row are not written and keep `fill`."""
+    rows = [t.encode("ascii") if isinstance(t, str) else bytes(t) for t in texts]
+    if not rows:
+        return np.zeros((0, 0), np.uint8), []
+    if any(len(r) != len(rows[0]) for r in rows) or len(rows[0]) % 2:
+        raise ValueError("the texts of a batch must all have the same even length")
+    n_bytes = len(rows[0]) // 2
+    pitch = len(rows[0]) if pitch is None else pitch
+    stride = n_bytes if out_stride is None else out_stride
+    if pitch < len(rows[0]) or stride < n_bytes:
+        raise ValueError("pitch / out_stride below a row")
+    staged = b"\xee" * lead + b"".join(r + b"\xee" * (pitch - len(r)) for r in rows)
+    d_text = _lib.DeviceBuffer.from_numpy(np.frombuffer(staged, dtype=np.uint8))
+    init = np.full((len(rows), max(stride, 1)), fill, np.uint8)
+    d_out = _lib.DeviceBuffer.from_numpy(init)
+    d_status = _lib.DeviceBuffer.from_numpy(np.full(len(rows), -1, np.int32))
+    check(lib().zk_bn254_bytes_decode_hex_rows_dev(d_text.ptr + lead, pitch, len(rows), n_bytes, d_out.ptr, stride, d_status.ptr, None))
+    return d_out.to_numpy(np.uint8, init.shape), [int(x) for x in d_status.to_numpy(np.int32, (len(rows),))]
+
+
+def decode_public_rows(texts: list, where, pitch: int | None = None, pub_stride: int | None = None, fill: int = 0, lead: int = 0) -> tuple[np.ndarray, list]:
+    """The verifier's reading of many felt-vector texts of one count in one launch (zk_bn254_felts_public_hex_rows_dev): the count header, every character, and
+    of the felts only those at the 0-based positions `where` -> ((rows, pub_stride, 4) Montgomery limbs, [status per row: _lib.ROW_OK / ROW_BAD_COUNT / ROW_BAD_HEX /
+    ROW_NOT_CANONICAL]).  pitch / lead / fill as in decode_hex_bytes_rows; a rejected row's public inputs are zeros."""
+    rows = [t.encode("ascii") if isinstance(t, str) else bytes(t) for t in texts]
+    where = np.ascontiguousarray(where, dtype=np.uint32).reshape(-1)
+    if not rows:
+        return np.zeros((0, len(where), 4), np.uint64), []
+    if any(len(r) != len(rows[0]) for r in rows) or len(rows[0]) < 8 or (len(rows[0]) - 8) % 64:
+        raise ValueError("the texts of a batch must all be 8 + 64 n characters long")
+    n = (len(rows[0]) - 8) // 64
+    pitch = len(rows[0]) if pitch is None else pitch
+    stride = len(where) if pub_stride is None else pub_stride
+    if pitch < len(rows[0]) or stride < len(where):
+        raise ValueError("pitch / pub_stride below a row")
+    staged = b"\xee" * lead + b"".join(r + b"\xee" * (pitch - len(r)) for r in rows)
+    d_text = _lib.DeviceBuffer.from_numpy(np.frombuffer(staged, dtype=np.uint8))
+    d_where = _lib.DeviceBuffer.from_numpy(where) if len(where) else None
+    init = np.full((len(rows), max(stride, 1), 4), fill, np.uint64)
+    d_pub = _lib.DeviceBuffer.from_numpy(init)
+    d_status = _lib.DeviceBuffer.from_numpy(np.full(len(rows), -1, np.int32))
+    check(lib().zk_bn254_felts_public_hex_rows_dev(d_text.ptr + lead, pitch, len(rows), n, d_where.ptr if d_where else None, len(where), d_pub.ptr, stride,
+                                                   d_status.ptr, None))
+    out = d_pub.to_numpy(np.uint64, init.shape)
+    return (out[:, :stride] if stride else out[:, :0]), [int(x) for x in d_status.to_numpy(np.int32, (len(rows),))]
