@@ -29,6 +29,7 @@ struct Fp29 {
     // 2^261 mod p: "one" of the radix-2^261 Montgomery domain (normalised limbs)
     static constexpr uint32_t ONE[9] = {0x157ccc21u, 0x141c2758u, 0x185230d3u, 0x014c0419u, 0x0aa36fb9u, 0x1d4240ceu, 0x11d54c07u, 0x052ac7a8u, 0x000dc836u};
     // k*p with every limb >= 2^30 (the top limb takes the rest): a + BIAS_k - b has no negative limb for a weakly normalised b < k*p
+    static constexpr uint32_t BIAS2[9] = {0x50f9fa8eu, 0x4208c16bu, 0x58e5469cu, 0x45aa459fu, 0x4b0bb2eeu, 0x45b6817fu, 0x414dc280u, 0x5cb84c66u, 0x0060c89au};
     static constexpr uint32_t BIAS4[9] = {0x41f3f51cu, 0x441182d9u, 0x51ca8d3au, 0x4b548b41u, 0x561765deu, 0x4b6d0300u, 0x429b8502u, 0x597098ceu, 0x00c19137u};
     static constexpr uint32_t BIAS8[9] = {0x43e7ea38u, 0x482305b4u, 0x43951a76u, 0x56a91685u, 0x4c2ecbbeu, 0x56da0603u, 0x45370a06u, 0x52e1319eu, 0x01832271u};
     static constexpr uint32_t BIAS12[9] = {0x45dbdf54u, 0x4c34888fu, 0x555fa7b2u, 0x41fda1c8u, 0x4246319fu, 0x42470906u, 0x47d28f0bu, 0x4c51ca6eu, 0x0244b3abu};
@@ -43,8 +44,8 @@ struct Fp29 {
     static constexpr uint32_t QM = 0xa948e6d7u;    // floor(2^53 / ((p >> 232) + 1))
     template <int K>
     static constexpr uint32_t bias(int i) {
-        static_assert(K == 4 || K == 8 || K == 12 || K == 16 || K == 24 || K == 32 || K == 40 || K == 64 || K == 80, "no bias table for this multiple of p");
-        return K == 4 ? BIAS4[i] : K == 8 ? BIAS8[i] : K == 12 ? BIAS12[i] : K == 16 ? BIAS16[i] : K == 24 ? BIAS24[i] : K == 32 ? BIAS32[i]
+        static_assert(K == 2 || K == 4 || K == 8 || K == 12 || K == 16 || K == 24 || K == 32 || K == 40 || K == 64 || K == 80, "no bias table for this multiple of p");
+        return K == 2 ? BIAS2[i] : K == 4 ? BIAS4[i] : K == 8 ? BIAS8[i] : K == 12 ? BIAS12[i] : K == 16 ? BIAS16[i] : K == 24 ? BIAS24[i] : K == 32 ? BIAS32[i]
              : K == 40 ? BIAS40[i] : K == 64 ? BIAS64[i] : BIAS80[i];
     }
 };
@@ -308,20 +309,46 @@ __device__ __forceinline__ XYZZ<Fp> acc29_to_xyzz(const Acc29& A) {
     return XYZZ<Fp>{u29_store(A.x), u29_store(A.y), u29_store(A.zz), u29_store(A.zzz)};
 }
 
-// A += (px, py), an affine point in gnark's memory image (sign already applied).  madd-2008-s; the operation order and
-// bias multiples are exactly those of tools/u29_model.py::madd_fp.
-__device__ __forceinline__ void xyzz_madd29(Acc29& A, const Fp& px, const Fp& py) {
-    if (px.is_zero() && py.is_zero()) return;
-    const U29 x2 = u29_load(px), y2 = u29_load(py);
-    if (A.inf) {
-        const U29 one = u29_one();
-        A.x = u29_mul(x2, one);
-        A.y = u29_mul(y2, one);
-        A.zz = one;
-        A.zzz = one;
-        A.inf = false;
-        return;
-    }
+// ---- native window-table rows (k_build_table writes them, the table variant of k_accumulate reads them): a coordinate is kept in the accumulate loop's own
+// domain -- x * 2^261 mod p, canonical, packed into 8 words like the G1 interchange format below -- so that a row unpacks into limbs below p (nothing to
+// contract, a sign applied by limbs) and an entry stays one 64-byte (G2: 128-byte) segment.  p < 2^254: bit 31 of the top word of y (G2: of y.a0) says
+// "this entry is a point", so a zeroed entry is the point at infinity.  Input class, sign in limb form and the copied first point: tools/u29_model.py
+// (check_table_rows).  (The rows as 9 limbs per coordinate, 72 / 144 bytes, save the unpacking too and measured SLOWER: DESIGN.md 8.)
+static constexpr uint32_t TAB29_VALID = 0x80000000u;
+template <class F>
+struct TabPt {
+    F x, y;
+};
+__device__ __forceinline__ Fp fp_times32(const Fp& v) {  // gnark's image x * 2^256 -> x * 2^261 mod p, canonical
+    Fp t = v;
+#pragma unroll
+    for (int i = 0; i < 5; i++) t = t.dbl();
+    return t;
+}
+__device__ __forceinline__ TabPt<Fp> tab29_make(const Affine<Fp>& a) {  // a point that is not the point at infinity
+    TabPt<Fp> r{fp_times32(a.x), fp_times32(a.y)};
+    r.y.l[7] |= TAB29_VALID;
+    return r;
+}
+__device__ __forceinline__ U29 u29_unpack_tab(const Fp& v) {  // a coordinate that may carry the flag: limbs of the value below p
+    U29 r = u29_unpack(v);
+    r.l[8] &= 0x3fffffu;
+    return r;
+}
+// y or K*p - y by limbs: no carries, NOT normalised (limbs < 2^31; the product schedules take limbs < 2^32)
+template <int K>
+__device__ __forceinline__ U29 u29_sign(const U29& y, bool neg) {
+    U29 r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.l[i] = neg ? Fp29::bias<K>(i) - y.l[i] : y.l[i];
+    return r;
+}
+
+// A += (x2, y2), an affine point in limb form (V << 5 of gnark's image, or a window-table row with the sign applied by limbs); A is not the point at
+// infinity.  madd-2008-s; the operation order and bias multiples are exactly those of tools/u29_model.py::madd_fp.  canon(px, py) yields the point's
+// canonical image for the rare same-x branch.
+template <class Canon>
+__device__ __forceinline__ void xyzz_madd29_body(Acc29& A, const U29& x2, const U29& y2, Canon canon) {
 #ifdef ZKMI_MUL_PAIR
     // the same ten products, eight of them issued as four interleaved pairs of INDEPENDENT ones: (U2, S2), (P^2, R^2), (ZZ1 PP, P PP), (X1 PP, ZZZ1 PPP)
     U29 U2, S2;
@@ -334,6 +361,8 @@ __device__ __forceinline__ void xyzz_madd29(Acc29& A, const Fp& px, const Fp& py
     u29_mul_x2(A.zz, PP, P, PP, ZZ3, PPP);
     if ((((ZZ3.l[0] & Fp29::MASK) * Fp29::PINV) & Fp29::MASK) < 2u) {
         XYZZ<Fp> c = acc29_to_xyzz(A);
+        Fp px, py;
+        canon(px, py);
         c.madd(px, py);
         acc29_from_xyzz(A, c);
         return;
@@ -366,6 +395,8 @@ __device__ __forceinline__ void xyzz_madd29(Acc29& A, const Fp& px, const Fp& py
         // way: take the canonical saturated path, which is correct for every input (inline: an out-of-line call here costs the G1
         // kernel 25 VGPRs and a wave of occupancy).
         XYZZ<Fp> c = acc29_to_xyzz(A);
+        Fp px, py;
+        canon(px, py);
         c.madd(px, py);
         acc29_from_xyzz(A, c);
         return;
@@ -384,6 +415,40 @@ __device__ __forceinline__ void xyzz_madd29(Acc29& A, const Fp& px, const Fp& py
     A.x = X3;
     A.y = Y3;
 #endif
+}
+// A += (px, py), an affine point in gnark's memory image (sign already applied)
+__device__ __forceinline__ void xyzz_madd29(Acc29& A, const Fp& px, const Fp& py) {
+    if (px.is_zero() && py.is_zero()) return;
+    const U29 x2 = u29_load(px), y2 = u29_load(py);
+    if (A.inf) {
+        const U29 one = u29_one();
+        A.x = u29_mul(x2, one);
+        A.y = u29_mul(y2, one);
+        A.zz = one;
+        A.zzz = one;
+        A.inf = false;
+        return;
+    }
+    xyzz_madd29_body(A, x2, y2, [&](Fp& cx, Fp& cy) { cx = px; cy = py; });
+}
+// A += +-p, a window-table row: the flag instead of a comparison with (0, 0), the sign a select by limbs, the first point of a task copied
+__device__ __forceinline__ void xyzz_madd29_tab(Acc29& A, const TabPt<Fp>& p, bool neg) {
+    if (!(p.y.l[7] & TAB29_VALID)) return;
+    const U29 x = u29_unpack(p.x), y = u29_unpack_tab(p.y);
+    if (A.inf) {
+        A.x = x;
+        A.y = u29_sign<2>(y, neg);
+        if (neg) A.y = u29_wnorm(A.y);  // it is subtracted from: weakly normalised, < 2 p
+        A.zz = u29_one();
+        A.zzz = A.zz;
+        A.inf = false;
+        return;
+    }
+    xyzz_madd29_body(A, x, u29_sign<4>(y, neg), [&](Fp& cx, Fp& cy) {
+        cx = u29_store(x);  // x * 2^261 -> gnark's x * 2^256
+        cy = u29_store(y);
+        if (neg) cy = cy.neg();
+    });
 }
 
 // m < 3p is a direct product output: m == 0 mod p ?
@@ -635,24 +700,19 @@ __device__ __forceinline__ U29x2 f2_mulF29(const U29x2& a, const U29x2& b, const
     return U29x2{u29_mul2(a.c0, b.c0, na1, b.c1), u29_mul2(a.c0, b.c1, a.c1, b.c0)};
 }
 
-// A += (px, py): fused multi-product schedule of tools/u29_model.py::madd_fp2_fused -- every stored coordinate is a direct
-// product output (< 2 p), no contraction multiplications:  X3 = R^2 - (P + 2 X1) PP,  Y3 = R (Q - X3) - Y1 PPP.
-__device__ __forceinline__ void xyzz_madd29(Acc29G2& A, const Fp2& px, const Fp2& py) {
-    if (px.is_zero() && py.is_zero()) return;
-    const U29x2 x2 = f2_load29(px), y2 = f2_load29(py);
-    if (A.inf) {
-        A.x = f2_contract29(x2);
-        A.y = f2_contract29(y2);
-        U29 z;
-#pragma unroll
-        for (int i = 0; i < 9; i++) z.l[i] = 0;
-        A.zz = U29x2{u29_one(), z};
-        A.zzz = A.zz;
-        A.inf = false;
-        return;
-    }
-    const U29x2 U2 = f2_mulF29(x2, A.zz, u29_neg<40>(x2.c1));
-    const U29x2 S2 = f2_mulF29(y2, A.zzz, u29_neg<40>(y2.c1));
+__device__ __forceinline__ TabPt<Fp2> tab29_make(const Affine<Fp2>& a) {  // a point that is not the point at infinity
+    TabPt<Fp2> r{Fp2{fp_times32(a.x.a0), fp_times32(a.x.a1)}, Fp2{fp_times32(a.y.a0), fp_times32(a.y.a1)}};
+    r.y.a0.l[7] |= TAB29_VALID;
+    return r;
+}
+
+// A += (x2, y2), A not the point at infinity, nx21 / ny21 = -x2.c1 / -y2.c1: fused multi-product schedule of tools/u29_model.py::madd_fp2_fused -- every
+// stored coordinate is a direct product output (< 2 p), no contraction multiplications:  X3 = R^2 - (P + 2 X1) PP,  Y3 = R (Q - X3) - Y1 PPP.
+// canon(px, py) yields the point's canonical image for the rare same-x branch.
+template <class Canon>
+__device__ __forceinline__ void xyzz_madd29_body(Acc29G2& A, const U29x2& x2, const U29x2& y2, const U29& nx21, const U29& ny21, Canon canon) {
+    const U29x2 U2 = f2_mulF29(x2, A.zz, nx21);
+    const U29x2 S2 = f2_mulF29(y2, A.zzz, ny21);
     const U29x2 P = f2_sub29<4>(U2, A.x);
     const U29x2 R = f2_sub29<4>(S2, A.y);
     const U29 nP1 = u29_neg<8>(P.c1), nR1 = u29_neg<8>(R.c1);
@@ -663,6 +723,8 @@ __device__ __forceinline__ void xyzz_madd29(Acc29G2& A, const Fp2& px, const Fp2
         // 2 P0 P1 == 0 mod p is NECESSARY for P == 0 (same x: doubling or P + (-P)); the canonical saturated path is correct
         // for every input, so it is taken whenever the filter fires.
         XYZZ<Fp2> c = acc29g2_to_xyzz(A);
+        Fp2 px, py;
+        canon(px, py);
         c.madd(px, py);
         acc29g2_from_xyzz(A, c);
         return;
@@ -683,6 +745,46 @@ __device__ __forceinline__ void xyzz_madd29(Acc29G2& A, const Fp2& px, const Fp2
     A.zzz = f2_mulF29(A.zzz, PPP, u29_neg<8>(A.zzz.c1));
     A.x = X3;
     A.y = Y3;
+}
+__device__ __forceinline__ U29x2 f2_one29() {
+    U29 z;
+#pragma unroll
+    for (int i = 0; i < 9; i++) z.l[i] = 0;
+    return U29x2{u29_one(), z};
+}
+// A += (px, py), an affine point in gnark's memory image (sign already applied)
+__device__ __forceinline__ void xyzz_madd29(Acc29G2& A, const Fp2& px, const Fp2& py) {
+    if (px.is_zero() && py.is_zero()) return;
+    const U29x2 x2 = f2_load29(px), y2 = f2_load29(py);
+    if (A.inf) {
+        A.x = f2_contract29(x2);
+        A.y = f2_contract29(y2);
+        A.zz = f2_one29();
+        A.zzz = A.zz;
+        A.inf = false;
+        return;
+    }
+    xyzz_madd29_body(A, x2, y2, u29_neg<40>(x2.c1), u29_neg<40>(y2.c1), [&](Fp2& cx, Fp2& cy) { cx = px; cy = py; });
+}
+// A += +-p, a window-table row (as the G1 form above; the negation of -y.a1 is y.a1 itself)
+__device__ __forceinline__ void xyzz_madd29_tab(Acc29G2& A, const TabPt<Fp2>& p, bool neg) {
+    if (!(p.y.a0.l[7] & TAB29_VALID)) return;
+    const U29x2 x{u29_unpack(p.x.a0), u29_unpack(p.x.a1)}, y{u29_unpack_tab(p.y.a0), u29_unpack(p.y.a1)};
+    if (A.inf) {
+        A.x = x;
+        A.y = U29x2{u29_sign<2>(y.c0, neg), u29_sign<2>(y.c1, neg)};
+        if (neg) A.y = U29x2{u29_wnorm(A.y.c0), u29_wnorm(A.y.c1)};  // subtracted from: weakly normalised, < 2 p
+        A.zz = f2_one29();
+        A.zzz = A.zz;
+        A.inf = false;
+        return;
+    }
+    xyzz_madd29_body(A, x, U29x2{u29_sign<4>(y.c0, neg), u29_sign<4>(y.c1, neg)}, u29_sign<4>(x.c1, true), u29_sign<4>(y.c1, !neg),
+                     [&](Fp2& cx, Fp2& cy) {
+                         cx = Fp2{u29_store(x.c0), u29_store(x.c1)};
+                         cy = Fp2{u29_store(y.c0), u29_store(y.c1)};
+                         if (neg) cy = cy.neg();
+                     });
 }
 
 // ---- XYZZ + XYZZ and doubling for the bucket-reduction tail (G2), fused multi-product form: every output coordinate is a direct

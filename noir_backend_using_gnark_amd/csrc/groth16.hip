@@ -144,7 +144,8 @@ static int pk_build_tables(Groth16PK* Pp, PkAllocs* mem, int table_window_bits, 
     P.tab_h.l1_m = (unsigned)ZK_EXP("ZKMI_L1H_M", 8);   // Z finishes last: its tail is exposed
     P.tab_h.l2_m = (unsigned)ZK_EXP("ZKMI_L2H_M", 0);
     const size_t Ww = P.tab_w.rows() ? P.tab_w.rows() : 1, Wh = P.tab_h.rows() ? P.tab_h.rows() : 1;  // rows held here (all of them unless window-sharded)
-    const size_t bytes = Ww * P.n_wires * (3 * 64 + 128) + Wh * N * 64;
+    const size_t e1 = msm_table_entry_bytes(0), e2 = msm_table_entry_bytes(1);  // table entries (TabPt, ff29.hpp)
+    const size_t bytes = Ww * P.n_wires * (3 * e1 + e2) + Wh * N * e1;
     size_t free_b = 0, total_b = 0;
     ZK_HIP(hipMemGetInfo(&free_b, &total_b));
     // measured (end of round 1): tables pay at every size that fits -- 2^23: 65.8 vs 76.3 ms per proof, 2^24 (84 GB of tables): 126.8 vs
@@ -156,9 +157,9 @@ static int pk_build_tables(Groth16PK* Pp, PkAllocs* mem, int table_window_bits, 
         ZK_TRY(acquire_slot(&g.s));
         hipStream_t st = g.s->stream;
         struct { void** t; const void* src; size_t n, stride, off, esz; unsigned c; size_t Wd; int g2; } jobs[5] = {
-            {&P.t_a, P.d_a, P.n_wires, P.n_wires, 0, 64, P.tab_w.c, Ww, 0},  {&P.t_b, P.d_b, P.n_wires, P.n_wires, 0, 64, P.tab_w.c, Ww, 0},
-            {&P.t_k, P.d_k, nk, P.n_wires, P.n_public, 64, P.tab_w.c, Ww, 0}, {&P.t_z, P.d_z, P.nz, N, 0, 64, P.tab_h.c, Wh, 0},
-            {&P.t_b2, P.d_b2, P.n_wires, P.n_wires, 0, 128, P.tab_w.c, Ww, 1}};
+            {&P.t_a, P.d_a, P.n_wires, P.n_wires, 0, e1, P.tab_w.c, Ww, 0},  {&P.t_b, P.d_b, P.n_wires, P.n_wires, 0, e1, P.tab_w.c, Ww, 0},
+            {&P.t_k, P.d_k, nk, P.n_wires, P.n_public, e1, P.tab_w.c, Ww, 0}, {&P.t_z, P.d_z, P.nz, N, 0, e1, P.tab_h.c, Wh, 0},
+            {&P.t_b2, P.d_b2, P.n_wires, P.n_wires, 0, e2, P.tab_w.c, Ww, 1}};
         for (auto& j : jobs) {
             if (bg_cancelled()) {  // the process is exiting under a background build: what was queued is drained, nothing is published
                 (void)slot_sync(g.s, st);
@@ -354,7 +355,7 @@ int zk_bn254_groth16_pk_bytes(uint64_t handle, size_t* bytes) {
     size_t b = 0;
     if (P.owns) b += nw * (64 + 64 + 128) + nk * 64 + N * 64;
     else if (P.owns_abb) b += nw * (64 + 64 + 128);
-    if (P.tables) b += (size_t)P.tab_w.rows() * nw * (3 * 64 + 128) + (size_t)P.tab_h.rows() * N * 64;
+    if (P.tables) b += (size_t)P.tab_w.rows() * nw * (3 * msm_table_entry_bytes(0) + msm_table_entry_bytes(1)) + (size_t)P.tab_h.rows() * N * msm_table_entry_bytes(0);
     if (P.d_fb_delta) b += FIXED_BASE_TABLE_POINTS * (64 + 128);
     *bytes = b;
     return ZK_OK;

@@ -609,11 +609,22 @@ struct AccBatch {
     void* partial[3];
     uint32_t skip_below[3];
 };
-// one task: the points vals[begin .. end) summed into partial[t]
-template <class F>
+// one task: the points vals[begin .. end) summed into partial[t].  TAB: `pts` is a window table in its native row format (TabPt<F>: the flag for infinity, the sign by limbs, the first point copied, no
+// skip_below -- a table's entries are not point indices); otherwise raw points in gnark's image.  Both share the formula's body (xyzz_madd29_body).
+template <class F, bool TAB = false>
 __device__ __forceinline__ void acc_task(const Affine<F>* __restrict__ pts, XYZZ<F>* __restrict__ partial, const uint32_t* __restrict__ vals, uint32_t skip_below,
                                          uint32_t t, uint32_t begin, uint32_t end) {
-    if constexpr (sizeof(F) == sizeof(Fp)) {
+    if constexpr (TAB) {
+        const TabPt<F>* __restrict__ tab = reinterpret_cast<const TabPt<F>*>(pts);
+        typename std::conditional<sizeof(F) == sizeof(Fp), Acc29, Acc29G2>::type acc;
+        acc.inf = true;
+        for (uint32_t j = begin; j < end; j++) {
+            const uint32_t v = vals[j];
+            xyzz_madd29_tab(acc, gload(tab + (v >> 1)), (v & 1) != 0);
+        }
+        if constexpr (sizeof(F) == sizeof(Fp)) gstore(partial + t, acc29_to_packed(acc));
+        else gstore(partial + t, acc29g2_to_xyzz(acc));
+    } else if constexpr (sizeof(F) == sizeof(Fp)) {
         // G1: unsaturated 9 x 29-bit accumulator (ff29.hpp); converted back to gnark's image once per task
         Acc29 acc;
         acc.inf = true;
@@ -645,20 +656,20 @@ __device__ __forceinline__ void acc_task(const Affine<F>* __restrict__ pts, XYZZ
 // four waves per SIMD (G1) / two (G2) are part of the kernel's design: say so, so that a change that wants a few registers more shows up as spills in
 // -Rpass-analysis=kernel-resource-usage instead of silently dropping a wave (a shorter formula for the second point of a task asked for 134: DESIGN.md 8)
 #define ZK_ACC_BOUNDS __launch_bounds__(256, (sizeof(F) == sizeof(Fp) ? 4 : 2))  // (measured equal to __launch_bounds__(256) in four alternating pairs: unlike the NTT passes, ntt.hip)
-template <class F>
+template <class F, bool TAB = false>
 __global__ ZK_ACC_BOUNDS void k_accumulate(AccBatch batch, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ task_begin,
                                                     const uint32_t* __restrict__ len_key_sorted, const uint32_t* __restrict__ task_sorted, uint32_t L,
                                                     uint32_t max_tasks) {
     const Affine<F>* __restrict__ pts = (const Affine<F>*)batch.pts[blockIdx.y];
     XYZZ<F>* __restrict__ partial = (XYZZ<F>*)batch.partial[blockIdx.y];
-    const uint32_t skip_below = batch.skip_below[blockIdx.y];
+    const uint32_t skip_below = TAB ? 0u : batch.skip_below[blockIdx.y];
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= max_tasks) return;
     uint32_t key = len_key_sorted[i];
     if (key == 0xffffffffu) return;
     uint32_t t = task_sorted[i];
     uint32_t begin = task_begin[t];
-    acc_task<F>(pts, partial, vals, skip_below, t, begin, begin + (L - key));
+    acc_task<F, TAB>(pts, partial, vals, skip_below, t, begin, begin + (L - key));
 }
 #ifdef ZKMI_EXPERIMENTS  // G2 accumulate with ZZ / ZZZ in LDS, three waves per SIMD (round 6: 6 % slower at 2^20, 5 % at 2^24, 3 % witness-like -- DESIGN.md 8)
 #include "experiments/msm_accumulate_g2_lds.inc"
@@ -1286,8 +1297,13 @@ static int msm_accumulate_batch(int nb, Slot* const* sl, const hipStream_t* sts,
     const char* acc_name = sizeof(F) == 32 ? "msm_accumulate_g1" : "msm_accumulate_g2";
     const unsigned full_grid = (unsigned)((max_tasks + 255) / 256);
     bool launched = false;
-#ifdef ZKMI_EXPERIMENTS  // launch of the prefetch / resident accumulate variants
+    const bool tab = P.table_stride != 0;  // d_pts are window tables in their native row format (TabPt<F>): the table variant of the kernel
+    for (int b = 0; tab && b < nb; b++)
+        if (skip_below[b]) return set_err(ZK_ERR_ARG, "skip_below is for the plain method (a table's entries are not point indices)");
+#ifdef ZKMI_EXPERIMENTS  // launch of the prefetch / resident accumulate variants (raw points only: they do not read the tables' row format)
+    if (!tab) {
 #include "experiments/msm_accumulate_variants_launch.inc"
+    }
 #endif
     // occupancy cap (experiment ZKMI_ACC_LDS_KB): an unused dynamic-LDS request of k KB per workgroup lets only floor(160 / k) workgroups -- that many waves per
     // SIMD -- of this kernel be resident per CU, so that the short kernels of other streams (sort, transforms) find registers and wave slots beside it
@@ -1301,19 +1317,22 @@ static int msm_accumulate_batch(int nb, Slot* const* sl, const hipStream_t* sts,
         if (!(attr_done & ((uint64_t)1 << current_entry()))) {
             ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_accumulate<Fp>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_accumulate<Fp2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_accumulate<Fp, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_accumulate<Fp2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             attr_done |= (uint64_t)1 << current_entry();
         }
     }
 #ifdef ZKMI_EXPERIMENTS
     if constexpr (sizeof(F) == sizeof(Fp2)) {
         static const bool g2_lds = ZK_EXP("ZKMI_G2_LDS", 0) != 0;  // experiment (round 6): ZZ / ZZZ of the G2 accumulator in LDS, three waves per SIMD
-        if (g2_lds && !launched) {
+        if (g2_lds && !launched && !tab) {
             ZK_LAUNCH(sl[0], sa, acc_name, k_accumulate_g2_lds, dim3(full_grid, (unsigned)nb), dim3(256), 0, batch, R.vals, R.task_begin, R.lkeys, R.tids, L, (uint32_t)max_tasks);
             launched = true;
         }
     }
 #endif
-    if (!launched) ZK_LAUNCH(sl[0], sa, acc_name, (k_accumulate<F>), dim3(full_grid, (unsigned)nb), dim3(256), acc_shmem, batch, R.vals, R.task_begin, R.lkeys, R.tids, L, (uint32_t)max_tasks);
+    if (!launched && tab) ZK_LAUNCH(sl[0], sa, acc_name, (k_accumulate<F, true>), dim3(full_grid, (unsigned)nb), dim3(256), acc_shmem, batch, R.vals, R.task_begin, R.lkeys, R.tids, L, (uint32_t)max_tasks);
+    else if (!launched) ZK_LAUNCH(sl[0], sa, acc_name, (k_accumulate<F>), dim3(full_grid, (unsigned)nb), dim3(256), acc_shmem, batch, R.vals, R.task_begin, R.lkeys, R.tids, L, (uint32_t)max_tasks);
     if (T) {
         hipEvent_t& e = T->ring[T->next];
         if (!e) ZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1616,16 +1635,16 @@ int msm_prepare_scalars_table(Slot* s, hipStream_t st, const void* d_scalars, si
     return msm_prepare(s, st, P, (const Fr*)d_scalars, n, cfg, out, nullptr, drop_zero_digits);
 }
 
-// T[k * stride + i] = 2^(c*w_k) * P_i as affine points for the rows w_k = row_first + k * row_step < Wd (all rows: row_first = 0, row_step = 1);
-// rows are `stride` entries apart, entries [n, stride) of a row are left untouched (the caller zeroes the buffer: (0,0) = infinity).
-// One-time cost per resident base array.
+// T[k * stride + i] = 2^(c*w_k) * P_i as affine points for the rows w_k = row_first + k * row_step < Wd (all rows: row_first = 0, row_step = 1), in the
+// accumulate kernel's own domain (TabPt<F>, ff29.hpp: x * 2^261 mod p packed, msm_table_entry_bytes per entry); rows are `stride` entries apart, entries [n, stride) of a row are
+// left untouched (the caller zeroes the buffer: a zeroed entry is the point at infinity).  One-time cost per resident base array.
 template <class F>
 __global__ __launch_bounds__(256) void k_build_table(const Affine<F>* __restrict__ pts, uint32_t n, uint32_t stride, uint32_t offset, unsigned c,
-                                                     unsigned Wd, unsigned row_first, unsigned row_step, Affine<F>* __restrict__ table) {
+                                                     unsigned Wd, unsigned row_first, unsigned row_step, TabPt<F>* __restrict__ table) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Affine<F> p = gload(pts + i);
-    if (p.is_inf()) return;  // the caller zeroed the table: (0, 0) in every row
+    if (p.is_inf()) return;  // the caller zeroed the table: no entry of this point carries TAB29_VALID
     // The doubling chain runs through all rows in XYZZ and the rows this table holds are normalised TOGETHER: one inversion per point instead of one per
     // entry (Montgomery's trick over the <= 32 rows of a lane; the per-row coordinates live in private memory) -- 20 doublings + ~37 products per entry
     // instead of 20 doublings + ~385.
@@ -1679,7 +1698,10 @@ __global__ __launch_bounds__(256) void k_build_table(const Affine<F>* __restrict
         run = run * (zs[j] * ws[j]);  // non-zero for points of odd order: a doubling cannot reach infinity
     }
     if (run.is_zero()) {  // a caller-supplied point of even order (outside the prime-order subgroup): row by row
-        for (int j = 0; j < k; j++) gstore(table + (size_t)j * stride + offset + i, XYZZ<F>{xs[j], ys[j], zs[j], ws[j]}.to_affine());
+        for (int j = 0; j < k; j++) {
+            const Affine<F> a = XYZZ<F>{xs[j], ys[j], zs[j], ws[j]}.to_affine();
+            if (!a.is_inf()) gstore(table + (size_t)j * stride + offset + i, tab29_make(a));
+        }
         return;
     }
     F inv = run.inv();
@@ -1687,19 +1709,20 @@ __global__ __launch_bounds__(256) void k_build_table(const Affine<F>* __restrict
         const F t = inv * pre[j];  // 1 / (zz * zzz) of row j
         inv = inv * (zs[j] * ws[j]);
         Affine<F> a{xs[j] * (t * ws[j]), ys[j] * (t * zs[j])};  // x / zz, y / zzz
-        gstore(table + (size_t)j * stride + offset + i, a);
+        gstore(table + (size_t)j * stride + offset + i, tab29_make(a));  // normalised, then * 2^5 mod p
     }
 }
+size_t msm_table_entry_bytes(int is_g2) { return is_g2 ? sizeof(TabPt<Fp2>) : sizeof(TabPt<Fp>); }
 template <class F>
 static int build_table(Slot* s, hipStream_t st, const void* d_pts, size_t n, size_t stride, size_t offset, unsigned c, void* d_table, unsigned row_first,
                        unsigned row_step) {
     MsmTable t;
     t.c = c; t.row_first = row_first; t.row_step = row_step ? row_step : 1;
     unsigned Wd = (255 + c - 1) / c, rows = t.rows();
-    ZK_HIP(hipMemsetAsync(d_table, 0, (size_t)(rows ? rows : 1) * stride * sizeof(Affine<F>), st));
+    ZK_HIP(hipMemsetAsync(d_table, 0, (size_t)(rows ? rows : 1) * stride * sizeof(TabPt<F>), st));
     if (n && rows)
         ZK_LAUNCH(s, st, sizeof(F) == 32 ? "msm_build_table_g1" : "msm_build_table_g2", (k_build_table<F>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                  (const Affine<F>*)d_pts, (uint32_t)n, (uint32_t)stride, (uint32_t)offset, c, Wd, row_first, t.row_step, (Affine<F>*)d_table);
+                  (const Affine<F>*)d_pts, (uint32_t)n, (uint32_t)stride, (uint32_t)offset, c, Wd, row_first, t.row_step, (TabPt<F>*)d_table);
     return ZK_OK;
 }
 int msm_build_table_g1(Slot* s, hipStream_t st, const void* d_pts, size_t n, size_t stride, size_t offset, unsigned c, void* d_table, unsigned row_first,
@@ -2062,6 +2085,25 @@ static void tail_affine(const unsigned char* raw, size_t count, uint64_t* out) {
         memcpy(out + i * (sizeof a / 8), &a, sizeof a);
     }
 }
+// window-table rows (TabPt<F>, ff29.hpp: `nc` coordinates x * 2^261 mod p of 4 words each; the top bit of y's first coordinate: the entry is a point) -> affine images
+static void table_affine(const uint64_t* rows, size_t count, unsigned nc, uint64_t* out) {
+    static const HFp inv32 = HFp{{32, 0, 0, 0}}.to_mont().inv();
+    for (size_t i = 0; i < count; i++) {
+        const uint64_t* e = rows + i * nc * 4;
+        uint64_t* o = out + i * nc * 4;
+        if (!(e[(nc / 2) * 4 + 3] >> 63)) {  // a zeroed entry: the point at infinity, (0, 0)
+            memset(o, 0, nc * 32);
+            continue;
+        }
+        for (unsigned k = 0; k < nc; k++) {
+            HFp v;
+            memcpy(&v, e + k * 4, 32);
+            v.l[3] &= ~((uint64_t)1 << 63);
+            v = v * inv32;  // the raw words are x * 2^261: as gnark's image they read x * 2^5
+            memcpy(o + k * 4, &v, 32);
+        }
+    }
+}
 struct DevFree {  // (hipFree waits for the device: nothing that reads the buffer is in flight when it goes)
     void* p = nullptr;
     ~DevFree() { if (p) (void)hipFree(p); }
@@ -2079,14 +2121,17 @@ static int msm_tail_inspect_run(Slot* s, const zk_msm_tail_request* q, const zk_
     if (n) ZK_HIP(hipMemcpyAsync(d_pts.p, q->points, n * psz, hipMemcpyHostToDevice, st));
     const size_t tab_entries = (size_t)r->table_entries;
     if (tab) {
-        const size_t tab_alloc = ((size_t)std::max(tab->rows(), 1u) * tab->stride + 1) * psz;  // (a table without rows: msm_build_table_g? still clears one row)
+        const size_t tsz = msm_table_entry_bytes(G2);
+        const size_t tab_alloc = ((size_t)std::max(tab->rows(), 1u) * tab->stride + 1) * tsz;  // (a table without rows: msm_build_table_g? still clears one row)
         ZK_HIP(hipMalloc(&d_tab.p, tab_alloc));
         ZK_HIP(hipMemsetAsync(d_tab.p, 0, tab_alloc, st));
         ZK_TRY(G2 ? msm_build_table_g2(s, st, d_pts.p, n, tab->stride, 0, tab->c, d_tab.p, tab->row_first, tab->row_step)
                   : msm_build_table_g1(s, st, d_pts.p, n, tab->stride, 0, tab->c, d_tab.p, tab->row_first, tab->row_step));
         if (r->table && tab_entries) {
             ZK_HIP(hipStreamSynchronize(st));
-            ZK_HIP(hipMemcpy(r->table, d_tab.p, tab_entries * psz, hipMemcpyDeviceToHost));
+            std::vector<uint64_t> rows(tab_entries * (tsz / 8));
+            ZK_HIP(hipMemcpy(rows.data(), d_tab.p, tab_entries * tsz, hipMemcpyDeviceToHost));
+            table_affine(rows.data(), tab_entries, G2 ? 4 : 2, r->table);
         }
     }
     // ---- the preparation (and its arrays, from THIS run: the device picks the task length)
@@ -2259,7 +2304,7 @@ static int bases_make_table(Bases* b, int table_c) {
     // experiment switches: level sizes of the reduction tail of commits against registered bases (0 = the latency-structured default)
     tab.l1_m = (unsigned)ZK_EXP("ZKMI_BASES_L1M", 0);
     tab.l2_m = (unsigned)ZK_EXP("ZKMI_BASES_L2M", 0);
-    const size_t Wd = (255 + tab.c - 1) / tab.c, tbytes = Wd * n * (is_g2 ? 128 : 64);
+    const size_t Wd = (255 + tab.c - 1) / tab.c, tbytes = Wd * n * msm_table_entry_bytes(is_g2);
     size_t free_b = 0, total_b = 0;
     ZK_HIP(hipMemGetInfo(&free_b, &total_b));
     if (tbytes < free_b / 2 && tbytes <= ((size_t)64 << 30)) {
@@ -2388,12 +2433,12 @@ static int msm_bases(uint64_t handle, size_t offset, const void* scalars, size_t
         int rc;
         if (b.is_g2) {
             XYZZ<HFp2> t;
-            rc = msm_g2_accumulate(g.s, st, prep, (const char*)b.d_table + offset * 128, 0, &job);
+            rc = msm_g2_accumulate(g.s, st, prep, (const char*)b.d_table + offset * msm_table_entry_bytes(1), 0, &job);
             if (rc == ZK_OK) rc = msm_g2_finish(job, &t);
             if (rc == ZK_OK) write_affine(t, (zk_g2_affine*)out);
         } else {
             XYZZ<HFp> t;
-            rc = msm_g1_accumulate(g.s, st, prep, (const char*)b.d_table + offset * 64, 0, &job);
+            rc = msm_g1_accumulate(g.s, st, prep, (const char*)b.d_table + offset * msm_table_entry_bytes(0), 0, &job);
             if (rc == ZK_OK) rc = msm_g1_finish(job, &t);
             if (rc == ZK_OK) write_affine(t, (zk_g1_affine*)out);
         }
@@ -2549,7 +2594,7 @@ int zk_bn254_msm_bases_prepared(uint64_t bases, size_t bases_offset, uint64_t sc
             S->geos.push_back(N);
             G = N;
         }
-        table = (const char*)b.d_table + bases_offset * esz;  // index i of the recoding is base bases_offset + i
+        table = (const char*)b.d_table + bases_offset * msm_table_entry_bytes(b.is_g2);  // index i of the recoding is base bases_offset + i
     }
     const MsmPrep& prep = G->prep;
     SlotGuard g;
@@ -2634,7 +2679,7 @@ static int msm_bases_batch(uint64_t handle, size_t offset, const void* const* sc
     MsmJob job;
     job.turnstile = up;  // as in msm_bases: host-slice callers are upstream's goroutines
     XYZZ<HFp> t[3];
-    int rc = msm_g1_accumulate(g.s, st, prep, (const char*)b.d_table + offset * 64, 0, &job);
+    int rc = msm_g1_accumulate(g.s, st, prep, (const char*)b.d_table + offset * msm_table_entry_bytes(0), 0, &job);
     if (rc == ZK_OK) rc = msm_g1_finish_batch(job, t);
     if (rc != ZK_OK) (void)hipStreamSynchronize(st);
     msm_prep_release(&prep);
@@ -2787,7 +2832,7 @@ static int msm_bases_rows(uint64_t handle, size_t offset, const void* scalars, s
         job.keep_final = true;
         job.turnstile = !on_dev;  // as in msm_bases: host-slice callers are upstream's goroutines
         rc = msm_prepare_scalars_table_rows(g.s, st, d_sc, on_dev ? row_stride : n, (unsigned)k, n, cfg, b.tab, &prep, sparse);
-        if (rc == ZK_OK) rc = msm_g1_accumulate(g.s, st, prep, (const char*)b.d_table + offset * 64, 0, &job);
+        if (rc == ZK_OK) rc = msm_g1_accumulate(g.s, st, prep, (const char*)b.d_table + offset * msm_table_entry_bytes(0), 0, &job);
         if (rc == ZK_OK) rc = msm_g1_sets_affine_dev(job, (unsigned)k, d_o, d_c);
         msm_prep_release(&prep);
         if (rc == ZK_OK && !on_dev) {

@@ -27,6 +27,9 @@ struct MsmTable {
                         // latency: right for MSMs whose tail hides under the next accumulate, wrong for the last one of a proof
 };
 unsigned msm_pick_window_table(size_t n);
+// A table entry is kept in the accumulate kernel's own domain (ff29.hpp TabPt: x * 2^261 mod p packed, a flag for "is a point", a zeroed entry = infinity): the
+// size of an affine point, 64 bytes (G1) / 128 (G2) -- what a table of rows() * stride entries takes per entry, and the step of a pointer into one.
+size_t msm_table_entry_bytes(int is_g2);
 int msm_build_table_g1(Slot* s, hipStream_t st, const void* d_pts, size_t n, size_t stride, size_t offset, unsigned c, void* d_table, unsigned row_first = 0,
                        unsigned row_step = 1);
 int msm_build_table_g2(Slot* s, hipStream_t st, const void* d_pts, size_t n, size_t stride, size_t offset, unsigned c, void* d_table, unsigned row_first = 0,

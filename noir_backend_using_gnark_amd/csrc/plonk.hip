@@ -1847,7 +1847,7 @@ int zk_bn254_plonk_pk_lagrange_srs(uint64_t handle) {
     const void* d_table = nullptr;
     MsmTable tab;
     size_t nb = 0;
-    if (bases_table(h, &d_table, &tab, &nb) == ZK_OK) P->bytes += (P->n + 2) * 64 * (1 + (d_table ? (size_t)tab.rows() : 0));
+    if (bases_table(h, &d_table, &tab, &nb) == ZK_OK) P->bytes += (P->n + 2) * (64 + (d_table ? (size_t)tab.rows() * msm_table_entry_bytes(0) : 0));
     return ZK_OK;
 }
 

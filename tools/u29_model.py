@@ -476,11 +476,12 @@ def f2_mulF(O, a, b, na1=None, site="g2f.n"):
     return (O.mulN([(a[0], b[0]), (na1, b[1])]), O.mulN([(a[0], b[1]), (a[1], b[0])]))
 
 
-def madd_fp2_fused(O, X1, Y1, ZZ1, ZZZ1, X2, Y2):
+def madd_fp2_fused(O, X1, Y1, ZZ1, ZZZ1, X2, Y2, nX2=None, nY2=None):
     """G2 madd with fused multi-product reductions: every stored coordinate is a direct product output (< ~3 p), so no
-    contraction multiplications are needed.  X3 = R^2 - (P + 2 X1) PP,  Y3 = R (Q - X3) - Y1 PPP."""
-    U2 = f2_mulF(O, X2, ZZ1, site="g2f.nfresh")
-    S2 = f2_mulF(O, Y2, ZZZ1, site="g2f.nfresh")
+    contraction multiplications are needed.  X3 = R^2 - (P + 2 X1) PP,  Y3 = R (Q - X3) - Y1 PPP.
+    nX2 / nY2: the negated second components of the point, where the caller has them already (window-table rows)."""
+    U2 = f2_mulF(O, X2, ZZ1, nX2, site="g2f.nfresh")
+    S2 = f2_mulF(O, Y2, ZZZ1, nY2, site="g2f.nfresh")
     P = f2_sub(O, U2, X1, "g2f.P")
     R = f2_sub(O, S2, Y1, "g2f.P")
     nP1 = O.neg(P[1], "g2f.n")
@@ -721,6 +722,148 @@ def exact_check_g2(n=60, madd=None):
     print("  exact G2 simulation of %d chained madds: ok" % n)
 
 
+# ----------------------------------------------------------------------------------------------- native window-table rows
+# A window-table coordinate is kept in the accumulate kernel's own domain: x * 2^261 mod p, canonical (< p), packed into 8 words of 32 bits (a G1 entry: x
+# then y, 16 words; a G2 entry: x.a0, x.a1, y.a0, y.a1, 32 words); the kernel unpacks it into 9 limbs below 2^29 (top limb below 2^22).  p < 2^254: bit 31 of
+# the top word of y (G2: of y.a0) says "this entry is a point", so that a zeroed entry is the point at infinity.
+# The kernel applies the digit's sign in limb form, y -> BIAS4 - y (no carries, NOT normalised: every product schedule takes limbs < 2^32), and the first
+# point of a task is copied into the accumulator (negated: BIAS2 - y, weakly normalised: it is subtracted from, so it has to stay below the 4 p of site g1.R).
+TAB_VALID = 1 << 31
+TAB_SIGN_K, TAB_FIRST_K = 4, 2
+
+
+def tab_limbs(x):
+    return limbs((x << RBITS) % Q)
+
+
+def tab_encode(coords):
+    """coords: the canonical field elements of an entry (G1: x, y; G2: x0, x1, y0, y1); None: the point at infinity.  -> 8 words of 32 bits per coordinate"""
+    if coords is None:
+        return None
+    out = [[(val(tab_limbs(c)) >> (32 * i)) & 0xffffffff for i in range(8)] for c in coords]
+    out[len(coords) // 2][7] |= TAB_VALID
+    return [w for c in out for w in c]
+
+
+def tab_decode(words):
+    """-> the limb vectors of the coordinates as the kernel unpacks them (u29_unpack; the flag masked off the top limb), or None for the point at infinity"""
+    nc = len(words) // 8
+    if not words[8 * (nc // 2) + 7] & TAB_VALID:
+        return None
+    out = []
+    for k in range(nc):
+        l = limbs(sum(w << (32 * i) for i, w in enumerate(words[8 * k:8 * k + 8])))
+        l[NL - 1] &= (1 << 22) - 1
+        out.append(l)
+    return out
+
+
+def tab_sign_exact(y, neg):
+    return [b - v for b, v in zip(bias_limbs(TAB_SIGN_K), y)] if neg else list(y)
+
+
+def tab_first_exact(y, neg):
+    return wnorm_exact([b - v for b, v in zip(bias_limbs(TAB_FIRST_K), y)]) if neg else list(y)
+
+
+def b_tab():
+    return B(Q, [MASK] * (NL - 1) + [(Q - 1) >> (W * (NL - 1))])
+
+
+def b_tab_signed():  # y or BIAS4 - y, as the kernel selects them
+    return b_max(b_tab(), B(TAB_SIGN_K * Q + 1, bias_limbs(TAB_SIGN_K)))
+
+
+def b_tab_first():   # y or wnorm(BIAS2 - y): the accumulator's Y after the first point
+    return b_max(b_tab(), b_wnorm(B(TAB_FIRST_K * Q + 1, bias_limbs(TAB_FIRST_K))))
+
+
+def fixed_point_table(is_f2):
+    """The accumulate loop over window-table rows: first point copied, every later one through the generic madd with X2 < p normalised and Y2 sign-applied in
+    limb form.  Must close with the biases the table-less loop already chose (the two variants share the formula's code)."""
+    before = dict(SITE_K)
+    one = B(2 * Q, [MASK] * (NL - 1) + [(2 * Q) >> (W * (NL - 1))])
+    mk = (lambda b: (b, b)) if is_f2 else (lambda b: b)
+    j = (lambda a, b: (b_max(a[0], b[0]), b_max(a[1], b[1]))) if is_f2 else b_max
+    X1, Y1, ZZ1, ZZZ1 = mk(b_tab()), mk(b_tab_first()), mk(one), mk(one)
+    X2, Y2 = mk(b_tab()), mk(b_tab_signed())
+    for it in range(12):
+        if is_f2:
+            X3, Y3, ZZ3, ZZZ3 = madd_fp2_fused(BoundOps, X1, Y1, ZZ1, ZZZ1, X2, Y2, b_tab_signed(), b_tab_signed())
+        else:
+            X3, Y3, ZZ3, ZZZ3 = madd_fp(BoundOps, X1, Y1, ZZ1, ZZZ1, X2, Y2)
+        X1, Y1, ZZ1, ZZZ1 = j(X1, X3), j(Y1, Y3), j(ZZ1, ZZ3), j(ZZZ1, ZZZ3)
+    assert SITE_K == before, "window-table rows need larger biases: %s vs %s" % (SITE_K, before)
+    g = (lambda b: max(b[0].kp(), b[1].kp())) if is_f2 else (lambda b: b.kp())
+    lm = (lambda b: max(max(b[0].lmax), max(b[1].lmax))) if is_f2 else (lambda b: max(b.lmax))
+    assert all(lm(v) < 1 << 32 for v in (X1, Y1, ZZ1, ZZZ1))
+    print("  window-table rows, fixed point bounds (units of p): X %.1f  Y %.1f  ZZ %.2f  ZZZ %.2f, same biases" % (g(X1), g(Y1), g(ZZ1), g(ZZZ1)))
+    return X1, Y1, ZZ1, ZZZ1
+
+
+def exact_check_table(n=300):
+    """chained madds from encoded window-table rows with random signs, against the affine chord rule (G1: curve points; G2: the generic identity)"""
+    random.seed(29)
+    def on_curve_point():
+        while True:
+            x = rand_fe()
+            rhs = (x * x * x + 3) % Q
+            y = pow(rhs, (Q + 1) // 4, Q)
+            if y * y % Q == rhs:
+                return x, y
+    one = limbs((1 << RBITS) % Q)
+    acc = None
+    for it in range(n):
+        P2 = on_curve_point()
+        neg = random.random() < 0.5
+        x2, y2 = tab_decode(tab_encode(P2))
+        assert val(x2) == (P2[0] << RBITS) % Q and val(y2) == (P2[1] << RBITS) % Q
+        S2 = (P2[0], (Q - P2[1]) % Q) if neg else P2
+        if acc is None:
+            X, Y, ZZ, ZZZ = x2, tab_first_exact(y2, neg), list(one), list(one)
+            acc = S2
+        else:
+            X, Y, ZZ, ZZZ = madd_fp(ExactOps, X, Y, ZZ, ZZZ, x2, tab_sign_exact(y2, neg))
+            acc = ec_madd_affine(acc, S2)
+        assert (from_u29(X) * pow(from_u29(ZZ), -1, Q) % Q, from_u29(Y) * pow(from_u29(ZZZ), -1, Q) % Q) == acc
+    print("  exact G1 simulation of %d chained madds from window-table rows: ok" % n)
+    f2m = lambda a, b: ((a[0] * b[0] - a[1] * b[1]) % Q, (a[0] * b[1] + a[1] * b[0]) % Q)
+    f2s = lambda a, b: ((a[0] - b[0]) % Q, (a[1] - b[1]) % Q)
+    def f2inv(a):
+        d = pow((a[0] * a[0] + a[1] * a[1]) % Q, -1, Q)
+        return (a[0] * d % Q, -a[1] * d % Q)
+    def chord(P1, P2):
+        lam = f2m(f2s(P2[1], P1[1]), f2inv(f2s(P2[0], P1[0])))
+        x3 = f2s(f2s(f2m(lam, lam), P1[0]), P2[0])
+        return x3, f2s(f2m(lam, f2s(P1[0], x3)), P1[1])
+    zero = [0] * NL
+    acc = None
+    for it in range(n // 5):
+        P2 = ((rand_fe(), rand_fe()), (rand_fe(), rand_fe()))
+        neg = random.random() < 0.5
+        x0, x1, y0, y1 = tab_decode(tab_encode((P2[0][0], P2[0][1], P2[1][0], P2[1][1])))
+        S2 = (P2[0], ((Q - P2[1][0]) % Q, (Q - P2[1][1]) % Q)) if neg else P2
+        if acc is None:
+            X, Y = (x0, x1), (tab_first_exact(y0, neg), tab_first_exact(y1, neg))
+            ZZ, ZZZ = (list(one), list(zero)), (list(one), list(zero))
+            acc = S2
+        else:
+            X, Y, ZZ, ZZZ = madd_fp2_fused(ExactOps, X, Y, ZZ, ZZZ, (x0, x1), (tab_sign_exact(y0, neg), tab_sign_exact(y1, neg)),
+                                           tab_sign_exact(x1, True), tab_sign_exact(y1, not neg))
+            acc = chord(acc, S2)
+        g = lambda v: (from_u29(v[0]), from_u29(v[1]))
+        assert (f2m(g(X), f2inv(g(ZZ))), f2m(g(Y), f2inv(g(ZZZ)))) == acc
+    print("  exact G2 simulation of %d chained madds from window-table rows: ok" % (n // 5))
+
+
+def check_table_rows():
+    print("window-table rows (x * 2^261 mod p, packed), G1:")
+    fixed_point_table(False)
+    print("window-table rows (x * 2^261 mod p, packed), G2 fused:")
+    fixed_point_table(True)
+    exact_check_table()
+
+
 RC_P = limbs((1 << RBITS) - Q)
 QM_P = (1 << 53) // ((Q >> (W * (NL - 1))) + 1)
 
@@ -785,7 +928,9 @@ def main():
     check_add_dbl_class()
     print("G2 add / dbl class check:")
     check_add_dbl_class_g2()
+    check_table_rows()
     print("bias multiple per subtraction site:", SITE_K)
+    print("bias   2 p:", ", ".join("0x%08xu" % v for v in bias_limbs(2)))
     for k in sorted(set(SITE_K.values())):
         print("bias %3d p:" % k, ", ".join("0x%08xu" % v for v in bias_limbs(k)))
     exact_check()
