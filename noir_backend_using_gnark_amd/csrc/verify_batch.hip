@@ -14,6 +14,8 @@
 //       lanes, prod e(r_i Ar_i, Bs_i) e(-c_0 alpha, beta) e(-sum c_j K_j, gamma) e(-sum r_i Krs_i, delta) == 1; fallback: k_vb_single, 3 n + 1 lanes (the last: e(alpha, beta))
 //   plonk (one lane per proof)   k_pv_gather, k_g1_decompress, k_pv_transcript, k_pv_scalars, k_pv_smul + k_pv_digests, k_pv_kzg, k_pv_smul +
 //       k_pv_combine (A_i, B_i); check: 2 lanes, e(sum A + the G, S1, S2 terms, [1]2) e(-sum B, [alpha]2) == 1; fallback: k_pv_smul + k_pv_single, 2 n lanes
+//   plonk, a key per row (plonk_verify_rows_keys)   the k_pvk_* twins of those kernels read the lane's key from a table in HBM (PvKeyRow, key_of); c_S1 S1 and
+//       c_S2 S2 are two more rows of the second k_pvk_smul launch and part of A_i; check: 2 lanes, e(sum A + the G term, [1]2) e(-sum B, [alpha]2) == 1
 //   kzg (one lane per opening)   k_kzg_combine (lambda_i T_i, lambda_i H_i and the lane's own pair); check: 2 lanes; fallback: 2 n lanes
 #include <string.h>
 
@@ -141,10 +143,8 @@ ZK_D uint32_t row_word(const uint8_t* p, bool aligned) {
 }
 
 // d_v = SHA-256(a_v || b_v), one lane per row (zkmi.h: zk_bn254_rows_sha256_dev; the device forms of the verifiers derive their coefficients from these)
-__global__ __launch_bounds__(64) void k_rows_digest(const uint8_t* __restrict__ a, size_t a_len, size_t a_stride, const uint8_t* __restrict__ b, size_t b_len,
-                                                    size_t b_stride, size_t rows, uint8_t* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows) return;
+ZK_D void rows_digest_lane(size_t i, const uint8_t* __restrict__ a, size_t a_len, size_t a_stride, const uint8_t* __restrict__ b, size_t b_len, size_t b_stride,
+                           uint8_t* __restrict__ out) {
     Sha256Dev h;
     h.reset();
     if (a_len) h.update(a + i * a_stride, a_len);
@@ -155,6 +155,12 @@ __global__ __launch_bounds__(64) void k_rows_digest(const uint8_t* __restrict__ 
     for (int k = 0; k < 8; k++)
 #pragma unroll
         for (int j = 0; j < 4; j++) out[32 * i + 4 * k + j] = (uint8_t)(d[k] >> (24 - 8 * j));
+}
+__global__ __launch_bounds__(64) void k_rows_digest(const uint8_t* __restrict__ a, size_t a_len, size_t a_stride, const uint8_t* __restrict__ b, size_t b_len,
+                                                    size_t b_stride, size_t rows, uint8_t* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    rows_digest_lane(i, a, a_len, a_stride, b, b_len, b_stride, out);
 }
 
 // the 128-byte Groth16 proof into the arrays the decompressors read: raw = Ar (n x 32 bytes) | Bs (n x 64) | Krs (n x 32), as words
@@ -235,6 +241,22 @@ struct PvTerm {
     size_t step;
     const Fr* sc;
 };
+// The many-key entries (zk_bn254_plonk_verify_batch_keys; DESIGN §3.10 "Many keys"): one row per key in HBM, lane i reads row key_of[i] where the single-key
+// kernels take K, kpts, mid and np as arguments.  gamma's prefix "gamma" || RawBytes(S1..Qk) is 517 bytes for every key -- eight blocks and five bytes --, so
+// the midstate's length and the tail's are the same for all keys and stay kernel arguments
+struct PvKeyRow {
+    PvKey K;
+    uint64_t np;
+    Affine<Fp> pts[9];  // S1 S2 S3 Ql Qr Qm Qo Qk G
+    uint32_t mid[8];    // SHA-256 chaining value after the prefix's whole blocks
+    uint8_t pre[24];    // the prefix's last bytes, then "betaalphazeta" (k_pv_transcript's pre)
+};
+// a term of k_pvk_smul: the lane's key's point kpt when kpt >= 0, pts[i] otherwise
+struct PvkTerm {
+    const Affine<Fp>* pts;
+    int kpt;
+    const Fr* sc;
+};
 
 // 256-bit big-endian word image (8 x u32 read straight from the bytes) -> limbs, reduced mod r as fr.SetBytes, Montgomery
 ZK_D Fr fr_from_be_words(const uint32_t* p) {
@@ -276,6 +298,7 @@ __global__ __launch_bounds__(64) void k_pv_transcript(const Affine<Fp>* __restri
                                                       const uint8_t* __restrict__ pre, uint32_t tail_len, uint8_t* __restrict__ valid, Fr* __restrict__ sc) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    // (pvk_transcript_lane below is a copy of these steps: every edit here is to be made there too)
     bool ok = !hdr_bad[i];
     for (int k = 0; k < PV_NPTS; k++) ok = ok && !bad[k * n + i];
     valid[i] = ok;
@@ -311,12 +334,60 @@ __global__ __launch_bounds__(64) void k_pv_transcript(const Affine<Fp>* __restri
         sc[(PV_GAMMA + c) * n + i] = fr_from_digest(d);
     }
 }
+// The many-key kernels (k_pvk_*) read the lane's row of the key table where the single-key kernels take arguments; from k_pv_scalars on, the two kernels of a
+// pair call one per-lane function.  Not here: this is a COPY of k_pv_transcript's steps for k_pvk_transcript, because sharing one function made k_pv_transcript
+// spill 10 SGPRs instead of 5.  The two bodies are kept in step by hand: every edit of one is to be made in the other
+ZK_D void pvk_transcript_lane(size_t i, const Affine<Fp>* __restrict__ pts, const uint8_t* __restrict__ bad, const uint8_t* __restrict__ hdr_bad,
+                              const Fr* __restrict__ pub, size_t ps, size_t n, size_t np, const uint32_t* __restrict__ mid, uint64_t mid_len,
+                              const uint8_t* __restrict__ pre, uint32_t tail_len, uint8_t* __restrict__ valid, Fr* __restrict__ sc) {
+    bool ok = !hdr_bad[i];
+    for (int k = 0; k < PV_NPTS; k++) ok = ok && !bad[k * n + i];
+    valid[i] = ok;
+    if (!ok) return;
+    uint32_t prev[8];
+#pragma unroll 1
+    for (int c = 0; c < 4; c++) {
+        Sha256Dev h;
+        if (c == 0) h.resume(mid, mid_len);
+        else h.reset();
+        const uint32_t off = c == 0 ? 0 : c == 1 ? tail_len : c == 2 ? tail_len + 4 : tail_len + 9, len = c == 0 ? tail_len : c == 2 ? 5 : 4;
+        h.update(pre + off, len);
+        if (c) h.put256(prev);
+        // bindings: gamma: public inputs, L, R, O; beta: none; alpha: Z; zeta: H0, H1, H2 -- 32-byte items
+        const size_t items = c == 0 ? np + 6 : c == 1 ? 0 : c == 2 ? 2 : 6;
+#pragma unroll 1
+        for (size_t j = 0; j < items; j++) {
+            uint32_t l[8];
+            if (c == 0 && j < np) {
+                const Fr w = pub[i * ps + j].from_mont();
+#pragma unroll
+                for (int k = 0; k < 8; k++) l[k] = w.l[k];
+            } else {
+                const size_t q = c == 0 ? j - np : j;
+                const int pt = (c == 0 ? PV_L : c == 2 ? PV_Z : PV_H0) + (int)(q >> 1);
+                raw_half(pts[pt * n + i], (int)(q & 1), l);
+            }
+            h.put256(l);
+        }
+        uint32_t d[8];
+        h.final(d);
+        sha_words_to_limbs(d, prev);  // the next challenge binds the raw digest
+        sc[(PV_GAMMA + c) * n + i] = fr_from_digest(d);
+    }
+}
+__global__ __launch_bounds__(64) void k_pvk_transcript(const Affine<Fp>* __restrict__ pts, const uint8_t* __restrict__ bad, const uint8_t* __restrict__ hdr_bad,
+                                                       const Fr* __restrict__ pub, size_t ps, size_t n, const PvKeyRow* __restrict__ tab,
+                                                       const uint32_t* __restrict__ key_of, uint64_t mid_len, uint32_t tail_len, uint8_t* __restrict__ valid,
+                                                       Fr* __restrict__ sc) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PvKeyRow* R = tab + key_of[i];
+    pvk_transcript_lane(i, pts, bad, hdr_bad, pub, ps, n, (size_t)R->np, R->mid, mid_len, R->pre, tail_len, valid, sc);
+}
 
 // zeta^n, PI(zeta), L1(zeta) and the quotient identity (a lane that fails it is invalid from here on); the digests' scalars.
 // PI(zeta) = sum_j w^j / n (zeta^n - 1) w_j / (zeta - w^j) accumulates as one fraction N / D: one inversion for all denominators
-__global__ __launch_bounds__(64) void k_pv_scalars(const Fr* __restrict__ pub, size_t ps, size_t n, size_t np, PvKey K, uint8_t* __restrict__ valid, Fr* __restrict__ sc) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !valid[i]) return;
+ZK_D void pv_scalars_lane(size_t i, const Fr* __restrict__ pub, size_t ps, size_t n, size_t np, const PvKey& K, uint8_t* __restrict__ valid, Fr* __restrict__ sc) {
     const Fr one = Fr::one();
     const Fr gamma = sc[PV_GAMMA * n + i], beta = sc[PV_BETA * n + i], alpha = sc[PV_ALPHA * n + i], zeta = sc[PV_ZETA * n + i];
     Fr zn = zeta;
@@ -354,6 +425,19 @@ __global__ __launch_bounds__(64) void k_pv_scalars(const Fr* __restrict__ pub, s
     sc[PV_CS3 * n + i] = f1 * f2 * zu * beta * alpha;
     sc[PV_CZ * n + i] = (lz + bz + gamma).neg() * (rz + bz * K.u + gamma) * (oz + bz * K.u.sqr() + gamma) * alpha + aa * l1;
 }
+__global__ __launch_bounds__(64) void k_pv_scalars(const Fr* __restrict__ pub, size_t ps, size_t n, size_t np, PvKey K, uint8_t* __restrict__ valid, Fr* __restrict__ sc) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !valid[i]) return;
+    pv_scalars_lane(i, pub, ps, n, np, K, valid, sc);
+}
+// (the lanes of a wave may run different log_n squaring counts and n_public loop lengths: at most 28 squarings and the largest n_public)
+__global__ __launch_bounds__(64) void k_pvk_scalars(const Fr* __restrict__ pub, size_t ps, size_t n, const PvKeyRow* __restrict__ tab,
+                                                    const uint32_t* __restrict__ key_of, uint8_t* __restrict__ valid, Fr* __restrict__ sc) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !valid[i]) return;
+    const PvKeyRow* R = tab + key_of[i];
+    pv_scalars_lane(i, pub, ps, n, (size_t)R->np, R->K, valid, sc);
+}
 
 // out[t n + i] = k P for term t = blockIdx.y of the table (infinity for an invalid lane)
 __global__ __launch_bounds__(64) void k_pv_smul(const PvTerm* __restrict__ terms, size_t n, const uint8_t* __restrict__ valid, XYZZ<Fp>* __restrict__ out) {
@@ -367,12 +451,24 @@ __global__ __launch_bounds__(64) void k_pv_smul(const PvTerm* __restrict__ terms
     }
     out[blockIdx.y * n + i] = r;
 }
+// the same over PvkTerm: a fixed-point term is the lane's key's point
+__global__ __launch_bounds__(64) void k_pvk_smul(const PvkTerm* __restrict__ terms, const PvKeyRow* __restrict__ tab, const uint32_t* __restrict__ key_of, size_t n,
+                                                 const uint8_t* __restrict__ valid, XYZZ<Fp>* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PvkTerm T = terms[blockIdx.y];
+    XYZZ<Fp> r = XYZZ<Fp>::inf();
+    if (valid[i]) {
+        const Fr k = T.sc[i].from_mont();
+        const Affine<Fp>* p = T.kpt >= 0 ? tab[key_of[i]].pts + T.kpt : T.pts + i;  // (both in HBM)
+        r = scalar_mul(*p, k.l);
+    }
+    out[blockIdx.y * n + i] = r;
+}
 
 // the folded quotient digest H0 + zeta^(n+2) H1 + zeta^(2(n+2)) H2 and the linearised digest (terms 2..7 + Qk), affine
-__global__ __launch_bounds__(64) void k_pv_digests(const Affine<Fp>* __restrict__ pts, const XYZZ<Fp>* __restrict__ t, const Affine<Fp>* __restrict__ kpts, size_t n,
-                                                   const uint8_t* __restrict__ valid, Affine<Fp>* __restrict__ dig) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !valid[i]) return;
+ZK_D void pv_digests_lane(size_t i, const Affine<Fp>* __restrict__ pts, const XYZZ<Fp>* __restrict__ t, const Affine<Fp>* __restrict__ kpts, size_t n,
+                          Affine<Fp>* __restrict__ dig) {
     XYZZ<Fp> fh = t[i];
     fh.add(t[n + i]);
     fh.madd(pts[PV_H0 * n + i]);
@@ -382,17 +478,32 @@ __global__ __launch_bounds__(64) void k_pv_digests(const Affine<Fp>* __restrict_
     dig[i] = fh.to_affine();
     dig[n + i] = lin.to_affine();
 }
+__global__ __launch_bounds__(64) void k_pv_digests(const Affine<Fp>* __restrict__ pts, const XYZZ<Fp>* __restrict__ t, const Affine<Fp>* __restrict__ kpts, size_t n,
+                                                   const uint8_t* __restrict__ valid, Affine<Fp>* __restrict__ dig) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !valid[i]) return;
+    pv_digests_lane(i, pts, t, kpts, n, dig);
+}
+__global__ __launch_bounds__(64) void k_pvk_digests(const Affine<Fp>* __restrict__ pts, const XYZZ<Fp>* __restrict__ t, const PvKeyRow* __restrict__ tab,
+                                                    const uint32_t* __restrict__ key_of, size_t n, const uint8_t* __restrict__ valid, Affine<Fp>* __restrict__ dig) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !valid[i]) return;
+    pv_digests_lane(i, pts, t, tab[key_of[i]].pts, n, dig);
+}
 
 // kzg.deriveGamma over zeta, the seven digests and the claimed values, then the lane's coefficients rho, rho' (SHA-256 of the host's prefix -- mid after 64
 // bytes, then rtail's rtail_len -- || u64 index || tag byte) and the scalars of  rho (D - e G + zeta W) + rho' (Z - zu G + zeta omega W')  and  rho W + rho' W':
 // per-lane terms into PV_T.., the fixed points' coefficients (G, S1, S2) into fix (columns) and fold (rows, k_fr_fold's input)
-__global__ __launch_bounds__(64) void k_pv_kzg(const Affine<Fp>* __restrict__ pts, const Affine<Fp>* __restrict__ dig, const Affine<Fp>* __restrict__ kpts, size_t n,
-                                               size_t c0, PvKey K, const uint32_t* __restrict__ rmid, const uint8_t* __restrict__ rtail, uint32_t rtail_len,
-                                               const uint8_t* __restrict__ valid, Fr* __restrict__ sc, Fr* __restrict__ fix, Fr* __restrict__ fold) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+// FC: how many of the three are folded (the many-key form folds G's alone: S1 and S2 differ per lane and become two more rows of k_pvk_smul)
+template <int FC>
+ZK_D void pv_kzg_lane(size_t i, const Affine<Fp>* __restrict__ pts, const Affine<Fp>* __restrict__ dig, const Affine<Fp>* __restrict__ kpts, size_t n, size_t c0,
+                      const PvKey& K, const uint32_t* __restrict__ rmid, const uint8_t* __restrict__ rtail, uint32_t rtail_len,
+                      const uint8_t* __restrict__ valid, Fr* __restrict__ sc, Fr* __restrict__ fix, Fr* __restrict__ fold) {
     if (!valid[i]) {
-        for (int j = 0; j < 3; j++) fix[j * n + i] = fold[3 * i + j] = Fr::zero();
+        for (int j = 0; j < 3; j++) {
+            if (j < FC) fix[j * n + i] = fold[FC * i + j] = Fr::zero();
+            else fix[j * n + i] = Fr::zero();
+        }
         return;
     }
     const Fr zeta = sc[PV_ZETA * n + i];
@@ -466,7 +577,27 @@ __global__ __launch_bounds__(64) void k_pv_kzg(const Affine<Fp>* __restrict__ pt
     T[9 * n] = rho2;             // W' (second pairing)
     const Fr f[3] = {(rho * e + rho2 * sc[PV_ZU * n + i]).neg(), p[5], p[6]};
 #pragma unroll
-    for (int j = 0; j < 3; j++) fix[j * n + i] = fold[3 * i + j] = f[j];
+    for (int j = 0; j < 3; j++) {
+        if (j < FC) fix[j * n + i] = fold[FC * i + j] = f[j];
+        else fix[j * n + i] = f[j];
+    }
+}
+__global__ __launch_bounds__(64) void k_pv_kzg(const Affine<Fp>* __restrict__ pts, const Affine<Fp>* __restrict__ dig, const Affine<Fp>* __restrict__ kpts, size_t n,
+                                               size_t c0, PvKey K, const uint32_t* __restrict__ rmid, const uint8_t* __restrict__ rtail, uint32_t rtail_len,
+                                               const uint8_t* __restrict__ valid, Fr* __restrict__ sc, Fr* __restrict__ fix, Fr* __restrict__ fold) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    pv_kzg_lane<3>(i, pts, dig, kpts, n, c0, K, rmid, rtail, rtail_len, valid, sc, fix, fold);
+}
+// key_of: the chunk's (the call's array + c0); c0 itself only numbers the lanes for rho, rho'
+__global__ __launch_bounds__(64) void k_pvk_kzg(const Affine<Fp>* __restrict__ pts, const Affine<Fp>* __restrict__ dig, const PvKeyRow* __restrict__ tab,
+                                                const uint32_t* __restrict__ key_of, size_t n, size_t c0, const uint32_t* __restrict__ rmid,
+                                                const uint8_t* __restrict__ rtail, uint32_t rtail_len, const uint8_t* __restrict__ valid, Fr* __restrict__ sc,
+                                                Fr* __restrict__ fix, Fr* __restrict__ fold) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PvKeyRow* R = tab + key_of[i];
+    pv_kzg_lane<1>(i, pts, dig, R->pts, n, c0, R->K, rmid, rtail, rtail_len, valid, sc, fix, fold);
 }
 
 // A_i = sum of terms 0..7, B_i = terms 8 + 9; a copy of each for the folds (which overwrite their input)
@@ -476,6 +607,19 @@ __global__ __launch_bounds__(256) void k_pv_combine(const XYZZ<Fp>* __restrict__
     if (i >= n) return;
     XYZZ<Fp> a = t[i];
     for (int k = 1; k < 8; k++) a.add(t[k * n + i]);
+    XYZZ<Fp> b = t[8 * n + i];
+    b.add(t[9 * n + i]);
+    A[i] = fa[i] = a;
+    B[i] = fb[i] = b;
+}
+// the many-key form: terms 10 and 11 are the lane's c_S1 S1 and c_S2 S2, part of A_i
+__global__ __launch_bounds__(256) void k_pvk_combine(const XYZZ<Fp>* __restrict__ t, size_t n, XYZZ<Fp>* __restrict__ A, XYZZ<Fp>* __restrict__ B,
+                                                     XYZZ<Fp>* __restrict__ fa, XYZZ<Fp>* __restrict__ fb) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    XYZZ<Fp> a = t[i];
+    for (int k = 1; k < 8; k++) a.add(t[k * n + i]);
+    for (int k = 10; k < 12; k++) a.add(t[k * n + i]);
     XYZZ<Fp> b = t[8 * n + i];
     b.add(t[9 * n + i]);
     A[i] = fa[i] = a;
@@ -495,6 +639,28 @@ __global__ __launch_bounds__(256) void k_pv_single(const XYZZ<Fp>* __restrict__ 
     for (int k = 0; k < 3; k++) a.add(t[k * n + i]);
     P[i] = a.to_affine();
     P[n + i] = B[i].to_affine().neg();
+}
+// the many-key fallback: A_i holds the lane's S1 and S2 terms already, t is c_G G alone.  Its launch name, pvk_single, is what says "the per-lane fallback ran"
+__global__ __launch_bounds__(256) void k_pvk_single(const XYZZ<Fp>* __restrict__ A, const XYZZ<Fp>* __restrict__ B, const XYZZ<Fp>* __restrict__ t, size_t n,
+                                                    const uint8_t* __restrict__ valid, Affine<Fp>* __restrict__ P) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (!valid[i]) {
+        P[i] = P[n + i] = Affine<Fp>::inf();
+        return;
+    }
+    XYZZ<Fp> a = A[i];
+    a.add(t[i]);
+    P[i] = a.to_affine();
+    P[n + i] = B[i].to_affine().neg();
+}
+// d_v = SHA-256(row v's a_len bytes || its 32 n_public(key_of[v]) public-input bytes): k_rows_digest with the second span's length the row's own
+__global__ __launch_bounds__(64) void k_rows_digest_keys(const uint8_t* __restrict__ a, size_t a_len, size_t a_stride, const uint8_t* __restrict__ b, size_t b_stride,
+                                                         const PvKeyRow* __restrict__ tab, const uint32_t* __restrict__ key_of, size_t rows,
+                                                         uint8_t* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    rows_digest_lane(i, a, a_len, a_stride, b, (size_t)tab[key_of[i]].np * 32, b_stride, out);
 }
 
 // batch KZG opening check, per lane: T = C - v G + z H;  fa = lambda T and fb = lambda H for the folds;
@@ -1076,6 +1242,269 @@ int zk_bn254_plonk_verify_batch_dev(const void* d_proofs, size_t proof_stride, s
     // the same with SHA-256(d_0 || .. || d_{n-1}) for the data digest, d_v the rows' digests made on the device
     ZK_TRY(rows_digest_of_call(in, 548, n_proofs, n_public, pre.data() + pre.size() - 32));
     return plonk_verify_rows(v, srs_g2, in, n_proofs, n_public, pre, accepted, n_accepted);
+}
+
+// ---- PLONK against many keys (DESIGN 3.10 "Many keys"): row i is a proof for vks[key_of[i]]
+// What both forms decide before a device is looked for: the keys parse (a malformed key j: the host verifier's code and message, "key j" in front), every
+// key_of[i] names a key, pub_stride holds the widest key's public inputs.  pre = tag || KD || SHA-256(srs_g2) || 32 bytes for the data digest, KD as in zkmi.h
+static int plonk_keys_head(size_t n_proofs, const void* const* vks, const size_t* vk_lens, size_t n_keys, int vk_is_hex, const zk_g2_affine srs_g2[2],
+                           const uint32_t* key_of, const void* pub, size_t pub_stride, const char* tag, std::vector<PlonkVk>* vs, std::vector<uint8_t>* pre) {
+    if (n_keys == 0 && n_proofs > 0) return set_err(ZK_ERR_ARG, "n_keys == 0 with %zu proofs", n_proofs);
+    vs->resize(n_keys);
+    size_t max_np = 0;
+    Sha256 kd;
+    uint8_t d[32];
+    const uint64_t nk = n_keys;
+    for (int b = 0; b < 8; b++) d[b] = (uint8_t)(nk >> (8 * b));
+    kd.update(d, 8);
+    for (size_t j = 0; j < n_keys; j++) {
+        if (!vks[j]) return set_err(ZK_ERR_ARG, "key %zu: null pointer", j);
+        const int rc = plonk_vk_parse(vks[j], vk_lens[j], vk_is_hex, &(*vs)[j]);
+        if (rc != ZK_OK) return set_err(rc, "key %zu: %s", j, zk_last_error());
+        max_np = std::max(max_np, (size_t)(*vs)[j].npub);
+        sha(d, (*vs)[j].bytes.data(), (*vs)[j].bytes.size());
+        kd.update(d, 32);
+    }
+    for (size_t i = 0; i < n_proofs; i++) {
+        if (key_of[i] >= n_keys) return set_err(ZK_ERR_ARG, "key_of[%zu] = %u is not below n_keys = %zu", i, key_of[i], n_keys);
+        for (int b = 0; b < 4; b++) d[b] = (uint8_t)(key_of[i] >> (8 * b));
+        kd.update(d, 4);
+    }
+    if (n_proofs > 1 && pub_stride < max_np)
+        return set_err(ZK_ERR_LEN, "pub_stride = %zu is below the %zu public inputs of the widest key", pub_stride, max_np);
+    if (n_proofs && max_np && !pub) return set_err(ZK_ERR_ARG, "null pointer");
+    const size_t tl = strlen(tag);
+    pre->assign(tl + 3 * 32, 0);
+    memcpy(pre->data(), tag, tl);
+    kd.final(pre->data() + tl);
+    sha(pre->data() + tl + 32, srs_g2, 2 * sizeof(zk_g2_affine));
+    return ZK_OK;
+}
+
+// plonk_verify_rows with a key per row.  pre: the coefficients' prefix (64 to 127 bytes); its last 32 bytes, the data digest, are the entry's in the host form
+// and made here in the device form (k_rows_digest_keys needs the key table).  What differs from the single-key core: the key table and key_of in HBM; c_S1 S1
+// and c_S2 S2 as two more rows of the second scalar-multiplication launch, inside A_i; only G's coefficient is folded, so the host multiplies once per chunk
+static int plonk_verify_rows_keys(const std::vector<PlonkVk>& vs, const zk_g2_affine srs_g2[2], const RowsIn& in, size_t n_proofs, const uint32_t* key_of,
+                                  std::vector<uint8_t>& pre, uint8_t* accepted, size_t* n_accepted) {
+    const PairConsts PK = pair_consts();
+    const Affine<HFp> G{HFp::one(), HFp::one() + HFp::one()};
+    const size_t nk = vs.size();
+    std::vector<PvKeyRow> tab(nk);
+    uint64_t mid_len = 0;
+    uint32_t tail_len = 0;
+    size_t max_np = 0;
+    for (size_t j = 0; j < nk; j++) {
+        const PlonkVk& v = vs[j];
+        PvKeyRow& R = tab[j];
+        memset(&R, 0, sizeof R);
+        R.K.n = v.n;
+        while (((uint64_t)1 << R.K.log_n) < v.n) R.K.log_n++;
+        R.K.size_inv = bit_cast_img<Fr>(v.size_inv);
+        R.K.gen = bit_cast_img<Fr>(v.gen);
+        R.K.u = bit_cast_img<Fr>(v.u);
+        R.np = v.npub;
+        max_np = std::max(max_np, (size_t)v.npub);
+        memcpy(R.pts, v.pts, 8 * sizeof(Affine<Fp>));
+        memcpy(R.pts + 8, &G, sizeof G);
+        Sha256 tg;
+        tg.update("gamma", 5);
+        for (int k = 0; k < 8; k++) {
+            uint8_t b[64];
+            g1_raw_bytes(v.pts[k], b);
+            tg.update(b, 64);
+        }
+        tail_len = (uint32_t)tg.fill;  // 5 for every key: the prefix is 517 bytes
+        mid_len = tg.len - tail_len;
+        if (tail_len + 13 > sizeof R.pre) return set_err(ZK_ERR_ARG, "transcript prefix of %llu bytes", (unsigned long long)tg.len);
+        memcpy(R.mid, tg.h, 32);
+        memcpy(R.pre, tg.buf, tail_len);
+        memcpy(R.pre + tail_len, "betaalphazeta", 13);
+    }
+    if (pre.size() < 64 || pre.size() >= 128) return set_err(ZK_ERR_ARG, "coefficient prefix of %zu bytes", pre.size());
+    const uint32_t rtail_len = (uint32_t)(pre.size() - 64);
+    // a chunk's public inputs as they come up in the host form: whole rows of the caller's stride but for the last, which ends with its own n_public
+    const size_t ps = in.pub_stride, pub_elems = max_np ? (std::min(n_proofs, CHUNK) - 1) * ps + max_np : 0;
+
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    Slot* s = g.s;
+    hipStream_t st = s->stream;
+    const size_t ch = std::min(n_proofs, CHUNK);
+    PairCheck pc(s, PK, ch);
+    uint32_t *d_praw, *d_rmid, *d_key_of;
+    Affine<Fp> *d_pts, *d_dig, *d_p;
+    uint8_t *d_stage, *d_bad, *d_hdr, *d_rtail, *d_rowdig;
+    Fr *d_sc, *d_pub, *d_fix;
+    XYZZ<Fp> *d_t, *d_A, *d_B;
+    FoldPair<XYZZ<Fp>> fa, fb;
+    FoldPair<Fr> fold;
+    Affine<Fp2>* d_g2;
+    PvKeyRow* d_tab;
+    PvkTerm* d_terms;
+    int* d_status;
+    ZK_TRY(plan_workspace(s, "plonk_verify_batch_keys", [&](ArenaPlan& p) {
+        p.take(in.on_device ? 1 : ch * 548, d_stage);
+        p.take(ch * PV_NPTS * 8, d_praw);
+        p.take(ch * PV_NPTS, d_pts, d_bad);
+        p.take(ch * PV_NCOL, d_sc);
+        p.take(in.on_device ? 1 : std::max(pub_elems, (size_t)1), d_pub);
+        p.take(ch * 12, d_t);
+        p.take(ch * 3, d_fix);
+        p.take(ch * 2, d_dig, d_p);
+        p.take(ch, d_hdr, d_A, d_B);
+        fa.layout(p, ch);
+        fb.layout(p, ch);
+        fold.layout(p, ch, 1);
+        pc.layout(p, ch * 2);
+        p.take(nk, d_tab);
+        p.take(n_proofs, d_key_of);
+        p.take(in.on_device ? n_proofs * 32 : 1, d_rowdig);
+        p.take(2, d_g2);
+        p.take(8, d_rmid);
+        p.take(64, d_rtail);
+        p.take(16, d_status);
+        p.take(21, d_terms);
+    }));
+    uint8_t* const d_valid = pc.d_valid;
+    ZK_HIP(hipMemcpyAsync(d_tab, tab.data(), nk * sizeof(PvKeyRow), hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_key_of, key_of, n_proofs * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_g2, srs_g2, 2 * 128, hipMemcpyHostToDevice, st));
+    if (in.on_device) {
+        // D = SHA-256(d_0 || .. || d_{n-1}) over the whole call, d_v = SHA-256(row v's proof || its own 32 n_public(key_of[v]) public-input bytes as they lie)
+        ZK_LAUNCH(s, st, "rows_digest_keys", k_rows_digest_keys, dim3(blocks(n_proofs, 64)), dim3(64), 0, in.proofs, (size_t)548, in.proof_stride,
+                  (const uint8_t*)in.pub, ps * 32, (const PvKeyRow*)d_tab, (const uint32_t*)d_key_of, n_proofs, d_rowdig);
+        std::vector<uint8_t> dig(n_proofs * 32);
+        ZK_HIP(hipMemcpyAsync(dig.data(), d_rowdig, dig.size(), hipMemcpyDeviceToHost, st));
+        ZK_TRY(slot_sync(s, st));
+        sha(pre.data() + pre.size() - 32, dig.data(), dig.size());
+    }
+    Sha256 tr;
+    tr.update(pre.data(), pre.size());  // one whole block into the lanes' midstate, the rest left in buf
+    ZK_HIP(hipMemcpyAsync(d_rmid, tr.h, 32, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_rtail, tr.buf, rtail_len, hipMemcpyHostToDevice, st));
+
+    std::vector<PvkTerm> terms(21);
+    size_t tn = 0;  // the table is rebuilt per chunk: its column pointers depend on the chunk's length
+    for (size_t c0 = 0; c0 < n_proofs; c0 += ch) {
+        const size_t n = std::min(ch, n_proofs - c0);
+        if (n != tn) {
+            auto col = [&](int c) { return (const Fr*)(d_sc + (size_t)c * n); };
+            auto lane = [&](int k) { return (const Affine<Fp>*)(d_pts + (size_t)k * n); };
+            // digests: H1 zp, H2 zp^2 | Ql l, Qr r, Qm lr, Qo o, S3 c_s3, Z c_z
+            terms[0] = {lane(PV_H0 + 1), -1, col(PV_ZP)};
+            terms[1] = {lane(PV_H0 + 2), -1, col(PV_ZP2)};
+            terms[2] = {nullptr, 3, col(PV_CLAIM + 2)};
+            terms[3] = {nullptr, 4, col(PV_CLAIM + 3)};
+            terms[4] = {nullptr, 5, col(PV_LR)};
+            terms[5] = {nullptr, 6, col(PV_CLAIM + 4)};
+            terms[6] = {nullptr, 2, col(PV_CS3)};
+            terms[7] = {lane(PV_Z), -1, col(PV_CZ)};
+            // the combined opening check: fh lin L R O W Z W' | W W' | the lane's key's S1, S2
+            const Affine<Fp>* cp[10] = {d_dig, d_dig + n, lane(PV_L), lane(PV_L + 1), lane(PV_L + 2), lane(PV_W), lane(PV_Z), lane(PV_WS), lane(PV_W), lane(PV_WS)};
+            for (int k = 0; k < 10; k++) terms[8 + k] = {cp[k], -1, col(PV_T + k)};
+            terms[18] = {nullptr, 0, d_fix + n};
+            terms[19] = {nullptr, 1, d_fix + 2 * n};
+            // fallback: G
+            terms[20] = {nullptr, 8, d_fix};
+            ZK_HIP(hipMemcpyAsync(d_terms, terms.data(), terms.size() * sizeof(PvkTerm), hipMemcpyHostToDevice, st));
+            tn = n;
+        }
+        RowsIn at;
+        if (in.on_device) {
+            at = RowsIn{in.proofs + c0 * in.proof_stride, in.proof_stride, max_np ? in.pub + c0 * ps : nullptr, ps, true};
+        } else {
+            ZK_HIP(hipMemcpyAsync(d_stage, in.proofs + c0 * 548, n * 548, hipMemcpyHostToDevice, st));
+            const size_t last = (size_t)vs[key_of[c0 + n - 1]].npub;
+            if (max_np && (n - 1) * ps + last)
+                ZK_HIP(hipMemcpyAsync(d_pub, in.pub + c0 * ps, ((n - 1) * ps + last) * 32, hipMemcpyHostToDevice, st));
+            at = RowsIn{d_stage, 548, d_pub, ps, true};
+        }
+        const uint32_t* kof = d_key_of + c0;  // lane i of this chunk is row c0 + i of the call
+        ZK_HIP(hipMemsetAsync(d_bad, 0, n * PV_NPTS, st));
+        ZK_HIP(hipMemsetAsync(d_status, 0, 4, st));
+        const dim3 g64(blocks(n, 64)), g256(blocks(n, 256));
+        ZK_LAUNCH(s, st, "pv_gather", k_pv_gather, g256, dim3(256), 0, at.proofs, at.proof_stride, n, d_praw, d_sc, d_hdr);
+        ZK_TRY(g1_decompress_dev(s, st, d_praw, PV_NPTS * n, d_pts, d_status, d_bad));
+        ZK_LAUNCH(s, st, "pvk_transcript", k_pvk_transcript, g64, dim3(64), 0, (const Affine<Fp>*)d_pts, (const uint8_t*)d_bad, (const uint8_t*)d_hdr, at.pub,
+                  at.pub_stride, n, (const PvKeyRow*)d_tab, kof, mid_len, tail_len, d_valid, d_sc);
+        ZK_LAUNCH(s, st, "pvk_scalars", k_pvk_scalars, g64, dim3(64), 0, at.pub, at.pub_stride, n, (const PvKeyRow*)d_tab, kof, d_valid, d_sc);
+        ZK_LAUNCH(s, st, "pvk_smul", k_pvk_smul, dim3(blocks(n, 64), 8), dim3(64), 0, (const PvkTerm*)d_terms, (const PvKeyRow*)d_tab, kof, n,
+                  (const uint8_t*)d_valid, d_t);
+        ZK_LAUNCH(s, st, "pvk_digests", k_pvk_digests, g64, dim3(64), 0, (const Affine<Fp>*)d_pts, (const XYZZ<Fp>*)d_t, (const PvKeyRow*)d_tab, kof, n,
+                  (const uint8_t*)d_valid, d_dig);
+        ZK_LAUNCH(s, st, "pvk_kzg", k_pvk_kzg, g64, dim3(64), 0, (const Affine<Fp>*)d_pts, (const Affine<Fp>*)d_dig, (const PvKeyRow*)d_tab, kof, n, c0,
+                  (const uint32_t*)d_rmid, (const uint8_t*)d_rtail, rtail_len, (const uint8_t*)d_valid, d_sc, d_fix, fold.a);
+        ZK_LAUNCH(s, st, "pvk_smul", k_pvk_smul, dim3(blocks(n, 64), 12), dim3(64), 0, (const PvkTerm*)(d_terms + 8), (const PvKeyRow*)d_tab, kof, n,
+                  (const uint8_t*)d_valid, d_t);
+        ZK_LAUNCH(s, st, "pvk_combine", k_pvk_combine, g256, dim3(256), 0, (const XYZZ<Fp>*)d_t, n, d_A, d_B, fa.a, fb.a);
+        const XYZZ<Fp>* a_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, fa, n, 1);
+        const XYZZ<Fp>* b_sum = fold_all(s, st, "g1_fold", k_g1_fold, 256, fb, n, 1);
+        const Fr* c_sum = fold_all(s, st, "fr_fold", k_fr_fold, 256, fold, n, 1);
+        XYZZ<HFp> sa, sb;
+        HFr c;
+        ZK_HIP(hipMemcpyAsync(&sa, a_sum, 128, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipMemcpyAsync(&sb, b_sum, 128, hipMemcpyDeviceToHost, st));
+        ZK_HIP(hipMemcpyAsync(&c, c_sum, 32, hipMemcpyDeviceToHost, st));
+        ZK_TRY(pc.sync_valid(n, accepted + c0));
+        if (pc.decided) continue;
+        // e(sum A_i + c_G G, [1]2) e(-sum B_i, [alpha]2) == 1: G is every key's, one host multiplication per chunk however many keys there are
+        Affine<HFp> two[2];
+        {
+            uint32_t k[8];
+            to_canonical_u32(c, k);
+            sa.add(scalar_mul(G, k));
+            two[0] = sa.to_affine();
+            two[1] = sb.to_affine().neg();
+        }
+        ZK_HIP(hipMemcpyAsync(d_p, two, 2 * 64, hipMemcpyHostToDevice, st));
+        ZK_TRY(pc.combined(d_p, 2, nullptr, 0, d_g2, n, accepted + c0));
+        if (pc.decided) continue;
+        // fallback: each valid proof's own two-pairing check; A_i lacks only the lane's c_G G
+        ZK_LAUNCH(s, st, "pvk_smul", k_pvk_smul, dim3(blocks(n, 64), 1), dim3(64), 0, (const PvkTerm*)(d_terms + 20), (const PvKeyRow*)d_tab, kof, n,
+                  (const uint8_t*)d_valid, d_t);
+        ZK_LAUNCH(s, st, "pvk_single", k_pvk_single, g256, dim3(256), 0, (const XYZZ<Fp>*)d_A, (const XYZZ<Fp>*)d_B, (const XYZZ<Fp>*)d_t, n,
+                  (const uint8_t*)d_valid, d_p);
+        ZK_TRY(pc.per_lane(d_p, n, 2, nullptr, 0, d_g2, false, accepted + c0));
+    }
+    *n_accepted = pc.total;
+    return ZK_OK;
+}
+
+int zk_bn254_plonk_verify_batch_keys(const uint8_t* proofs, size_t n_proofs, const void* const* vks, const size_t* vk_lens, size_t n_keys, int vk_is_hex,
+                                     const zk_g2_affine srs_g2[2], const uint32_t* key_of, const zk_fr* public_inputs, size_t pub_stride, uint8_t* accepted,
+                                     size_t* n_accepted) {
+    if (n_accepted) *n_accepted = 0;
+    if (!srs_g2 || !n_accepted || (n_keys && (!vks || !vk_lens)) || (n_proofs && (!proofs || !accepted || !key_of))) return set_err(ZK_ERR_ARG, "null pointer");
+    std::vector<PlonkVk> vs;
+    std::vector<uint8_t> pre;
+    ZK_TRY(plonk_keys_head(n_proofs, vks, vk_lens, n_keys, vk_is_hex, srs_g2, key_of, public_inputs, pub_stride, "zkmi-plonk-batch-keys", &vs, &pre));
+    if (n_proofs == 0) return ZK_OK;
+    ZK_TRY(ensure_init());
+    // rho_i, rho'_i = the low 128 bits of SHA-256(tag || KD || SHA-256(srs_g2) || SHA-256(proofs || each row's own public inputs) || u64 i || 0 / 1)
+    Sha256 h;
+    h.update(proofs, n_proofs * 548);
+    for (size_t i = 0; i < n_proofs; i++) {
+        const size_t np = (size_t)vs[key_of[i]].npub;
+        if (np) h.update(public_inputs + i * pub_stride, np * 32);
+    }
+    h.final(pre.data() + pre.size() - 32);
+    return plonk_verify_rows_keys(vs, srs_g2, RowsIn{proofs, 548, (const Fr*)public_inputs, pub_stride, false}, n_proofs, key_of, pre, accepted, n_accepted);
+}
+
+int zk_bn254_plonk_verify_batch_keys_dev(const void* d_proofs, size_t proof_stride, size_t n_proofs, const void* const* vks, const size_t* vk_lens, size_t n_keys,
+                                         int vk_is_hex, const zk_g2_affine srs_g2[2], const uint32_t* key_of, const void* d_public_inputs, size_t pub_stride,
+                                         uint8_t* accepted, size_t* n_accepted) {
+    if (n_accepted) *n_accepted = 0;
+    if (!srs_g2 || !n_accepted || (n_keys && (!vks || !vk_lens)) || (n_proofs && (!d_proofs || !accepted || !key_of))) return set_err(ZK_ERR_ARG, "null pointer");
+    std::vector<PlonkVk> vs;
+    std::vector<uint8_t> pre;
+    ZK_TRY(plonk_keys_head(n_proofs, vks, vk_lens, n_keys, vk_is_hex, srs_g2, key_of, d_public_inputs, pub_stride, "zkmi-plonk-batch-keys-rows", &vs, &pre));
+    if (n_proofs > 1 && proof_stride < 548) return set_err(ZK_ERR_ARG, "proof_stride = %zu is below the %zu bytes of a proof", proof_stride, (size_t)548);
+    if (n_proofs == 0) return ZK_OK;
+    ZK_TRY(ensure_init());
+    // the same with D = SHA-256(d_0 || .. || d_{n-1}) for the data digest, made by the core once the key table is in HBM
+    const RowsIn in{(const uint8_t*)d_proofs, proof_stride, (const Fr*)d_public_inputs, pub_stride, true};
+    return plonk_verify_rows_keys(vs, srs_g2, in, n_proofs, key_of, pre, accepted, n_accepted);
 }
 
 int zk_bn254_rows_sha256_dev(const void* d_a, size_t a_len, size_t a_stride, const void* d_b, size_t b_len, size_t b_stride, size_t rows, void* d_out, void* stream) {

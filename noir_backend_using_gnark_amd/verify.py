@@ -124,6 +124,64 @@ def plonk_verify_batch(proofs, vk, srs_g2, public_inputs) -> np.ndarray:
     return acc[:n].astype(bool)
 
 
+def _keys_args(vks, key_of, n: int):
+    """(key blobs kept alive, char*[n_keys], size_t[n_keys], n_keys, is_hex, key_of as contiguous uint32) of the many-key entries"""
+    blobs = [_blob(k) for k in vks]
+    if len({h for _, h in blobs}) > 1:
+        raise ValueError("the keys are all bytes or all hex text")
+    raw = [b for b, _ in blobs]
+    ptrs = (C.c_char_p * max(len(raw), 1))(*raw)
+    lens = (C.c_size_t * max(len(raw), 1))(*[len(b) for b in raw])
+    ko = np.asarray(key_of)
+    if ko.shape != (n,) or (n and (ko.min() < 0 or ko.max() >= 1 << 32)):
+        raise ValueError("key_of holds one key index per proof")
+    return raw, ptrs, lens, len(raw), blobs[0][1] if blobs else 0, np.ascontiguousarray(ko, dtype=np.uint32)
+
+
+def plonk_verify_batch_keys(proofs, vks, key_of, srs_g2, public_inputs) -> np.ndarray:
+    """plonk_verify_batch against MANY verifying keys of one SRS in one device call (zk_bn254_plonk_verify_batch_keys): proof i is verified against
+    vks[key_of[i]], all openings of all keys in one two-pairing check.  vks: a sequence of keys (all bytes or all hex str); key_of: n_proofs key indices;
+    public_inputs: (n_proofs, pub_stride, 4) Montgomery limbs, of which row i's first n_public(key_of[i]) elements are read, or a list of per-row arrays of
+    each row's own length, which is padded here.  The verdicts are plonk_verify's per row, a malformed proof being False instead of an error."""
+    pb = _lib.PLONK_PROOF_BYTES
+    blob = bytes(proofs) if isinstance(proofs, (bytes, bytearray)) else b"".join(bytes(x) for x in proofs)
+    if len(blob) % pb:
+        raise ValueError("a PLONK proof is %d bytes (Proof.WriteTo)" % pb)
+    n = len(blob) // pb
+    raw, ptrs, lens, n_keys, is_hex, ko = _keys_args(vks, key_of, n)
+    g2 = np.ascontiguousarray(srs_g2, dtype=np.uint64).reshape(2, 16)
+    if isinstance(public_inputs, (list, tuple)):
+        rows = [np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4) for r in public_inputs]
+        if len(rows) != n:
+            raise ValueError("one row of public inputs per proof")
+        pub = np.zeros((n, max([len(r) for r in rows] + [0]), 4), np.uint64)
+        for i, r in enumerate(rows):
+            pub[i, :len(r)] = r
+    else:
+        pub = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        pub = pub.reshape(n, -1, 4) if pub.size else np.zeros((n, 0, 4), np.uint64)
+    stride = pub.shape[1]
+    acc = np.zeros(max(n, 1), np.uint8)
+    n_acc = C.c_size_t(0)
+    rc = lib().zk_bn254_plonk_verify_batch_keys(blob, n, ptrs, lens, n_keys, is_hex, vp(g2), vp(ko) if n else None, vp(pub) if pub.size else None, stride,
+                                                vp(acc), C.addressof(n_acc))
+    return _verdicts(rc, acc, n)
+
+
+def plonk_verify_batch_keys_dev(d_proofs, proof_stride: int, n_proofs: int, vks, key_of, srs_g2, d_public_inputs, pub_stride: int) -> np.ndarray:
+    """plonk_verify_batch_keys for rows that already lie in HBM (zk_bn254_plonk_verify_batch_keys_dev): proof v is the 548 bytes at d_proofs + v * proof_stride,
+    its public inputs the first n_public(key_of[v]) Montgomery elements at element v * pub_stride of d_public_inputs (None when no key has any); vks and key_of
+    are host data."""
+    raw, ptrs, lens, n_keys, is_hex, ko = _keys_args(vks, key_of, n_proofs)
+    g2 = np.ascontiguousarray(srs_g2, dtype=np.uint64).reshape(2, 16)
+    p, q = _dev_rows(d_proofs, d_public_inputs, None)
+    acc = np.zeros(max(n_proofs, 1), np.uint8)
+    n_acc = C.c_size_t(0)
+    rc = lib().zk_bn254_plonk_verify_batch_keys_dev(p, proof_stride, n_proofs, ptrs, lens, n_keys, is_hex, vp(g2), vp(ko) if n_proofs else None, q or None,
+                                                    pub_stride, vp(acc), C.addressof(n_acc))
+    return _verdicts(rc, acc, n_proofs)
+
+
 def _dev_rows(proofs, public_inputs, n_public: int | None):
     """(device pointer or DeviceBuffer, rows) pair of arguments of the device forms -> raw pointers (0 for no public inputs)"""
     p = proofs.ptr if isinstance(proofs, _lib.DeviceBuffer) else int(proofs)
