@@ -141,70 +141,9 @@ __global__ __launch_bounds__(256) void k_batch_inverse(Fr* __restrict__ a, size_
     }
 }
 
-// ------------------------------------------------------------------------------------------------ scans (K consecutive elements per lane)
-// Exclusive prefix product z[0] = 1, z[i+1] = z[i] * num[i] * dinv[i]  (the rolling products + ratio of BuildRatioCopyConstraint).
-// pass 1: lane totals, block-level inclusive scan (Hillis-Steele in LDS); pass 2: one block scans the block totals; pass 3: apply.
-__global__ __launch_bounds__(256) void k_pscan_local(const Fr* __restrict__ num, const Fr* __restrict__ dinv, size_t n, uint32_t K, Fr* __restrict__ texcl,
-                                                     Fr* __restrict__ btot) {
-    __shared__ Fr sh[256];
-    size_t gt = (size_t)blockIdx.x * 256 + threadIdx.x, base = gt * K;
-    Fr tot = Fr::one();
-    for (uint32_t k = 0; k < K; k++) {
-        size_t i = base + k;
-        if (i < n) tot = tot * (ld(num + i) * ld(dinv + i));
-    }
-    sh[threadIdx.x] = tot;
-    __syncthreads();
-    Fr inc = tot;
-    for (unsigned d = 1; d < 256; d <<= 1) {
-        Fr o = threadIdx.x >= d ? sh[threadIdx.x - d] : Fr::one();
-        __syncthreads();
-        inc = inc * o;
-        sh[threadIdx.x] = inc;
-        __syncthreads();
-    }
-    texcl[gt] = threadIdx.x ? sh[threadIdx.x - 1] : Fr::one();
-    if (threadIdx.x == 255) btot[blockIdx.x] = inc;
-}
-__global__ __launch_bounds__(1024) void k_pscan_blocks(Fr* __restrict__ btot, uint32_t nb) {  // in place: btot[b] <- prod_{b' < b} btot[b']
-    __shared__ Fr sh[1024];
-    Fr carry = Fr::one();
-    for (uint32_t c0 = 0; c0 < nb; c0 += 1024) {
-        uint32_t b = c0 + threadIdx.x;
-        Fr v = b < nb ? ld(btot + b) : Fr::one();
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        Fr inc = v;
-        for (unsigned d = 1; d < 1024; d <<= 1) {
-            Fr o = threadIdx.x >= d ? sh[threadIdx.x - d] : Fr::one();
-            __syncthreads();
-            inc = inc * o;
-            sh[threadIdx.x] = inc;
-            __syncthreads();
-        }
-        Fr excl = carry * (threadIdx.x ? sh[threadIdx.x - 1] : Fr::one());
-        Fr total = sh[1023];
-        __syncthreads();
-        if (b < nb) btot[b] = excl;
-        carry = carry * total;
-    }
-}
-__global__ __launch_bounds__(256) void k_pscan_apply(const Fr* __restrict__ num, const Fr* __restrict__ dinv, size_t n, uint32_t K, const Fr* __restrict__ texcl,
-                                                     const Fr* __restrict__ bexcl, Fr* __restrict__ z) {
-    size_t gt = (size_t)blockIdx.x * 256 + threadIdx.x, base = gt * K;
-    if (base >= n) return;
-    Fr p = ld(bexcl + blockIdx.x) * ld(texcl + gt);
-    for (uint32_t k = 0; k < K; k++) {
-        size_t i = base + k;
-        if (i >= n) break;
-        z[i] = p;
-        p = p * (ld(num + i) * ld(dinv + i));
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ row form of the ratio (ratio_rows_dev below)
-// The kernels above with the ROW as a grid dimension: R witnesses of one domain, every row with its own challenges.  num / den of a chunk of rows are ONE flat
-// array (row v at v * n), so k_batch_inverse serves all rows in one launch as it is.  An edit of a kernel above belongs in its row form.
+// The ROW as a grid dimension: R witnesses of one domain, every row with its own challenges.  num / den of a chunk of rows are ONE flat array (row v at v * n),
+// so k_batch_inverse serves all rows in one launch as it is.  One row -- the single prover's Z -- is R = 1 of the product-scan kernels.
 // omega^k as omega_pow, also for the domain of one element (whose half table holds omega^0 alone)
 __device__ __forceinline__ Fr omega_pow_any(const Fr* __restrict__ tw, uint32_t k, uint32_t n) { return n > 1 ? omega_pow(tw, k, n) : Fr::one(); }
 // k_sigma_lagrange for a caller's permutation: an entry >= 3n raises bit 8 of *status (and counts as 0), as k_perm_from_be does it
@@ -234,7 +173,9 @@ __global__ void k_z_terms_rows(const Fr* __restrict__ l, const Fr* __restrict__ 
     num[out] = (lv + w) * (rv + u * w) * (ov + uu * w);
     den[out] = (lv + beta * ld(sig + i)) * (rv + beta * ld(sig + n + i)) * (ov + beta * ld(sig + 2 * (size_t)n + i));
 }
-// inclusive product scan of one value per lane over a workgroup of 256 (Hillis-Steele in LDS, the loop of k_pscan_local): the caller's lane gets its
+// Exclusive prefix product z[0] = 1, z[i+1] = z[i] * num[i] * dinv[i] (the rolling products + ratio of BuildRatioCopyConstraint), K consecutive elements per lane.
+// pass 1: lane totals, workgroup-level scan; pass 2: one workgroup per row scans the row's workgroup totals; pass 3: apply.
+// The workgroup-level scan: inclusive product scan of one value per lane over a workgroup of 256 (Hillis-Steele in LDS); the caller's lane gets its
 // EXCLUSIVE prefix, *total (lane 255's inclusive value) is valid in lane 255
 __device__ __forceinline__ Fr pscan_wg256(Fr* sh, Fr tot, Fr* total) {
     sh[threadIdx.x] = tot;
@@ -250,7 +191,7 @@ __device__ __forceinline__ Fr pscan_wg256(Fr* sh, Fr tot, Fr* total) {
     *total = inc;
     return threadIdx.x ? sh[threadIdx.x - 1] : Fr::one();
 }
-// k_pscan_local, row blockIdx.y: num / dinv rows n apart, lane prefixes nb * 256 apart, block totals nb apart (nb = gridDim.x)
+// pass 1, row blockIdx.y: num / dinv rows n apart, lane prefixes nb * 256 apart, block totals nb apart (nb = gridDim.x)
 __global__ __launch_bounds__(256) void k_pscan_local_rows(const Fr* __restrict__ num, const Fr* __restrict__ dinv, uint32_t n, uint32_t K, Fr* __restrict__ texcl,
                                                           Fr* __restrict__ btot) {
     __shared__ Fr sh[256];
@@ -267,7 +208,7 @@ __global__ __launch_bounds__(256) void k_pscan_local_rows(const Fr* __restrict__
     texcl[row * gridDim.x * 256 + gt] = excl;
     if (threadIdx.x == 255) btot[row * gridDim.x + blockIdx.x] = inc;
 }
-// k_pscan_blocks, one workgroup per row: row blockIdx.x's nb block totals in place
+// pass 2, one workgroup per row: row blockIdx.x's nb block totals in place, btot[b] <- prod_{b' < b} btot[b']
 __global__ __launch_bounds__(1024) void k_pscan_blocks_rows(Fr* __restrict__ btot, uint32_t nb) {
     __shared__ Fr sh[1024];
     btot += (size_t)blockIdx.x * nb;
@@ -292,7 +233,7 @@ __global__ __launch_bounds__(1024) void k_pscan_blocks_rows(Fr* __restrict__ bto
         carry = carry * total;
     }
 }
-// k_pscan_apply, row blockIdx.y: row v's n values of Z to z + v * out_stride
+// pass 3, row blockIdx.y: row v's n values of Z to z + v * out_stride
 __global__ __launch_bounds__(256) void k_pscan_apply_rows(const Fr* __restrict__ num, const Fr* __restrict__ dinv, uint32_t n, uint32_t K, const Fr* __restrict__ texcl,
                                                           const Fr* __restrict__ bexcl, Fr* __restrict__ z, size_t out_stride) {
     const size_t row = blockIdx.y, gt = (size_t)blockIdx.x * 256 + threadIdx.x, base = gt * K;
@@ -332,119 +273,7 @@ __global__ __launch_bounds__(256) void k_pscan_fused_rows(const Fr* __restrict__
     }
 }
 
-// Suffix recurrence S_i = f_i + a * S_(i+1) over a polynomial f of `len` coefficients: S_0 = f(a), and q_i = S_(i+1) are the coefficients of
-// (f - f(a)) / (X - a) -- kzg.dividePolyByXminusA and polynomial evaluation in one structure.
-// pass 1: lane Horner totals T_t, block-level suffix scan with multiplier A = a^K (A^d doubles per step); lane carry-in and block totals out.
-__global__ __launch_bounds__(256) void k_hscan_local(const Fr* __restrict__ f, size_t len, uint32_t K, Fr a, Fr A, Fr* __restrict__ tcarry, Fr* __restrict__ btot) {
-    __shared__ Fr sh[256];
-    size_t gt = (size_t)blockIdx.x * 256 + threadIdx.x, base = gt * K;
-    Fr acc = Fr::zero();
-    for (int k = (int)K - 1; k >= 0; k--) {
-        size_t i = base + (size_t)k;
-        acc = acc * a;
-        if (i < len) acc = acc + ld(f + i);
-    }
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    Fr val = acc, Ad = A;
-    for (unsigned d = 1; d < 256; d <<= 1) {
-        Fr o = threadIdx.x + d < 256 ? sh[threadIdx.x + d] : Fr::zero();
-        __syncthreads();
-        val = val + Ad * o;
-        sh[threadIdx.x] = val;
-        __syncthreads();
-        Ad = Ad.sqr();
-    }
-    if (tcarry) tcarry[gt] = threadIdx.x < 255 ? sh[threadIdx.x + 1] : Fr::zero();
-    if (threadIdx.x == 0) btot[blockIdx.x] = val;
-}
-// Several polynomials at the SAME point in one launch (plonk.Prove evaluates l, r, o, s1, s2 and then foldedH, linPol at zeta: seven evaluations that are two
-// launches each -- a lane-Horner pass and a single-workgroup block scan that is pure latency): blockIdx.y selects the polynomial.
-struct HscanBatch {
-    const Fr* f[HSCAN_BATCH_MAX];
-    size_t len[HSCAN_BATCH_MAX];
-};
-__global__ __launch_bounds__(256) void k_hscan_local_batch(HscanBatch Bt, uint32_t K, Fr a, Fr A, uint32_t nb, Fr* __restrict__ btot) {
-    __shared__ Fr sh[256];
-    const Fr* __restrict__ f = Bt.f[blockIdx.y];
-    const size_t len = Bt.len[blockIdx.y];
-    size_t gt = (size_t)blockIdx.x * 256 + threadIdx.x, base = gt * K;
-    Fr acc = Fr::zero();
-    for (int k = (int)K - 1; k >= 0; k--) {
-        size_t i = base + (size_t)k;
-        acc = acc * a;
-        if (i < len) acc = acc + ld(f + i);
-    }
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    Fr val = acc, Ad = A;
-    for (unsigned d = 1; d < 256; d <<= 1) {
-        Fr o = threadIdx.x + d < 256 ? sh[threadIdx.x + d] : Fr::zero();
-        __syncthreads();
-        val = val + Ad * o;
-        sh[threadIdx.x] = val;
-        __syncthreads();
-        Ad = Ad.sqr();
-    }
-    if (threadIdx.x == 0) btot[(size_t)blockIdx.y * nb + blockIdx.x] = val;
-}
-// (kzg.hip's k_hscan_*_rows are these three passes with polynomial, length and point per row, and k_hscan_*_dev below -- over scan.hpp's hscan_*_body -- with
-// the row's point in device memory: an edit of one belongs in the others)
-// pass 2: one block; btot[b] <- C_b = sum_{b' > b} btot[b'] * M^(b'-b-1) (M = A^256); *total = S_0 = f(a).
-__global__ __launch_bounds__(1024) void k_hscan_blocks(Fr* __restrict__ btot, uint32_t nb, Fr M, Fr* __restrict__ total) {
-    __shared__ Fr sh[1024];
-    btot += (size_t)blockIdx.x * nb;  // batched form: one workgroup per polynomial, rows of nb block totals, results in total[blockIdx.x]
-    if (total) total += blockIdx.x;
-    Fr carry = Fr::zero();  // S at the start of the chunk above
-    uint32_t nchunks = (nb + 1023) / 1024;
-    Fr M1024 = M;
-    for (int i = 0; i < 10; i++) M1024 = M1024.sqr();
-    for (int c = (int)nchunks - 1; c >= 0; c--) {
-        uint32_t b = (uint32_t)c * 1024 + threadIdx.x;
-        Fr v = b < nb ? ld(btot + b) : Fr::zero();
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        Fr val = v, Md = M;
-        for (unsigned d = 1; d < 1024; d <<= 1) {
-            Fr o = threadIdx.x + d < 1024 ? sh[threadIdx.x + d] : Fr::zero();
-            __syncthreads();
-            val = val + Md * o;
-            sh[threadIdx.x] = val;
-            __syncthreads();
-            Md = Md.sqr();
-        }
-        // val = sum_{u >= t in chunk} v_u M^(u-t); global S''_b = val + M^(1024 - t) * carry
-        Fr next = threadIdx.x < 1023 ? sh[threadIdx.x + 1] : Fr::zero();   // S'' of the next block, chunk-local part
-        uint32_t e = 1023 - threadIdx.x;                                     // M^e * carry completes it
-        Fr pw = Fr::one(), bs = M;
-        for (int i = 0; i < 10; i++) { if ((e >> i) & 1) pw = pw * bs; bs = bs.sqr(); }
-        Fr C = next + pw * carry;
-        Fr chunk_total = sh[0];
-        __syncthreads();
-        if (b < nb) btot[b] = C;
-        carry = chunk_total + M1024 * carry;
-    }
-    if (threadIdx.x == 0 && total) *total = carry;
-}
-// pass 3: q_i = S_(i+1); q may alias f
-__global__ __launch_bounds__(256) void k_hscan_apply(const Fr* f, size_t len, uint32_t K, Fr a, Fr A, const Fr* __restrict__ tcarry, const Fr* __restrict__ bC, Fr* q) {
-    size_t gt = (size_t)blockIdx.x * 256 + threadIdx.x, base = gt * K;
-    if (base >= len) return;
-    uint32_t e = 255 - threadIdx.x;
-    Fr pw = Fr::one(), bs = A;
-    for (int i = 0; i < 8; i++) { if ((e >> i) & 1) pw = pw * bs; bs = bs.sqr(); }
-    Fr S = ld(tcarry + gt) + pw * ld(bC + blockIdx.x);
-    for (int k = (int)K - 1; k >= 0; k--) {
-        size_t i = base + (size_t)k;
-        if (i >= len) continue;
-        Fr fv = ld(f + i);
-        q[i] = S;
-        S = fv + a * S;
-    }
-}
-
-// The three passes with the row as a grid dimension and everything that belongs to a row in device memory (scan.hpp's bodies; k_hscan_local / _batch / _blocks /
-// _apply above and kzg.hip's k_hscan_*_rows are the same passes with their points in the kernel arguments: an edit of one belongs in the others).  Row v reads
+// The three passes of the Horner suffix scan (scan.hpp's bodies) with the row as a grid dimension and everything that belongs to a row in device memory.  Row v reads
 // polynomial p at f[p] + v * stride[p] and takes its point from the row's prepared points: a, A = a^K, M = A^256 at pts + v * pstride + 3 pt[p], written once per
 // row by k_hscan_points_dev / k_lin_points_rows.
 constexpr int HSCAN_DEV_POLYS = 6;
@@ -1041,50 +870,6 @@ static int to_big_coset(Slot* s, hipStream_t st, Fr* dst, const Fr* p, size_t le
     return ntt_dev(s, st, dst, P->logN4, 0, ZK_DIF, 1);
 }
 
-// scratch carved from the slot arena for the scans over `len` elements (scan.hpp)
-int scan_bufs(Slot* s, size_t len, ScanBufs* B) {
-    uint32_t K = (uint32_t)((len + 256 * 1024 - 1) / (256 * 1024));
-    if (K < 8) K = 8;
-    size_t T = (len + K - 1) / K;
-    B->K = K;
-    B->nb = (uint32_t)((T + 255) / 256);
-    B->t = (Fr*)s->alloc((size_t)B->nb * 256 * sizeof(Fr));
-    B->b = (Fr*)s->alloc((size_t)HSCAN_BATCH_MAX * B->nb * sizeof(Fr) + 64);  // HSCAN_BATCH_MAX rows: poly_eval_batch_dev
-    B->total = (Fr*)s->alloc(64);
-    if (!B->t || !B->b || !B->total) return set_err(ZK_ERR_HIP, "PLONK scan workspace was not reserved");
-    return ZK_OK;
-}
-// f_k(a) -> d_out[k] for cnt <= HSCAN_BATCH_MAX polynomials, two launches in all
-int poly_eval_batch_dev(Slot* s, hipStream_t st, const Fr* const* f, const size_t* len, int cnt, const HFr& a, const ScanBufs& B, Fr* d_out) {
-    if (cnt < 1 || cnt > HSCAN_BATCH_MAX) return set_err(ZK_ERR_ARG, "evaluation batch of %d", cnt);
-    HFr A = HFr::one(), M;
-    {
-        HFr base = a;
-        for (uint32_t k = B.K; k; k >>= 1) { if (k & 1) A = A * base; base = base.sqr(); }
-        M = A;
-        for (int i = 0; i < 8; i++) M = M.sqr();
-    }
-    HscanBatch Bt;
-    for (int k = 0; k < HSCAN_BATCH_MAX; k++) { Bt.f[k] = f[k < cnt ? k : 0]; Bt.len[k] = len[k < cnt ? k : 0]; }
-    ZK_LAUNCH(s, st, "plonk_horner_local", k_hscan_local_batch, dim3(B.nb, (unsigned)cnt), dim3(256), 0, Bt, B.K, to_dev(a), to_dev(A), B.nb, B.b);
-    ZK_LAUNCH(s, st, "plonk_horner_blocks", k_hscan_blocks, dim3((unsigned)cnt), dim3(1024), 0, B.b, B.nb, to_dev(M), d_out);
-    return ZK_OK;
-}
-// q = (f - f(a)) / (X - a) (len - 1 coefficients; q may alias f; q[len-1] is set to 0), f(a) -> *d_eval
-int poly_divide_dev(Slot* s, hipStream_t st, const Fr* f, size_t len, const HFr& a, const ScanBufs& B, Fr* q, Fr* d_eval) {
-    HFr A = HFr::one(), M;
-    {
-        HFr base = a;
-        for (uint32_t k = B.K; k; k >>= 1) { if (k & 1) A = A * base; base = base.sqr(); }
-        M = A;
-        for (int i = 0; i < 8; i++) M = M.sqr();
-    }
-    ZK_LAUNCH(s, st, "plonk_horner_local", k_hscan_local, dim3(B.nb), dim3(256), 0, f, len, B.K, to_dev(a), to_dev(A), B.t, B.b);
-    ZK_LAUNCH(s, st, "plonk_horner_blocks", k_hscan_blocks, dim3(1), dim3(1024), 0, B.b, B.nb, to_dev(M), d_eval);
-    ZK_LAUNCH(s, st, "plonk_divide_apply", k_hscan_apply, dim3(B.nb), dim3(256), 0, f, len, B.K, to_dev(a), to_dev(A), (const Fr*)B.t, (const Fr*)B.b, q);
-    return ZK_OK;
-}
-
 // sigma in Lagrange form from the permutation (what BuildRatioCopyConstraint evaluates through pk.Permutation)
 static int make_sigma(PlonkPK* P, Slot* s, hipStream_t st, const uint32_t* d_perm) {
     const size_t n = P->n;
@@ -1173,22 +958,16 @@ static int domains_for(size_t size_system, unsigned* logn, unsigned* logN4) {
 
 // ------------------------------------------------------------------------------------------------ round 2 for R witnesses of one domain
 // iop.BuildRatioCopyConstraint on `rows` triples (l, r, o) that share a domain and a permutation: Z in Lagrange form, regular order, per row.
-//   one row     the five launches of zk_bn254_plonk_prove's round 2, kernel for kernel, on the scan plan the prover uses (scan_bufs of n + 8)
+//   one row     z_chain_dev, the five launches of zk_bn254_plonk_prove's round 2, on the scan plan the prover uses (scan_bufs of n + 8)
 //   more rows   k_z_terms_rows (row = blockIdx.y), ONE k_batch_inverse over the rows * n denominators of the chunk, then
 //                 n <= 256 K:  k_pscan_fused_rows, one workgroup per row                                    -- three launches in all
 //                 above:       k_pscan_local_rows, k_pscan_blocks_rows (one workgroup per row), k_pscan_apply_rows -- five
 //               on the plan of n itself: K = max(8, ceil(n / 2^18)) elements per lane, nb = ceil(n / 256 K) workgroups per row
 // The workspace comes from the slot's arena, RATIO_SCRATCH bytes at a time: more rows than fit (or than a grid's y holds) go in chunks on the same stream.
 constexpr size_t RATIO_SCRATCH = (size_t)1 << 30;
-static void ratio_plan(size_t n, uint32_t* K, uint32_t* nb) {
-    uint32_t k = (uint32_t)((n + 256 * 1024 - 1) / (256 * 1024));
-    if (k < 8) k = 8;
-    *K = k;
-    *nb = (uint32_t)(((n + k - 1) / k + 255) / 256);
-}
 size_t ratio_row_bytes(size_t n) {
     uint32_t K, nb;
-    ratio_plan(n, &K, &nb);
+    scan_plan(n, &K, &nb);
     return (3 * n + (size_t)nb * 257) * sizeof(Fr);
 }
 // rows per chunk when every row also takes `extra` bytes of the caller's (the staging rows of the host entry)
@@ -1207,17 +986,40 @@ int ratio_ws_take(Slot* s, size_t n, size_t chunk, bool single, RatioWs* W) {
     W->scr = (Fr*)s->alloc(W->chunk * n * sizeof(Fr));
     if (!W->num || !W->den || !W->scr) return set_err(ZK_ERR_HIP, "ratio workspace was not reserved");
     if (single) return scan_bufs(s, n + 8, &W->one);
-    ratio_plan(n, &W->K, &W->nb);
+    scan_plan(n, &W->K, &W->nb);
     W->t = (Fr*)s->alloc(W->chunk * W->nb * 256 * sizeof(Fr));
     W->b = (Fr*)s->alloc(W->chunk * W->nb * sizeof(Fr));
     if (!W->t || !W->b) return set_err(ZK_ERR_HIP, "ratio workspace was not reserved");
     return ZK_OK;
 }
+// the three passes of the product scan over R rows of n products on the plan (K, nb): Z of row v to z + v * out_stride
+struct PscanNames {
+    const char *local, *blocks, *apply;
+};
+static const PscanNames kPscanOne = {"plonk_pscan_local", "plonk_pscan_blocks", "plonk_pscan_apply"};
+static const PscanNames kPscanRows = {"plonk_pscan_local_rows", "plonk_pscan_blocks_rows", "plonk_pscan_apply_rows"};
+static int pscan_passes(Slot* s, hipStream_t st, const PscanNames& names, const Fr* num, const Fr* den, size_t n, unsigned R, uint32_t K, uint32_t nb, Fr* t, Fr* b,
+                        Fr* z, size_t out_stride) {
+    ZK_LAUNCH(s, st, names.local, k_pscan_local_rows, dim3(nb, R), dim3(256), 0, num, den, (uint32_t)n, K, t, b);
+    ZK_LAUNCH(s, st, names.blocks, k_pscan_blocks_rows, dim3(R), dim3(1024), 0, b, nb);
+    ZK_LAUNCH(s, st, names.apply, k_pscan_apply_rows, dim3(nb, R), dim3(256), 0, num, den, (uint32_t)n, K, (const Fr*)t, (const Fr*)b, z, out_stride);
+    return ZK_OK;
+}
+// Z of ONE row with its challenges on the host, five launches: k_z_terms, k_batch_inverse and the three passes on the plan of SB (the prover's scan_bufs(n + 8)).
+// num, den, scr: n elements each.
+static int z_chain_dev(Slot* s, hipStream_t st, const Fr* tw, const HFr& u, const Fr* sig, const Fr* l, const Fr* r, const Fr* o, size_t n, const HFr& beta,
+                       const HFr& gamma, Fr* num, Fr* den, Fr* scr, const ScanBufs& SB, Fr* z) {
+    ZK_LAUNCH(s, st, "plonk_z_terms", k_z_terms, dim3(grid_of(n)), dim3(256), 0, l, r, o, sig, tw, (uint32_t)n, to_dev(beta), to_dev(beta * u), to_dev(beta * (u * u)),
+              to_dev(gamma), num, den);
+    const size_t lanes = (n + BINV_K - 1) / BINV_K;
+    ZK_LAUNCH(s, st, "plonk_batch_inverse", k_batch_inverse, dim3(grid_of(lanes)), dim3(256), 0, den, n, scr);
+    return pscan_passes(s, st, kPscanOne, num, den, n, 1, SB.K, SB.nb, SB.t, SB.b, z, 0);
+}
 // row v: wires at l / r / o + v * in_stride, challenges d_beta[v], d_gamma[v] (device), Z to z + v * out_stride.  sig = S1 | S2 | S3 in Lagrange form.
 int ratio_rows_dev(Slot* s, hipStream_t st, const Domain* d0, const Fr* sig, const Fr* l, const Fr* r, const Fr* o, size_t in_stride, size_t rows,
                    const Fr* d_beta, const Fr* d_gamma, Fr* z, size_t out_stride, const RatioWs& W) {
     const size_t n = (size_t)1 << d0->logn;
-    const HFr u = d0->coset, uu = u * u;
+    const HFr u = d0->coset;
     const Fr* tw = d0->tw;
     if (W.single) {
         if (rows != 1) return set_err(ZK_ERR_ARG, "internal: one-row ratio workspace for %zu rows", rows);
@@ -1225,23 +1027,12 @@ int ratio_rows_dev(Slot* s, hipStream_t st, const Domain* d0, const Fr* sig, con
         ZK_HIP(hipMemcpyAsync(&bg[0], d_beta, sizeof(Fr), hipMemcpyDeviceToHost, st));
         ZK_HIP(hipMemcpyAsync(&bg[1], d_gamma, sizeof(Fr), hipMemcpyDeviceToHost, st));
         ZK_HIP(hipStreamSynchronize(st));
-        const HFr beta = bg[0], gamma = bg[1];
-        const ScanBufs& SB = W.one;
-        ZK_LAUNCH(s, st, "plonk_z_terms", k_z_terms, dim3(grid_of(n)), dim3(256), 0, l, r, o, sig, tw, (uint32_t)n, to_dev(beta), to_dev(beta * u), to_dev(beta * uu),
-                  to_dev(gamma), W.num, W.den);
-        {
-            size_t lanes = (n + BINV_K - 1) / BINV_K;
-            ZK_LAUNCH(s, st, "plonk_batch_inverse", k_batch_inverse, dim3(grid_of(lanes)), dim3(256), 0, W.den, n, W.scr);
-        }
-        ZK_LAUNCH(s, st, "plonk_pscan_local", k_pscan_local, dim3(SB.nb), dim3(256), 0, (const Fr*)W.num, (const Fr*)W.den, n, SB.K, SB.t, SB.b);
-        ZK_LAUNCH(s, st, "plonk_pscan_blocks", k_pscan_blocks, dim3(1), dim3(1024), 0, SB.b, SB.nb);
-        ZK_LAUNCH(s, st, "plonk_pscan_apply", k_pscan_apply, dim3(SB.nb), dim3(256), 0, (const Fr*)W.num, (const Fr*)W.den, n, SB.K, (const Fr*)SB.t, (const Fr*)SB.b, z);
-        return ZK_OK;
+        return z_chain_dev(s, st, tw, u, sig, l, r, o, n, bg[0], bg[1], W.num, W.den, W.scr, W.one, z);
     }
     for (size_t first = 0; first < rows; first += W.chunk) {
         const unsigned R = (unsigned)std::min(W.chunk, rows - first);
         ZK_LAUNCH(s, st, "plonk_z_terms_rows", k_z_terms_rows, dim3(grid_of(n), R), dim3(256), 0, l + first * in_stride, r + first * in_stride, o + first * in_stride,
-                  in_stride, sig, tw, (uint32_t)n, d_beta + first, d_gamma + first, to_dev(u), to_dev(uu), W.num, W.den);
+                  in_stride, sig, tw, (uint32_t)n, d_beta + first, d_gamma + first, to_dev(u), to_dev(u * u), W.num, W.den);
         {
             const size_t cnt = (size_t)R * n, lanes = (cnt + BINV_K - 1) / BINV_K;
             ZK_LAUNCH(s, st, "plonk_batch_inverse", k_batch_inverse, dim3(grid_of(lanes)), dim3(256), 0, W.den, cnt, W.scr);
@@ -1251,10 +1042,7 @@ int ratio_rows_dev(Slot* s, hipStream_t st, const Domain* d0, const Fr* sig, con
             ZK_LAUNCH(s, st, "plonk_pscan_fused_rows", k_pscan_fused_rows, dim3(R), dim3(256), 0, (const Fr*)W.num, (const Fr*)W.den, (uint32_t)n, W.K, zc, out_stride);
             continue;
         }
-        ZK_LAUNCH(s, st, "plonk_pscan_local_rows", k_pscan_local_rows, dim3(W.nb, R), dim3(256), 0, (const Fr*)W.num, (const Fr*)W.den, (uint32_t)n, W.K, W.t, W.b);
-        ZK_LAUNCH(s, st, "plonk_pscan_blocks_rows", k_pscan_blocks_rows, dim3(R), dim3(1024), 0, W.b, W.nb);
-        ZK_LAUNCH(s, st, "plonk_pscan_apply_rows", k_pscan_apply_rows, dim3(W.nb, R), dim3(256), 0, (const Fr*)W.num, (const Fr*)W.den, (uint32_t)n, W.K, (const Fr*)W.t,
-                  (const Fr*)W.b, zc, out_stride);
+        ZK_TRY(pscan_passes(s, st, kPscanRows, W.num, W.den, n, R, W.K, W.nb, W.t, W.b, zc, out_stride));
     }
     return ZK_OK;
 }
@@ -1366,11 +1154,11 @@ struct OpenWs {
 };
 size_t open_row_bytes(size_t len, unsigned npoly, size_t pt, size_t fold) {
     uint32_t K, nb;
-    ratio_plan(len, &K, &nb);
+    scan_plan(len, &K, &nb);
     return (pt + (size_t)npoly * nb + (size_t)nb * 256 + fold) * sizeof(Fr);
 }
 static int open_ws_take(Slot* s, size_t len, size_t rows, unsigned npoly, size_t pt, size_t fold, OpenWs* W) {
-    ratio_plan(len, &W->K, &W->nb);
+    scan_plan(len, &W->K, &W->nb);
     const size_t row = open_row_bytes(len, npoly, pt, fold);
     W->chunk = std::min(std::min(rows, RATIO_GRID_ROWS), std::max<size_t>(1, OPEN_SCRATCH / row));
     ZK_TRY(s->reserve(W->chunk * row + 5 * 256));
@@ -2069,15 +1857,7 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
     // z's chain (short kernels) on the slot's high-priority stream instead of behind them, and its commitment starts as soon as THAT stream is done
     static const bool z_side = ZK_EXP("ZKMI_PLONK_Z_SIDE", 0) != 0;
     hipStream_t zst = (z_side && used_lagrange) ? s->hi() : st;
-    ZK_LAUNCH(s, zst, "plonk_z_terms", k_z_terms, dim3(grid_of(n)), dim3(256), 0, (const Fr*)l_lag, (const Fr*)r_lag, (const Fr*)o_lag, (const Fr*)P->sig, (const Fr*)d0->tw,
-              (uint32_t)n, to_dev(beta), to_dev(beta * u), to_dev(beta * uu), to_dev(gamma), num, den);
-    {
-        size_t lanes = (n + BINV_K - 1) / BINV_K;
-        ZK_LAUNCH(s, zst, "plonk_batch_inverse", k_batch_inverse, dim3(grid_of(lanes)), dim3(256), 0, den, n, W + 14 * S);
-    }
-    ZK_LAUNCH(s, zst, "plonk_pscan_local", k_pscan_local, dim3(SB.nb), dim3(256), 0, (const Fr*)num, (const Fr*)den, n, SB.K, SB.t, SB.b);
-    ZK_LAUNCH(s, zst, "plonk_pscan_blocks", k_pscan_blocks, dim3(1), dim3(1024), 0, SB.b, SB.nb);
-    ZK_LAUNCH(s, zst, "plonk_pscan_apply", k_pscan_apply, dim3(SB.nb), dim3(256), 0, (const Fr*)num, (const Fr*)den, n, SB.K, (const Fr*)SB.t, (const Fr*)SB.b, bz_);
+    ZK_TRY(z_chain_dev(s, zst, d0->tw, u, P->sig, l_lag, r_lag, o_lag, n, beta, gamma, num, den, W + 14 * S, SB, bz_));
     ZK_HIP(hipMemsetAsync(bz_ + n, 0, 8 * sizeof(Fr), zst));
     ZK_TRY(to_canonical(s, zst, bz_, logn));
     {

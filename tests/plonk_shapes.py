@@ -21,7 +21,7 @@ DEGENERATE = ("zeros", "zeros+identity_perm")   # with zero blinders: l = r = o 
 
 
 def scan_plan(length):
-    """(K, nb) of csrc/plonk.hip scan_bufs(): K consecutive elements per lane, nb workgroups of 256 lanes"""
+    """(K, nb) of csrc/scan.hpp scan_plan(): K consecutive elements per lane, nb workgroups of 256 lanes"""
     K = max(8, (length + 256 * 1024 - 1) // (256 * 1024))
     lanes = (length + K - 1) // K
     return K, (lanes + 255) // 256

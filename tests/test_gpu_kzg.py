@@ -23,6 +23,7 @@ M = pl.ints_to_mont_np
 ALPHA = 0x2b7e151628aed2a6abf7158809cf4f3c762e7160f38b4da56a784d9045190cfe % R
 SIZE = (1 << 16) + 8  # the SRS's full size: one of the lengths
 LENGTHS = (1, 2, 255, 256, 257, (1 << 11) + 3, 1 << 16, SIZE)
+BOUNDARY = (8, 9, 2047, 2048, 2049, 2050)  # the scan's lane boundary and workgroup boundary at K = 8 (csrc/scan.hpp scan_plan)
 
 
 def g1_img(P):
@@ -117,6 +118,20 @@ def test_open_many_unequal_rows(env, count):
         check_many(env, srs, cases, on_device=(t + count) % 2 == 1)
 
 
+def test_open_at_lane_and_workgroup_boundaries(env):
+    """K = 8 coefficients per lane, 2048 per workgroup: a row that ends with a lane, with a workgroup, one coefficient either side -- alone, and in one call next to
+    a long row, whose workgroups above the short rows' ends contribute nothing"""
+    rng = random.Random(24)
+    cases = [case(rng, n, k % 4) for k, n in enumerate(BOUNDARY)]
+    for k, (p, z) in enumerate(cases):
+        h, v = env["srs"][k % 2].open(M(p), M([z])[0])
+        wh, wv = want_open(env, p, z)
+        assert from_mont_limbs(v) == [wv] and h.tobytes() == wh.tobytes(), len(p)
+    cases.insert(3, case(rng, 1 << 16, 3))  # between 2047 and 2048
+    for t, srs in enumerate(env["srs"]):
+        check_many(env, srs, cases, on_device=t == 1)
+
+
 def test_open_many_same_polynomial_or_same_point(env):
     rng = random.Random(23)
     p, q = rand_poly(rng, 300), rand_poly(rng, 257)
@@ -125,6 +140,30 @@ def test_open_many_same_polynomial_or_same_point(env):
         check_many(env, srs, [(p, z1), (p, z2)], on_device=False)
         check_many(env, srs, [(p, z1), (q, z1)], on_device=True)
         check_many(env, srs, [(p, z1), (p, z1), (p, z1)], on_device=False)
+
+
+def check_batch(env, polys, z, flip):
+    """batch_open_single_point of polys at z on both SRS forms, from host arrays on one and from DeviceBuffers on the other, against the oracle's fold and division"""
+    lens = [len(p) for p in polys]
+    digests = np.stack([commit(env, p) for p in polys])
+    claimed = [pl.poly_eval(p, z) for p in polys]
+    kg = pl.kzg_derive_gamma(z, [pl.g1_from_np(d) for d in digests], claimed)
+    folded, fe, acc = [0] * max(lens), 0, 1
+    for p, v in zip(polys, claimed):
+        for j, c in enumerate(p):
+            folded[j] = (folded[j] + c * acc) % R
+        fe = (fe + v * acc) % R
+        acc = acc * kg % R
+    want_h = commit(env, pl.divide_by_x_minus_a(folded, fe, z))
+    for t, srs in enumerate(env["srs"]):
+        arrs = [M(p) for p in polys]
+        on_device = (t + flip) % 2 == 1
+        bufs = [_lib.DeviceBuffer.from_numpy(a) for a in arrs] if on_device else None
+        h, v = srs.batch_open_single_point(bufs if on_device else arrs, digests, M([z])[0], lens if on_device else None)
+        assert from_mont_limbs(v) == claimed
+        assert h.tobytes() == want_h.tobytes()
+        for b in bufs or []:
+            b.free()
 
 
 @pytest.mark.parametrize("count", [1, 2, 3, 7, 8, 9, 20])
@@ -138,25 +177,22 @@ def test_batch_open_single_point(env, count):
     z = (rng.randrange(R), 0, 1, rng.randrange(R), rng.randrange(R), rng.randrange(R))[count % 6]
     if count == 8:
         polys[3] = poly_with_root(rng, len(polys[3]), z)
-    digests = np.stack([commit(env, p) for p in polys])
-    claimed = [pl.poly_eval(p, z) for p in polys]
-    kg = pl.kzg_derive_gamma(z, [pl.g1_from_np(d) for d in digests], claimed)
-    folded, fe, acc = [0] * max(lens), 0, 1
-    for p, v in zip(polys, claimed):
-        for j, c in enumerate(p):
-            folded[j] = (folded[j] + c * acc) % R
-        fe = (fe + v * acc) % R
-        acc = acc * kg % R
-    want_h = commit(env, pl.divide_by_x_minus_a(folded, fe, z))
-    for t, srs in enumerate(env["srs"]):
-        arrs = [M(p) for p in polys]
-        on_device = (t + count) % 2 == 1
-        bufs = [_lib.DeviceBuffer.from_numpy(a) for a in arrs] if on_device else None
-        h, v = srs.batch_open_single_point(bufs if on_device else arrs, digests, M([z])[0], lens if on_device else None)
-        assert from_mont_limbs(v) == claimed
-        assert h.tobytes() == want_h.tobytes()
-        for b in bufs or []:
-            b.free()
+    check_batch(env, polys, z, count)
+
+
+@pytest.mark.parametrize("root_of", [None, 3])
+def test_batch_open_single_point_at_lane_and_workgroup_boundaries(env, root_of):
+    """the evaluation scan over rows that end at a lane's last coefficient and at a workgroup's (K = 8: 2048 is one workgroup exactly), then the division of their
+    fold; the point a root of the 2048-coefficient row, or random.  The first m rows alone make the divided fold end at each of the boundaries in turn."""
+    rng = random.Random(300 + (root_of or 0))
+    z = rng.randrange(R)
+    polys = [poly_with_root(rng, n, z) if k == root_of else rand_poly(rng, n) for k, n in enumerate(BOUNDARY)]
+    if root_of is not None:
+        assert BOUNDARY[root_of] == 2048 and pl.poly_eval(polys[root_of], z) == 0
+        check_batch(env, polys, z, 1)
+        return
+    for m in range(1, len(polys) + 1):
+        check_batch(env, polys[:m], z, m)
 
 
 def test_constant_polynomials_and_length_errors(env):
