@@ -991,6 +991,36 @@ typedef struct {
 } zk_msm_tail_result;
 int zk_bn254_msm_tail_inspect(const zk_msm_tail_request *req, zk_msm_tail_result *res);
 
+/* The Horner suffix scan under every PLONK proof and every KZG opening (S_i = f_i + a S_(i+1): S_0 = f(a), q_i = S_(i+1)), for inspection / tests: up to
+ * ZK_HSCAN_ROWS_MAX HOST rows -- coefficients, length, point -- are uploaded and the production launcher of the argument-point kernels is called once, with the
+ * points prepared by the production preparation (a -> a, a^K, a^(256 K)) and a trace attached: after the first launch the stream is synchronised and the
+ * workgroup totals copied, since the second launch overwrites them in place.  No kernel and no launch differs from a prover's; the profile names are the single
+ * PLONK prover's (plonk_horner_local, plonk_horner_blocks, plonk_divide_apply).  Nothing stays behind: the slot is released on every path.
+ *   request   rows in [1, ZK_HSCAN_ROWS_MAX]; K >= 1 coefficients per lane (the caller's, NOT the planner's: any K runs); nb workgroups of 256 lanes per row,
+ *             0 = what the longest row needs at this K (((len + K - 1) / K + 255) / 256), a larger value is taken as it is, a smaller one is an error; pad: guard
+ *             elements in front of and behind every row.  f[r]: pad + len[r] + pad Montgomery elements, the coefficients in the middle; equal f pointers stay ONE
+ *             device array.  q[r]: where row r's quotient goes, a buffer of the same shape -- or f[r] itself: division in place (not with a shared f).  Both are
+ *             uploaded whole, guards included, and copied back whole after the run, so the caller sees what was written where.  eval_only: two launches, no lane
+ *             carries kept, no quotient (q[r] may be NULL; where given it comes back as it went in).  a[r]: the point (Montgomery).
+ *   result    nb as used; the arrays, where the pointer is not NULL, are uploaded from the caller's memory before the run (the caller's poison shows what no
+ *             kernel wrote) and copied back after it: tcarry [rows * nb * 256] the lane carries after pass 1 ((row nb + block) 256 + lane; untouched with
+ *             eval_only), btot_local [rows * nb] the workgroup totals after pass 1 (the trace), btot [rows * nb] after pass 2, total [rows] = f_r(a_r).
+ * Errors, decided before a device is looked for: ZK_ERR_ARG for a null pointer, rows == 0 or above ZK_HSCAN_ROWS_MAX, K == 0, a length of 0, nb below what the
+ * longest row needs, rows * nb above 65,536, a missing q[r] without eval_only, in-place division of a shared f, two rows with one q. */
+#define ZK_HSCAN_ROWS_MAX 8
+typedef struct {
+    uint32_t rows, K, nb, pad;
+    int eval_only, reserved;
+    zk_fr *f[ZK_HSCAN_ROWS_MAX], *q[ZK_HSCAN_ROWS_MAX];
+    size_t len[ZK_HSCAN_ROWS_MAX];
+    zk_fr a[ZK_HSCAN_ROWS_MAX];
+} zk_hscan_request;
+typedef struct {
+    uint32_t nb, reserved;
+    zk_fr *tcarry, *btot_local, *btot, *total;
+} zk_hscan_result;
+int zk_bn254_hscan_inspect(const zk_hscan_request *req, zk_hscan_result *res);
+
 /* ---- felt-vector wire codec (the data format in front of the hot path) -------------------------------------------
  * The reference hands witness values to the Go side as hex( u32 BE count || count x 32 B BE canonical felts )
  * [REF src/gnark_backend_wrapper/serialize.rs:33-47,71-106; gnark_backend_ffi/internal/backend/helpers.go:24-33

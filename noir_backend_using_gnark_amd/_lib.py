@@ -68,6 +68,19 @@ class MsmTailResult(C.Structure):
                [(k, C.c_void_p) for k in MSM_TAIL_ARRAYS]
 
 
+HSCAN_ROWS_MAX = 8
+
+
+class HscanRequest(C.Structure):
+    _fields_ = [("rows", C.c_uint32), ("K", C.c_uint32), ("nb", C.c_uint32), ("pad", C.c_uint32), ("eval_only", C.c_int), ("reserved", C.c_int),
+                ("f", C.c_void_p * HSCAN_ROWS_MAX), ("q", C.c_void_p * HSCAN_ROWS_MAX), ("len", C.c_size_t * HSCAN_ROWS_MAX),
+                ("a", (C.c_uint64 * 4) * HSCAN_ROWS_MAX)]
+
+
+class HscanResult(C.Structure):
+    _fields_ = [("nb", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_void_p) for k in ("tcarry", "btot_local", "btot", "total")]
+
+
 class Groth16PK(C.Structure):
     _fields_ = [("log_domain", C.c_uint32), ("n_wires", C.c_size_t), ("n_public", C.c_size_t),
                 ("g1_alpha", C.c_void_p), ("g1_beta", C.c_void_p), ("g1_delta", C.c_void_p),
@@ -138,6 +151,7 @@ SYMBOLS = [
     "zk_bn254_felts_public_hex_rows_dev", "zk_plonk_verify_batch_with_vk", "zk_groth16_verify_batch_with_vk",
     "zk_bn254_kzg_open", "zk_bn254_kzg_batch_open_single_point", "zk_bn254_kzg_verify", "zk_bn254_kzg_fold_proof", "zk_bn254_kzg_batch_verify_single_point", "zk_bn254_kzg_verify_batch",
     "zk_bn254_plonk_verify_batch_keys", "zk_bn254_plonk_verify_batch_keys_dev",
+    "zk_bn254_hscan_inspect",
 ]
 
 # ctypes signatures of the row entries of the export path (the other entries are called with explicit ctypes values at every call site)

@@ -10,6 +10,8 @@
 #pragma once
 #include <string.h>
 
+#include <vector>
+
 #include "ctx.hpp"
 #include "ff.hpp"
 #include "host_ff.hpp"
@@ -144,7 +146,13 @@ struct HscanNames {
 // The passes over `rows` <= HSCAN_BATCH_MAX rows of R (the entries from `rows` on are not read): lane carries to tcarry[(row nb + block) 256 + lane],
 // workgroup totals to btot[row nb + block], f_r(a_r) to total[r]; then q_i = S_(i+1) for i < len (q[len - 1] = 0).  tcarry == nullptr: evaluation only, two
 // launches and no lane carries kept.
-int hscan_rows_passes(Slot* s, hipStream_t st, const HscanNames& names, const HscanRows& R, unsigned rows, uint32_t K, uint32_t nb, Fr* tcarry, Fr* btot, Fr* total);
+// With a trace (inspection, tests: zk_bn254_hscan_inspect) the stream is synchronised after pass 1 and the rows * nb workgroup totals, which pass 2 overwrites in
+// place, are copied to the host; the launches are the same.  Without one nothing is added but the test of the pointer.
+struct HscanTrace {
+    std::vector<Fr> btot_local;
+};
+int hscan_rows_passes(Slot* s, hipStream_t st, const HscanNames& names, const HscanRows& R, unsigned rows, uint32_t K, uint32_t nb, Fr* tcarry, Fr* btot, Fr* total,
+                      HscanTrace* trace = nullptr);
 
 // scratch carved from the slot arena for the scans over `len` elements
 struct ScanBufs {

@@ -6,6 +6,7 @@
     kzg.BatchOpenSinglePoint        plonk.Prove's batched opening of seven polynomials at zeta               -> SRS.batch_open_single_point
     kzg.Verify / FoldProof / BatchVerifySinglePoint   the end of plonk.Verify (host, no device)              -> verify / fold_proof / batch_verify_single_point
     kzg.BatchVerifyMultiPoints      many openings in one check, a verdict each (device)                      -> batch_verify_multi_points
+    (tests)                         the Horner scan under Open and plonk.Prove, every stage copied back       -> hscan_inspect
 The G1 side lives in HBM as a registered base array with its window tables; decoding a serialised SRS decompresses the points on the
 device (one square root each) instead of on the host cores, and happens once instead of on every prove / verify call."""
 from __future__ import annotations
@@ -152,6 +153,42 @@ def batch_verify_multi_points(digests, hs, claimed, points, g2) -> np.ndarray:
     acc, cnt = np.zeros(max(n, 1), np.uint8), C.c_size_t(0)
     check(lib().zk_bn254_kzg_verify_batch(vp(d), vp(o), vp(z), C.c_size_t(n), vp(np.ascontiguousarray(g2, dtype=np.uint64)), vp(acc), C.byref(cnt)))
     return acc[:n]
+
+
+def hscan_inspect(rows, K: int, nb: int = 0, mode: str = "divide", pad: int = 4, poison=None) -> dict:
+    """The Horner suffix scan under the openings and the PLONK prover, alone (zk_bn254_hscan_inspect; for tests): the production launcher over up to eight host
+    rows with the caller's K (and nb, 0 = what the longest row needs), every stage copied back.
+    rows: (f, a) pairs -- f (len, 4) Montgomery coefficients, a (4,) the point; the SAME array object twice is one device array.  mode: "divide" (the quotient
+    into a buffer of its own), "in_place" (over f) or "eval" (two launches, no quotient).  Every row gets `pad` guard elements either side and every output
+    array starts as `poison` (4 limbs), so that what no kernel wrote shows.
+    Returns nb, tcarry (rows, nb, 256, 4), btot_local / btot (rows, nb, 4): the workgroup totals after pass 1 / pass 2, total (rows, 4), and per row f and q as
+    they came back, guards included ((pad + len + pad, 4) each; in place q is f)."""
+    if mode not in ("divide", "in_place", "eval"):
+        raise ValueError("mode: divide, in_place or eval")
+    poison = np.full(4, 0xDEADBEEFCAFEF00D, np.uint64) if poison is None else np.asarray(poison, np.uint64).reshape(4)
+    req, res = _lib.HscanRequest(), _lib.HscanResult()
+    req.rows, req.K, req.nb, req.pad, req.eval_only = len(rows), K, nb, pad, int(mode == "eval")
+    fs, qs, padded = [], [], {}
+    for k, (f, a) in enumerate(rows[:_lib.HSCAN_ROWS_MAX]):
+        c = np.ascontiguousarray(f, dtype=np.uint64).reshape(-1, 4)
+        if id(f) not in padded:
+            padded[id(f)] = np.concatenate([np.tile(poison, (pad, 1)), c, np.tile(poison, (pad, 1))])
+        fs.append(padded[id(f)])
+        qs.append(fs[k] if mode == "in_place" else np.tile(poison, (c.shape[0] + 2 * pad, 1)))
+        req.f[k], req.q[k], req.len[k] = fs[k].ctypes.data, qs[k].ctypes.data, c.shape[0]
+        req.a[k][:] = [int(x) for x in np.asarray(a, np.uint64).reshape(4)]
+    # the geometry the entry will use (csrc/scan.hpp scan_blocks); arguments it refuses get arrays of one workgroup, which it never touches
+    longest = max([int(n) for n in req.len[:len(fs)]] + [1])
+    n, used = len(rows), max(nb, ((longest + K - 1) // K + 255) // 256) if K >= 1 else 1
+    out = dict(nb=used, tcarry=np.tile(poison, (n, used, 256, 1)), btot_local=np.tile(poison, (n, used, 1)), btot=np.tile(poison, (n, used, 1)),
+               total=np.tile(poison, (n, 1)))
+    for key in ("tcarry", "btot_local", "btot", "total"):
+        setattr(res, key, out[key].ctypes.data)
+    check(lib().zk_bn254_hscan_inspect(C.byref(req), C.byref(res)))
+    if int(res.nb) != used:
+        raise RuntimeError("scan inspection ran %d workgroups a row, %d were expected" % (res.nb, used))
+    out["f"], out["q"] = fs, qs
+    return out
 
 
 def new_srs(size: int, alpha_mont, table_window_bits: int = 0) -> SRS:
