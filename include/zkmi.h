@@ -1021,6 +1021,31 @@ typedef struct {
 } zk_hscan_result;
 int zk_bn254_hscan_inspect(const zk_hscan_request *req, zk_hscan_result *res);
 
+/* The Lagrange-form transform of a base array (zk_bn254_bases_lagrange: the inverse radix-2 transform taken in the exponent), for inspection / tests: n_points
+ * HOST G1 points are uploaded and the production builder is called once with a trace attached: after the scale-in launch, after every stage launch and after the
+ * finish the stream is synchronised and the array copied, since every stage overwrites it in place.  No kernel and no launch differs from those of
+ * zk_bn254_bases_lagrange; the profile names are its own (lagrange_scale_in, lagrange_dif_stage, lagrange_finish).  Nothing stays behind: the uploaded points and
+ * the base array that the builder registers are freed on every path.
+ *   request   points: n_points >= 2^log_n + 2 affine points (gnark's Montgomery image, (0, 0) = infinity); log_n <= 27.
+ *   result    n = 2^log_n.  stage_points [(log_n + 1) * n * 8 words], stage_inf [(log_n + 1) * n]: array 0 is the work array after the scale-in ((1 / n) P_j),
+ *             array k the same array after the k-th stage (butterflies i, i + m with m = n / 2^k), in the device's order -- the last one is the transform in
+ *             bit-reversed order.  The device keeps these entries projective (XYZZ); they come back NORMALISED on the host: the affine image of the group element,
+ *             whichever representative the kernels left, and stage_inf[i] = 1 where the entry is the point at infinity (its image is then (0, 0)) -- a flag of
+ *             its own, read from the projective entry, so that an image of zeros under a flag of 0 is a wrong point and not an infinity.
+ *             final_points [(n + 2) * 8 words], final_inf [n + 2]: the n + 2 affine points as the finish wrote them (the registered bases), final_inf[i] = 1
+ *             where the device wrote (0, 0).
+ * Errors, decided before a device is looked for: ZK_ERR_ARG for a null pointer, log_n above 27 and fewer than 2^log_n + 2 points. */
+typedef struct {
+    const zk_g1_affine *points;
+    size_t n_points;
+    uint32_t log_n, reserved;
+} zk_lagrange_request;
+typedef struct {
+    uint64_t *stage_points, *final_points;
+    uint8_t *stage_inf, *final_inf;
+} zk_lagrange_result;
+int zk_bn254_lagrange_inspect(const zk_lagrange_request *req, zk_lagrange_result *res);
+
 /* ---- felt-vector wire codec (the data format in front of the hot path) -------------------------------------------
  * The reference hands witness values to the Go side as hex( u32 BE count || count x 32 B BE canonical felts )
  * [REF src/gnark_backend_wrapper/serialize.rs:33-47,71-106; gnark_backend_ffi/internal/backend/helpers.go:24-33

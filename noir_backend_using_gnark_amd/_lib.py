@@ -81,6 +81,14 @@ class HscanResult(C.Structure):
     _fields_ = [("nb", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_void_p) for k in ("tcarry", "btot_local", "btot", "total")]
 
 
+class LagrangeRequest(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("n_points", C.c_size_t), ("log_n", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LagrangeResult(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("stage_points", "final_points", "stage_inf", "final_inf")]
+
+
 class Groth16PK(C.Structure):
     _fields_ = [("log_domain", C.c_uint32), ("n_wires", C.c_size_t), ("n_public", C.c_size_t),
                 ("g1_alpha", C.c_void_p), ("g1_beta", C.c_void_p), ("g1_delta", C.c_void_p),
@@ -151,7 +159,7 @@ SYMBOLS = [
     "zk_bn254_felts_public_hex_rows_dev", "zk_plonk_verify_batch_with_vk", "zk_groth16_verify_batch_with_vk",
     "zk_bn254_kzg_open", "zk_bn254_kzg_batch_open_single_point", "zk_bn254_kzg_verify", "zk_bn254_kzg_fold_proof", "zk_bn254_kzg_batch_verify_single_point", "zk_bn254_kzg_verify_batch",
     "zk_bn254_plonk_verify_batch_keys", "zk_bn254_plonk_verify_batch_keys_dev",
-    "zk_bn254_hscan_inspect",
+    "zk_bn254_hscan_inspect", "zk_bn254_lagrange_inspect",
 ]
 
 # ctypes signatures of the row entries of the export path (the other entries are called with explicit ctypes values at every call site)

@@ -373,6 +373,24 @@ class ResidentBases:
         check(lib().zk_bn254_bases_lagrange(self.handle, C.c_uint32(log_n), C.byref(rb.handle)))
         return rb
 
+    @staticmethod
+    def lagrange_inspect(points, log_n: int) -> dict:
+        """The transform under lagrange(), alone and stage by stage (zk_bn254_lagrange_inspect; for tests): host G1 points (at least 2^log_n + 2, gnark's images)
+        through the production builder with a trace.  Returns stages (log_n + 1, n, 8): the work array after the scale-in and after every stage, in the device's
+        order, every entry normalised to its affine image; stage_inf (log_n + 1, n): 1 where the entry is the point at infinity (a flag of its own: the image is
+        then zeros, and zeros under a flag of 0 are a wrong point); final (n + 2, 8) and final_inf (n + 2,): the points the finish wrote."""
+        points = _as_u64(points, 8)
+        n = 1 << log_n if 0 <= log_n < 32 else 1
+        fits = 0 <= log_n <= 27 and points.shape[0] >= n + 2   # arguments the entry refuses get arrays of one point, which it never touches
+        k, m = (log_n + 1, n) if fits else (1, 1)
+        out = dict(stages=np.zeros((k, m, 8), np.uint64), stage_inf=np.full((k, m), 0xEE, np.uint8), final=np.zeros((m + 2, 8), np.uint64),
+                   final_inf=np.full(m + 2, 0xEE, np.uint8))
+        req, res = _lib.LagrangeRequest(), _lib.LagrangeResult()
+        req.points, req.n_points, req.log_n = points.ctypes.data, points.shape[0], log_n & 0xFFFFFFFF
+        res.stage_points, res.stage_inf, res.final_points, res.final_inf = (out[key].ctypes.data for key in ("stages", "stage_inf", "final", "final_inf"))
+        check(lib().zk_bn254_lagrange_inspect(C.byref(req), C.byref(res)))
+        return out
+
     def build_table(self, table_window_bits: int = 0) -> None:
         """Window tables for bases registered without them (zk_bn254_bases_build_table); a no-op when they exist."""
         check(lib().zk_bn254_bases_build_table(self.handle, C.c_int(table_window_bits)))

@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void k_lag_finish(const XYZZ<Fp>* __restrict__
 }
 
 // d_srs: the SRS's G1 points (affine, at least 2^logn + 2 of them) -> *handle: n + 2 registered bases (with their window table when the planner gives one)
-int lagrange_srs_build(const void* d_srs, size_t srs_n, unsigned logn, uint64_t* handle) {
+int lagrange_srs_build(const void* d_srs, size_t srs_n, unsigned logn, uint64_t* handle, LagTrace* trace) {
     const size_t n = (size_t)1 << logn;
     if (logn > 27 || srs_n < n + 2) return set_err(ZK_ERR_ARG, "the Lagrange form over 2^%u points needs %zu SRS points, %zu given", logn, n + 2, srs_n);
     SlotGuard g;
@@ -146,12 +146,50 @@ int lagrange_srs_build(const void* d_srs, size_t srs_n, unsigned logn, uint64_t*
         for (int i = 0; i < 8; i++) s_in.l[i] = c[i];
     }
     const unsigned grid_n = (unsigned)((n + 255) / 256);
+    auto snap = [&]() -> int {  // inspection: the next launch overwrites the array in place
+        static_assert(sizeof(XYZZ<Fp>) == 128 && sizeof(Affine<Fp>) == 64, "LagTrace counts 16 and 8 words a point");
+        trace->work.emplace_back(n * 16);
+        ZK_HIP(hipStreamSynchronize(st));
+        ZK_HIP(hipMemcpy(trace->work.back().data(), work, n * sizeof(XYZZ<Fp>), hipMemcpyDeviceToHost));
+        return ZK_OK;
+    };
     ZK_LAUNCH(s, st, "lagrange_scale_in", k_lag_scale_in, dim3(grid_n), dim3(256), 0, (const Affine<Fp>*)d_srs, (uint32_t)n, s_in, work);
-    for (size_t m = n / 2; m >= 1; m >>= 1)
+    if (trace) ZK_TRY(snap());
+    for (size_t m = n / 2; m >= 1; m >>= 1) {
         ZK_LAUNCH(s, st, "lagrange_dif_stage", k_lag_dif_stage, dim3((unsigned)((n / 2 + 255) / 256)), dim3(256), 0, work, (uint32_t)n, (uint32_t)m, (const Fr*)d->tw_inv);
+        if (trace) ZK_TRY(snap());
+    }
     ZK_LAUNCH(s, st, "lagrange_finish", k_lag_finish, dim3((unsigned)((n + 2 + 255) / 256)), dim3(256), 0, (const XYZZ<Fp>*)work, (const Affine<Fp>*)d_srs, (uint32_t)n, logn, out);
     ZK_TRY(slot_sync(s, st));
+    if (trace) {
+        trace->out.resize((n + 2) * 8);
+        ZK_HIP(hipMemcpy(trace->out.data(), out, (n + 2) * sizeof(Affine<Fp>), hipMemcpyDeviceToHost));
+    }
     return zk_bn254_bases_register_dev(out, n + 2, 0, handle);
+}
+
+// raw XYZZ entries as the kernels leave them -> the affine image of each group element and a flag for the point at infinity, which is read from the projective
+// entry (zz == 0) and not from the image; one inversion for the whole array (the product of the denominators, unwound)
+static void lag_normalise(const uint64_t* raw, size_t count, uint64_t* pts, uint8_t* inf) {
+    std::vector<XYZZ<HFp>> p(count);
+    std::vector<HFp> pre(count);
+    memcpy(p.data(), raw, count * sizeof(XYZZ<HFp>));
+    HFp acc = HFp::one();
+    for (size_t i = 0; i < count; i++) {
+        inf[i] = p[i].is_inf() ? 1 : 0;
+        pre[i] = acc;
+        if (!inf[i] && !p[i].zzz.is_zero()) acc = acc * (p[i].zz * p[i].zzz);
+    }
+    acc = acc.inv();
+    for (size_t i = count; i-- > 0;) {
+        Affine<HFp> a = Affine<HFp>::inf();
+        if (!inf[i] && !p[i].zzz.is_zero()) {  // (zz != 0 over zzz == 0 is no point: zeros under a flag of 0)
+            const HFp zi = acc * pre[i];  // 1 / (zz zzz)
+            acc = acc * (p[i].zz * p[i].zzz);
+            a = Affine<HFp>{p[i].x * (zi * p[i].zzz), p[i].y * (zi * p[i].zz)};
+        }
+        memcpy(pts + i * 8, &a, sizeof a);
+    }
 }
 
 }  // namespace zkmi
@@ -170,4 +208,32 @@ extern "C" int zk_bn254_bases_lagrange(uint64_t bases, uint32_t log_n, uint64_t*
     ZK_TRY(bases_ptr(bases, &d, &n, &is_g2));
     if (is_g2) return set_err(ZK_ERR_ARG, "the Lagrange form is built for G1 base arrays");
     return lagrange_srs_build(d, n, log_n, out_handle);
+}
+
+// the transform alone, for inspection / tests (include/zkmi.h): host points up, lagrange_srs_build as zk_bn254_bases_lagrange calls it, with a trace; every stage
+// normalised on the host; both base arrays -- the uploaded points and the builder's result -- freed on every path
+extern "C" int zk_bn254_lagrange_inspect(const zk_lagrange_request* q, zk_lagrange_result* r) {
+    using namespace zkmi;
+    if (!q || !r || !q->points || !r->stage_points || !r->final_points || !r->stage_inf || !r->final_inf) return set_err(ZK_ERR_ARG, "null pointer");
+    const size_t n = (size_t)1 << (q->log_n & 31);
+    if (q->log_n > 27 || q->n_points < n + 2)
+        return set_err(ZK_ERR_ARG, "Lagrange inspection over 2^%u points needs log_n <= 27 and %zu points, %zu given", q->log_n, n + 2, q->n_points);
+    struct Drop { uint64_t h = 0; ~Drop() { if (h) (void)zk_bn254_bases_free(h); } } in, lag;
+    ZK_TRY(zk_bn254_bases_register_cfg(q->points, q->n_points, 0, 0, -1, &in.h));
+    ZK_ON_ENTRY_OF(in.h);
+    const void* d = nullptr;
+    size_t cnt = 0;
+    ZK_TRY(bases_ptr(in.h, &d, &cnt, nullptr));
+    LagTrace trace;
+    ZK_TRY(lagrange_srs_build(d, cnt, q->log_n, &lag.h, &trace));
+    if (trace.work.size() != (size_t)q->log_n + 1 || trace.out.size() != (n + 2) * 8)
+        return set_err(ZK_ERR_HIP, "Lagrange inspection: the trace holds %zu arrays, %u stages were run", trace.work.size(), q->log_n);
+    for (size_t k = 0; k < trace.work.size(); k++) lag_normalise(trace.work[k].data(), n, r->stage_points + k * n * 8, r->stage_inf + k * n);
+    memcpy(r->final_points, trace.out.data(), (n + 2) * 64);
+    for (size_t i = 0; i < n + 2; i++) {
+        uint64_t any = 0;
+        for (int w = 0; w < 8; w++) any |= trace.out[i * 8 + w];
+        r->final_inf[i] = any == 0;
+    }
+    return ZK_OK;
 }
