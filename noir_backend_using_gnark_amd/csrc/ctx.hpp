@@ -20,7 +20,7 @@
 // ---- environment variables ---------------------------------------------------------------------------------------------------------
 // The shipped library is loaded into the prover's process (nargo, through libgnark_backend.so): nothing a stray environment variable says may change a
 // result or crash it.  It reads exactly two variables, both validated and neither able to affect a result: ZKMI_TABLE_CAP_GB (groth16.hip: upper bound of
-// the window tables of a resident key) and ZKMI_SLOT_TIMEOUT_S (ctx.hip).  Every A/B switch of the measurements in DESIGN.md is a ZK_EXP(name, default):
+// the window tables of a resident key) and ZKMI_SLOT_TIMEOUT_S (ctx.hip).  Every A/B switch in the code (DESIGN.md 8 lists them) is a ZK_EXP(name, default):
 // the default, as a constant, unless the library is built with -DZKMI_EXPERIMENTS (`make EXPERIMENTS=1` -> libzkmi_exp.so, never shipped), where the
 // variable is read.  tests/test_cabi_cpu.py asserts that libzkmi.so contains no other ZKMI_* string.
 #ifdef ZKMI_EXPERIMENTS
@@ -98,7 +98,6 @@ struct Slot {
     hipStream_t hi();                 // creates it on first use
     hipStream_t hi_locked();          // the same under the owner's mutex (acquire_slots)
     void sync_hi() { if (stream_hi_) (void)hipStreamSynchronize(stream_hi_); }
-    hipStream_t stream_prep = nullptr, stream_acc = nullptr;  // experiment (ZKMI_CU_SPLIT=k): CU-masked pair -- k CUs for scalar preparation, the rest for accumulates
     char* arena = nullptr;
     size_t arena_cap = 0, arena_off = 0;
     void* pinned = nullptr;
@@ -170,7 +169,6 @@ bool bg_cancelled();
 int acquire_slot(Slot** out);       // blocks (spins) until a slot is free
 int acquire_slots(int k, Slot** out); // k slots at once (all or nothing: no partial holds, hence no deadlock)
 void release_slot(Slot* s);
-int masked_streams(Slot* s);         // creates stream_prep / stream_acc on first use; ZK_OK with both left null when ZKMI_CU_SPLIT is unset
 int slot_sync(Slot* s, hipStream_t st);  // synchronize + fold pending profile events
 int h2d_big(void* dst, const void* src, size_t bytes, hipStream_t st);  // pageable host memory -> HBM through a ring of pinned buffers (ctx.hip); src is free on return
 

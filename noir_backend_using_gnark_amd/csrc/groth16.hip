@@ -190,13 +190,6 @@ int zk_bn254_groth16_pk_load(const zk_groth16_pk* pk, uint64_t* handle) {
     if (_entry.rc != ZK_OK) return _entry.rc;
     if (pk->log_domain > 28 || pk->n_public > pk->n_wires) return set_err(ZK_ERR_ARG, "bad proving-key geometry");
     if (pk->n_wires >= ((size_t)1 << 31)) return set_err(ZK_ERR_ARG, "n_wires = %zu does not fit 31 bits", pk->n_wires);
-    {   // experiment: the five slots of a proof session (and their high-priority streams) exist from the key's load on, not from the first proof on
-        static const bool warm = ZK_EXP("ZKMI_PK_LOAD_WARMS_SESSION", 0) != 0;
-        if (warm) {
-            SlotsGuard<5> g;
-            ZK_TRY(acquire_slots(5, g.s));
-        }
-    }
     if (!pk->g1_alpha || !pk->g1_beta || !pk->g1_delta || !pk->g2_beta || !pk->g2_delta) return set_err(ZK_ERR_ARG, "null pk element");
     if ((pk->infinity_a == nullptr) != (pk->infinity_b == nullptr)) return set_err(ZK_ERR_ARG, "InfinityA and InfinityB must be given together");
     if (!pk->infinity_a && (pk->nb_infinity_a || pk->nb_infinity_b)) return set_err(ZK_ERR_ARG, "NbInfinityA/B without the bitmaps");
@@ -483,7 +476,6 @@ static bool k_shares_w(const Msm5Inputs& in, size_t* j) {
 struct Msm5State {
     MsmJob jobs[5];
     MsmPrep prep_w, prep_h;
-    hipStream_t chain = nullptr;  // stream on which the accumulate kernels are serialised
 };
 
 // Stream plan.  Every kernel of a proof is ALU-bound except the sorts, so nothing is gained by letting accumulate kernels
@@ -497,15 +489,13 @@ struct Msm5State {
 // that the GPU is busy while the host is still enqueuing computeH and prepare(h).
 // scalar side of the four MSMs over the wire values (digits, sort, task plan) on slot 4's stream
 static int msm5_prepare_w(Slot* sl[5], const Msm5Inputs& in, hipEvent_t ev_w, Msm5State* S) {
-    static const bool low = ZK_EXP("ZKMI_PREPW_LOW", 0) == 1;  // experiment: normal priority under computeH
-    hipStream_t st4 = low ? sl[4]->stream : sl[4]->hi();
+    hipStream_t st4 = sl[4]->hi();
     if (ev_w) ZK_HIP(hipStreamWaitEvent(st4, ev_w, 0));
     // The wire values of a real circuit are mostly 0 / 1 / small (booleans, bytes, range-check limbs): their zero digits never enter the sort (msm.hip
     // k_msm_digits_compact; the pair count stays on the device): 2^20 witness-like wires 6.5 -> 6.1 ms.  A vector without zero digits pays nothing for it
-    // (one pass over the scalars either way).  ZKMI_W_DROP_ZERO_DIGITS=0 (experiments build): the ordinary recoding.
-    static const bool drop = ZK_EXP("ZKMI_W_DROP_ZERO_DIGITS", 1) != 0;
-    if (in.tab_w) return msm_prepare_scalars_table(sl[4], st4, in.d_w, in.nw, &kMontCfg, *in.tab_w, &S->prep_w, drop);
-    return msm_prepare_scalars(sl[4], st4, in.d_w, in.nw, &kMontCfg, &S->prep_w, drop);
+    // (one pass over the scalars either way).
+    if (in.tab_w) return msm_prepare_scalars_table(sl[4], st4, in.d_w, in.nw, &kMontCfg, *in.tab_w, &S->prep_w, true);
+    return msm_prepare_scalars(sl[4], st4, in.d_w, in.nw, &kMontCfg, &S->prep_w, true);
 }
 // `between` (optional): called once the G2.B accumulate is enqueued, with its completion event; it may enqueue work that must own the machine
 // next (computeH when the inputs came from the host) and return the event the A accumulate has to wait for instead.
@@ -519,45 +509,17 @@ static int msm5_accumulate_w(Slot* sl[5], const Msm5Inputs& in, hipEvent_t ev_w,
     hipStream_t st4 = sl[4]->hi();
     size_t j = 0;
     const bool share_k = k_shares_w(in, &j);
-    // accumulate kernels chained through events, each on its MSM's own stream (measured alternatives: one shared "chain" stream
-    // for all accumulate kernels removes the ~0.15 ms event gaps but delays prepare(h) -- rocPRIM's onesweep sort spins on
-    // look-back tiles that cannot get a wave slot under an accumulate kernel -- and ends up slower)
-    // ZKMI_CHAIN=1 (experiment switch): all accumulate kernels back to back on ONE stream, tails on the jobs' own streams
-    static const bool one_chain = ZK_EXP("ZKMI_CHAIN", 0) == 1;
-    if (one_chain && (in.tab_w || share_k)) {
-        hipStream_t chain = sl[4]->stream;
-        S->jobs[4].gate_acc = gate_first_acc;
-        S->jobs[4].chain = chain;
-        ZK_TRY(msm_g2_accumulate(sl[4], st4, S->prep_w, in.tab_w ? in.t_b2 : in.d_b2, 0, &S->jobs[4]));
-        S->jobs[1].chain = chain;
-        ZK_TRY(msm_g1_accumulate(sl[1], sl[1]->stream, S->prep_w, in.tab_w ? in.t_a : in.d_a, 0, &S->jobs[1]));
-        S->jobs[2].chain = chain;
-        ZK_TRY(msm_g1_accumulate(sl[2], sl[2]->stream, S->prep_w, in.tab_w ? in.t_b : in.d_b, 0, &S->jobs[2]));
-        S->jobs[3].chain = chain;
-        S->jobs[3].want_done = true;
-        if (in.tab_w) ZK_TRY(msm_g1_accumulate(sl[3], sl[3]->stream, S->prep_w, in.t_k, 0, &S->jobs[3]));
-        else ZK_TRY(msm_g1_accumulate(sl[3], sl[3]->stream, S->prep_w, (const char*)in.d_k - j * 64, (uint32_t)j, &S->jobs[3]));
-        return ZK_OK;
-    }
+    // accumulate kernels chained through events, each on its MSM's own stream (measured: one shared stream for all accumulate kernels removes the
+    // ~0.15 ms event gaps but delays prepare(h) -- rocPRIM's onesweep sort spins on look-back tiles that cannot get a wave slot under an accumulate
+    // kernel -- and ends up slower)
     S->jobs[4].gate_acc = gate_first_acc;
     S->jobs[4].want_done = true;
     ZK_TRY(msm_g2_accumulate(sl[4], st4, S->prep_w, in.tab_w ? in.t_b2 : in.d_b2, 0, &S->jobs[4]));
     hipEvent_t prev = S->jobs[4].acc_done;
     if (between) ZK_TRY((*between)(S->jobs[4].acc_done, &prev));
-    // ZKMI_BATCH_ACC=1 (experiment switch): A, B1, K -- which read the same sorted digits -- in ONE accumulate launch (grid.y = 3).
-    // Measured 0.25 ms SLOWER per proof than the chained launches (11.2 vs 10.95 ms): the kernel itself runs at 0.70 of the madd
-    // peak instead of 0.61, but the three reduction tails then all start late and pile up under Z instead of hiding one by one.
-    static const bool batch_acc = ZK_EXP("ZKMI_BATCH_ACC", 0) == 1;
-    if (batch_acc && (in.tab_w || share_k)) {
-        Slot* bs[3] = {sl[1], sl[2], sl[3]};
-        hipStream_t bst[3] = {sl[1]->stream, sl[2]->stream, sl[3]->stream};
-        const void* bp[3] = {in.tab_w ? in.t_a : in.d_a, in.tab_w ? in.t_b : in.d_b, in.tab_w ? in.t_k : (const void*)((const char*)in.d_k - j * 64)};
-        uint32_t bskip[3] = {0, 0, in.tab_w ? 0u : (uint32_t)j};
-        MsmJob* bj[3] = {&S->jobs[1], &S->jobs[2], &S->jobs[3]};
-        S->jobs[1].gate_acc = prev;
-        S->jobs[3].want_done = true;
-        return msm_g1_accumulate_batch(3, bs, bst, S->prep_w, bp, bskip, bj);
-    }
+    // A, B1, K read the same sorted digits but keep a launch each.  Measured: ONE accumulate launch for the three (grid.y = 3) is 0.25 ms SLOWER per
+    // proof (11.2 vs 10.95 ms): the kernel itself runs at 0.70 of the madd peak instead of 0.61, but the three reduction tails then all start late
+    // and pile up under Z instead of hiding one by one.
     S->jobs[1].gate_acc = prev;
     S->jobs[1].want_done = true;
     ZK_TRY(msm_g1_accumulate(sl[1], sl[1]->stream, S->prep_w, in.tab_w ? in.t_a : in.d_a, 0, &S->jobs[1]));
@@ -579,36 +541,16 @@ static int msm5_accumulate_w(Slot* sl[5], const Msm5Inputs& in, hipEvent_t ev_w,
     return ZK_OK;
 }
 // Z side, on st0 (after whatever produced h on that stream); its accumulate goes last in the chain
-static int msm5_prepare_h(Slot* sl[5], hipStream_t st0, const Msm5Inputs& in, Msm5State* S) {
-    if (in.tab_h) return msm_prepare_scalars_table(sl[0], st0, in.d_h, in.nz, &kMontCfg, *in.tab_h, &S->prep_h);
-    return msm_prepare_scalars(sl[0], st0, in.d_h, in.nz, &kMontCfg, &S->prep_h);
-}
-static int msm5_launch_h(Slot* sl[5], hipStream_t st0, const Msm5Inputs& in, Msm5State* S, bool prepared = false) {
-    // ZKMI_PREPH_LOW=1 (experiment switch): prepare(h) on slot 0's NORMAL-priority stream (it has ~7 ms of slack until Z needs it)
-    static const bool preph_low = ZK_EXP("ZKMI_PREPH_LOW", 0) == 1;
-    if (!prepared && preph_low && sl[0]->stream != st0) {
-        hipEvent_t ev;
-        ZK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        ZK_HIP(hipEventRecord(ev, st0));
-        ZK_HIP(hipStreamWaitEvent(sl[0]->stream, ev, 0));
-        (void)hipEventDestroy(ev);
-        ZK_TRY(msm5_prepare_h(sl, sl[0]->stream, in, S));
-        prepared = true;
-    }
-    if (!prepared) ZK_TRY(msm5_prepare_h(sl, st0, in, S));
-    // Z's accumulate goes last on the chain stream (which then waits for prepare(h) through the event inside msm_accumulate)
-    S->jobs[0].chain = S->chain;
-    if (!S->chain) {
-        hipEvent_t prev = nullptr;
-        for (int i : {4, 1, 2, 3})
-            if (S->jobs[i].acc_done) prev = S->jobs[i].acc_done;
-        S->jobs[0].gate_acc = prev;
-    }
-    // ZKMI_QUAD_TAIL=1 (experiment switch): wave levels of Z's reduction tail -- the only tail nothing can hide -- with four lanes per
-    // point.  Measured: those levels shrink 0.39 -> 0.27 ms under the profiler but the proof does not (10.6-10.8 ms either way), and
-    // level 1, which already fills every SIMD, gets 3x slower in that form; off by default.
-    static const bool quad_tail = ZK_EXP("ZKMI_QUAD_TAIL", 0) == 1;
-    S->jobs[0].quad_tail = quad_tail;
+static int msm5_launch_h(Slot* sl[5], hipStream_t st0, const Msm5Inputs& in, Msm5State* S) {
+    if (in.tab_h) ZK_TRY(msm_prepare_scalars_table(sl[0], st0, in.d_h, in.nz, &kMontCfg, *in.tab_h, &S->prep_h));
+    else ZK_TRY(msm_prepare_scalars(sl[0], st0, in.d_h, in.nz, &kMontCfg, &S->prep_h));
+    hipEvent_t prev = nullptr;
+    for (int i : {4, 1, 2, 3})
+        if (S->jobs[i].acc_done) prev = S->jobs[i].acc_done;
+    S->jobs[0].gate_acc = prev;
+    // Z's reduction tail -- the only tail nothing can hide -- keeps one lane per point.  Measured: with four lanes per point (MsmJob::quad_tail) its wave
+    // levels shrink 0.39 -> 0.27 ms under the profiler but the proof does not (10.6-10.8 ms either way), and level 1, which already fills every SIMD,
+    // gets 3x slower in that form.
     ZK_TRY(msm_g1_accumulate(sl[0], st0, S->prep_h, in.tab_h ? in.t_z : in.d_z, 0, &S->jobs[0]));
     return ZK_OK;
 }
@@ -949,21 +891,13 @@ int zk_bn254_groth16_prove(uint64_t pk_handle, const void* a, const void* b, con
     }
     ZK_TRY(msm5_reserve(g.s, in, 3 * N * 32 + nw * 32 + 4096));
     hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    // Order on the GPU:  [computeH  ||  upload + prepare(w)]  ->  G2.B acc -> A acc -> B1 acc -> K acc -> Z acc  (reduce tails and
-    // prepare(h) run underneath the accumulate kernels).  computeH goes FIRST and alone with the bandwidth-bound sort of w:
-    // measured, an NTT launched underneath an accumulate kernel is starved (1.3 ms -> 8 ms) because the long-running accumulate
-    // workgroups never free enough wave slots, and the Z chain then finishes late.
     hipStream_t st4 = g.s[4]->hi();
     int rc = ZK_OK;
     Fr* d_abc[3] = {nullptr, nullptr, nullptr};
     const void* src[3] = {a, b, c};
     // full-length inputs already in HBM are read in place by the first NTT pass (they stay untouched); otherwise copy / pad first
     const bool direct = on_device && n_constraints == N && N > 1;
-    // Host inputs (what a cgo caller has): 128 bytes per constraint cross PCIe inside the call.  Order: w first (32 B / wire), its scalar preparation
-    // and the G2.B accumulate -- none of which needs a, b, c -- run while a, b, c (96 B / constraint) are still uploading; computeH then takes the
-    // machine BETWEEN the G2.B and A accumulates (under an accumulate kernel it would be starved).  ZKMI_HOST_ORDER=0 restores computeH-first.
-    static const bool host_order_on = (ZK_EXP("ZKMI_HOST_ORDER", 1) != 0);
-    const bool host_order = !on_device && host_order_on && nw > 0 && N > 1;
+    const bool host_order = !on_device && nw > 0 && N > 1;
     Fr* d_w = (Fr*)s0->alloc(nw * 32 + 16);
     for (int i = 0; i < 3; i++) d_abc[i] = (Fr*)s0->alloc(N * 32);
     if (on_device) d_w = (Fr*)const_cast<void*>(w);  // wire values already in HBM are only read: no staging copy
@@ -977,25 +911,26 @@ int zk_bn254_groth16_prove(uint64_t pk_handle, const void* a, const void* b, con
     };
     // h = computeH(a, b, c), left in d_abc[0] (bit-reversed order, like upstream; pk.G1.Z is stored to match)
     const Fr* in_place_src[3] = {(const Fr*)a, (const Fr*)b, (const Fr*)c};
-    // ZKMI_H_STREAMS=1 (experiment switch): the transforms of b and c on the (idle) high-priority streams of slots 1 and 2, next to a's
-    static const bool h_streams = ZK_EXP("ZKMI_H_STREAMS", 0) == 1;
-    const hipStream_t side[2] = {g.s[1]->hi(), g.s[2]->hi()};
     hipEvent_t ev_h = nullptr;
     auto run_compute_h = [&]() -> int {
-        ZK_TRY(compute_h_inplace(s0, st, d_abc[0], d_abc[1], d_abc[2], P.log_domain, direct ? in_place_src : nullptr, h_streams ? side : nullptr));
+        ZK_TRY(compute_h_inplace(s0, st, d_abc[0], d_abc[1], d_abc[2], P.log_domain, direct ? in_place_src : nullptr));
         ZK_HIP(hipEventCreateWithFlags(&ev_h, hipEventDisableTiming));
         ZK_HIP(hipEventRecord(ev_h, st));
         return ZK_OK;
     };
     Msm5State S;
-    static const bool nogate = ZK_EXP("ZKMI_NOGATE", 0) == 1;  // experiment: G2.B accumulate does not wait for computeH
-    static const bool preph_first = ZK_EXP("ZKMI_PREPH_FIRST", 0) == 1;  // experiment: prepare(h) alone, before G2.B
-    static const bool preph_early = ZK_EXP("ZKMI_PREPH_EARLY", 0) == 1;  // experiment: prepare(h) ENQUEUED before the w-side accumulates (no extra gating)
+    in.d_w = d_w;
+    in.d_wk = d_w + P.n_public;
+    in.d_h = d_abc[0];
+    // Order on the GPU:  [computeH  ||  upload + prepare(w)]  ->  G2.B acc -> A acc -> B1 acc -> K acc -> Z acc  (reduce tails and
+    // prepare(h) run underneath the accumulate kernels).  computeH goes alone with the bandwidth-bound sort of w: measured, an NTT
+    // launched underneath an accumulate kernel is starved (1.3 ms -> 8 ms) because the long-running accumulate workgroups never free
+    // enough wave slots, and the Z chain then finishes late.
     if (host_order) {
+        // Host inputs (what a cgo caller has): 128 bytes per constraint cross PCIe inside the call.  w goes first (32 B / wire): its scalar preparation
+        // and the G2.B accumulate -- none of which needs a, b, c -- run while a, b, c (96 B / constraint) are still uploading; computeH then takes the
+        // machine BETWEEN the G2.B and A accumulates.
         if (hipMemcpyAsync(d_w, w, nw * 32, kind, st4) != hipSuccess) rc = set_err(ZK_ERR_HIP, "hipMemcpyAsync failed");
-        in.d_w = d_w;
-        in.d_wk = d_w + P.n_public;
-        in.d_h = d_abc[0];
         if (rc == ZK_OK) rc = msm5_prepare_w(g.s, in, nullptr, &S);
         if (rc == ZK_OK) rc = upload_abc();  // the host blocks here while the GPU sorts the digits of w
         const BetweenFn between = [&](hipEvent_t g2_done, hipEvent_t* gate_next) -> int {
@@ -1007,47 +942,12 @@ int zk_bn254_groth16_prove(uint64_t pk_handle, const void* a, const void* b, con
         if (rc == ZK_OK) rc = msm5_accumulate_w(g.s, in, nullptr, &S, nullptr, &between);
         if (rc == ZK_OK) rc = msm5_launch_h(g.s, st, in, &S);
     } else {
-        // Order on the GPU:  [computeH  ||  upload + prepare(w)]  ->  G2.B acc -> A acc -> B1 acc -> K acc -> Z acc  (reduce tails and
-        // prepare(h) run underneath the accumulate kernels).  computeH goes FIRST and alone with the bandwidth-bound sort of w:
-        // measured, an NTT launched underneath an accumulate kernel is starved (1.3 ms -> 8 ms) because the long-running accumulate
-        // workgroups never free enough wave slots, and the Z chain then finishes late.
-        // ZKMI_H_UNDER_G2=1 (experiment switch): prepare(w) ALONE first, then computeH started together with the G2.B accumulate (to be combined with
-        // ZKMI_ACC_WG_G2=1: that kernel at one wave per SIMD leaves half of the registers and the LDS to the transforms' workgroups)
-        static const bool h_under_g2 = ZK_EXP("ZKMI_H_UNDER_G2", 0) == 1;
-        if (h_under_g2) {
-            if (!on_device && nw && hipMemcpyAsync(d_w, w, nw * 32, kind, st4) != hipSuccess) rc = set_err(ZK_ERR_HIP, "hipMemcpyAsync failed");
-            in.d_w = d_w;
-            in.d_wk = d_w + P.n_public;
-            in.d_h = d_abc[0];
-            if (rc == ZK_OK) rc = msm5_prepare_w(g.s, in, nullptr, &S);
-            if (rc == ZK_OK) rc = upload_abc();
-            if (rc == ZK_OK && S.prep_w.ready && hipStreamWaitEvent(st, S.prep_w.ready, 0) != hipSuccess) rc = set_err(ZK_ERR_HIP, "hipStreamWaitEvent failed");
-            if (rc == ZK_OK) rc = run_compute_h();
-            if (rc == ZK_OK) rc = msm5_accumulate_w(g.s, in, nullptr, &S, nullptr);
-            if (rc == ZK_OK) rc = msm5_launch_h(g.s, st, in, &S);
-        } else {
+        // Everything else: computeH first, the G2.B accumulate gated on its end
         rc = upload_abc();
         if (rc == ZK_OK) rc = run_compute_h();
         if (!on_device && rc == ZK_OK && nw && hipMemcpyAsync(d_w, w, nw * 32, kind, st4) != hipSuccess) rc = set_err(ZK_ERR_HIP, "hipMemcpyAsync failed");
-        in.d_w = d_w;
-        in.d_wk = d_w + P.n_public;
-        in.d_h = d_abc[0];
-        if (preph_first) {
-            if (rc == ZK_OK) rc = msm5_prepare_h(g.s, st, in, &S);
-            if (rc == ZK_OK) rc = msm5_launch_w(g.s, in, nullptr, &S, S.prep_h.ready ? S.prep_h.ready : ev_h);
-            if (rc == ZK_OK) rc = msm5_launch_h(g.s, st, in, &S, true);
-        } else if (preph_early) {
-            // host enqueue order only: prepare(h) is enqueued (on computeH's stream, behind it) BEFORE the ~40 launches of the four w-side accumulates and their
-            // tails -- with witness-like wires those are short and the GPU reaches the end of computeH before the host has enqueued prepare(h) behind them
-            if (rc == ZK_OK) rc = msm5_prepare_w(g.s, in, nullptr, &S);
-            if (rc == ZK_OK) rc = msm5_prepare_h(g.s, st, in, &S);
-            if (rc == ZK_OK) rc = msm5_accumulate_w(g.s, in, nullptr, &S, nogate ? nullptr : ev_h);
-            if (rc == ZK_OK) rc = msm5_launch_h(g.s, st, in, &S, true);
-        } else {
-            if (rc == ZK_OK) rc = msm5_launch_w(g.s, in, nullptr, &S, nogate ? nullptr : ev_h);
-            if (rc == ZK_OK) rc = msm5_launch_h(g.s, st, in, &S);
-        }
-        }
+        if (rc == ZK_OK) rc = msm5_launch_w(g.s, in, nullptr, &S, ev_h);
+        if (rc == ZK_OK) rc = msm5_launch_h(g.s, st, in, &S);
     }
     if (ev_h) (void)hipEventDestroy(ev_h);
     uint64_t parts[96];

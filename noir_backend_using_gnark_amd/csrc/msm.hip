@@ -1270,11 +1270,10 @@ static int msm_accumulate_batch(int nb, Slot* const* sl, const hipStream_t* sts,
         batch.partial[b] = partial[b];
         batch.skip_below[b] = skip_below[b];
     }
-    // The throughput-bound accumulate kernel runs on `jobs[0]->chain` when given (the caller serialises the accumulate kernels of
-    // several MSMs back to back on one stream, no event round trips between them); everything after it -- the latency-bound
-    // reduction tail -- runs on each job's own stream, gated on an event.
+    // The throughput-bound accumulate kernel runs on the first job's stream; everything after it -- the latency-bound reduction tail -- on each
+    // job's own stream, gated on an event.
     MsmJob* j0 = jobs[0];
-    hipStream_t sa = j0->chain ? j0->chain : sts[0];
+    hipStream_t sa = sts[0];
     if (R.ready) ZK_HIP(hipStreamWaitEvent(sa, R.ready, 0));
     if (j0->gate_acc) ZK_HIP(hipStreamWaitEvent(sa, j0->gate_acc, 0));
     // Independent callers (the MultiExp calls upstream issues from concurrent goroutines) pass through a turnstile per device entry: their accumulate kernels
@@ -1341,7 +1340,7 @@ static int msm_accumulate_batch(int nb, Slot* const* sl, const hipStream_t* sts,
         T->next = (T->next + 1) % 16;
         turn_lock.unlock();
     }
-    bool want = j0->chain != nullptr || nb > 1;
+    bool want = nb > 1;
     for (int b = 0; b < nb; b++) want = want || jobs[b]->want_done;
     if (want) {
         hipEvent_t done;
@@ -1774,11 +1773,6 @@ void msm_prep_release(MsmPrep* R) {
 }
 int msm_g1_accumulate(Slot* s, hipStream_t st, const MsmPrep& R, const void* d_pts, uint32_t skip_below, MsmJob* job) {
     return msm_accumulate<Fp>(s, st, R, (const Affine<Fp>*)d_pts, skip_below, job);
-}
-int msm_g1_accumulate_batch(int nb, Slot* const* sl, const hipStream_t* sts, const MsmPrep& R, const void* const* d_pts, const uint32_t* skip_below,
-                            MsmJob* const* jobs) {
-    if (nb < 1 || nb > 3) return set_err(ZK_ERR_ARG, "accumulate batch of %d", nb);
-    return msm_accumulate_batch<Fp>(nb, sl, sts, R, d_pts, skip_below, jobs);
 }
 int msm_g2_accumulate(Slot* s, hipStream_t st, const MsmPrep& R, const void* d_pts, uint32_t skip_below, MsmJob* job) {
     return msm_accumulate<Fp2>(s, st, R, (const Affine<Fp2>*)d_pts, skip_below, job);

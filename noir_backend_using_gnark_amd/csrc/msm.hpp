@@ -93,10 +93,9 @@ struct MsmJob {
     hipEvent_t gate_acc = nullptr;
     bool want_done = false;
     hipEvent_t acc_done = nullptr;
-    hipStream_t chain = nullptr;  // run the accumulate kernel on this stream (reduction tail stays on the job's stream)
     bool turnstile = false;       // an independent caller: the accumulate kernel takes its turn behind those of other callers on this device entry
-    bool quad_tail = false;       // G1: reduction tail with four lanes per point (3x shorter serial chain, ~1.4x the ALU work): for the
-                                  // tail nothing else can hide -- the last MSM of a proof
+    bool quad_tail = false;       // G1: reduction tail with four lanes per point (3x shorter serial chain, ~1.4x the ALU work); no prover sets it
+                                  // (groth16.hip msm5_launch_h has the measurement), zk_bn254_msm_tail_inspect does
     // keep_final (set by the caller BEFORE launch; off: nothing changes): the last-level entries stay on the device -- W * n_final entries each, set w at
     // [w * n_final, (w + 1) * n_final), in the slot's arena -- instead of being copied to pinned memory; msm_g1_sets_affine_dev finishes such a job
     bool keep_final = false;
@@ -135,9 +134,6 @@ int msm_g1_finish_batch(const MsmJob& job, XYZZ<HFp> out[3]);
 void msm_prep_release(MsmPrep* R);
 int msm_g1_accumulate(Slot* s, hipStream_t st, const MsmPrep& R, const void* d_pts, uint32_t skip_below, MsmJob* job);
 int msm_g2_accumulate(Slot* s, hipStream_t st, const MsmPrep& R, const void* d_pts, uint32_t skip_below, MsmJob* job);
-// up to three G1 MSMs over the same prepared scalars in ONE accumulate launch (jobs[0]->gate_acc gates it; the last job's acc_done owns the event)
-int msm_g1_accumulate_batch(int nb, Slot* const* sl, const hipStream_t* sts, const MsmPrep& R, const void* const* d_pts, const uint32_t* skip_below,
-                            MsmJob* const* jobs);
 int msm_g1_finish(const MsmJob& job, XYZZ<HFp>* out);
 int msm_g2_finish(const MsmJob& job, XYZZ<HFp2>* out);
 // Device-pointer MSMs returning the un-normalised total (host XYZZ); they synchronise `st` before returning.

@@ -31,8 +31,7 @@ namespace zkmi {
 // TILE_LOG, K_STRIDED and plan_passes() below are re-stated in tests/ntt_shapes.py (plan_passes), from which tests/test_ntt_shapes_cpu.py checks that the swept
 // sizes run every pass shape: change them there too.
 static constexpr unsigned TILE_LOG = 11;        // 2048 elements = 64 KiB of LDS per workgroup
-static const unsigned K_STRIDED = (unsigned)std::min<long>(9, std::max<long>(2, ZK_EXP("ZKMI_NTT_KS", 9)));  // strided passes: k <= 9, rows of L >= 4 elements (128-byte runs); 2^20 = 11 + 9 bits = two passes
-static constexpr unsigned NTT_THREADS = 256;
+static constexpr unsigned K_STRIDED = 9;         // strided passes: k <= 9, rows of L >= 4 elements (128-byte runs); 2^20 = 11 + 9 bits = two passes
 
 struct PowBasis {
     Fr pw[28];  // base^(2^b)
@@ -92,117 +91,9 @@ __device__ __forceinline__ Fr gload_fr(const Fr* p) {
     return r;
 }
 
-// G consecutive stages of the pass on one butterfly group per lane-iteration.  Stage index s counts from the start of the pass;
-// DIF walks the tile bits downwards (q = k-1-s), DIT upwards (q = s).  ql = lowest tile bit of the group.
-template <int G, bool DIF>
-__device__ __forceinline__ void ntt_group(const PassArgs& A, uint4* lo, uint4* hi, size_t base, unsigned E, unsigned s0, bool first, bool last) {
-    constexpr unsigned NE = 1u << G;
-    const unsigned L = 1u << A.logL;
-    const unsigned ql = DIF ? (A.k - s0 - G) : s0;
-    for (unsigned u = threadIdx.x; u < (E >> G); u += NTT_THREADS) {
-        const unsigned l = u & (L - 1), r = u >> A.logL;
-        const unsigned mid0 = ((r >> ql) << (ql + G)) | (r & ((1u << ql) - 1));
-        Fr x[NE];
-#pragma unroll
-        for (unsigned e = 0; e < NE; e++) {
-            const unsigned t = ((mid0 | (e << ql)) << A.logL) + l;
-            x[e] = lds_load(lo, hi, t);
-            if (first && A.pre) x[e] = x[e] * gload_fr(A.pre + base + ((size_t)(mid0 | (e << ql)) << A.bit_lo) + l);
-        }
-#pragma unroll
-        for (int sl = 0; sl < G; sl++) {
-            const unsigned bitl = DIF ? (unsigned)(G - 1 - sl) : (unsigned)sl;  // bit inside the group (compile-time after unrolling)
-            const unsigned b = A.bit_lo + ql + bitl;                               // global index bit
-#pragma unroll
-            for (unsigned e0 = 0; e0 < NE; e0++) {
-                if (e0 & (1u << bitl)) continue;
-                const unsigned e1 = e0 | (1u << bitl);
-                const size_t g0 = base + ((size_t)(mid0 | (e0 << ql)) << A.bit_lo) + l;
-                if (DIF) {
-                    Fr sum = x[e0] + x[e1], dif = x[e0] - x[e1];
-                    if (b != 0) {
-                        size_t j = g0 & (((size_t)1 << b) - 1);
-                        dif = dif * gload_fr(A.tw + (j << (A.logn - 1 - b)));
-                    }
-                    x[e0] = sum;
-                    x[e1] = dif;
-                } else {
-                    Fr y = x[e1];
-                    if (b != 0) {
-                        size_t j = g0 & (((size_t)1 << b) - 1);
-                        y = y * gload_fr(A.tw + (j << (A.logn - 1 - b)));
-                    }
-                    Fr sum = x[e0] + y, dif = x[e0] - y;
-                    x[e0] = sum;
-                    x[e1] = dif;
-                }
-            }
-        }
-#pragma unroll
-        for (unsigned e = 0; e < NE; e++) {
-            const unsigned t = ((mid0 | (e << ql)) << A.logL) + l;
-            if (last) {
-                if (A.post) x[e] = x[e] * gload_fr(A.post + base + ((size_t)(mid0 | (e << ql)) << A.bit_lo) + l);
-                else if (A.has_post_const) x[e] = x[e] * A.post_const;
-            }
-            lds_store(lo, hi, t, x[e]);
-        }
-    }
-}
-
-__global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(PassArgs A) {
-    prio_mid();
-    extern __shared__ uint4 lds[];
-    const unsigned E = 1u << (A.k + A.logL);
-    uint4* lo = lds;
-    uint4* hi = lds + E;
-    const unsigned L = 1u << A.logL;
-    const unsigned lo_blks = (1u << A.bit_lo) >> A.logL;  // >= 1
-    const size_t tile = blockIdx.x;
-    const size_t hi_idx = tile / lo_blks;
-    const unsigned lo_blk = (unsigned)(tile % lo_blks);
-    const size_t base = (hi_idx << (A.bit_lo + A.k)) + ((size_t)lo_blk << A.logL);
-    uint4* g = reinterpret_cast<uint4*>(A.data);
-
-    // ---- load tile: consecutive threads fetch consecutive 16-byte halves
-    for (unsigned h = threadIdx.x; h < 2 * E; h += NTT_THREADS) {
-        unsigned e = h >> 1, half = h & 1;
-        unsigned mid = e >> A.logL, l = e & (L - 1);
-        size_t gi = base + ((size_t)mid << A.bit_lo) + l;
-        uint4 v = g[gi * 2 + half];
-        (half ? hi : lo)[e] = v;
-    }
-    __syncthreads();
-
-    // Stages are taken up to three at a time: a lane pulls the 2^G elements of one radix-2^G butterfly group out of LDS, runs
-    // G stages on them in registers and puts them back -- one LDS round trip and one barrier per G stages instead of per stage.
-    for (unsigned s0 = 0; s0 < A.k;) {
-        const unsigned G = (A.k - s0 >= 3) ? 3 : (A.k - s0);
-        const bool first = (s0 == 0), last = (s0 + G == A.k);
-        if (A.dif) {
-            if (G == 3) ntt_group<3, true>(A, lo, hi, base, E, s0, first, last);
-            else if (G == 2) ntt_group<2, true>(A, lo, hi, base, E, s0, first, last);
-            else ntt_group<1, true>(A, lo, hi, base, E, s0, first, last);
-        } else {
-            if (G == 3) ntt_group<3, false>(A, lo, hi, base, E, s0, first, last);
-            else if (G == 2) ntt_group<2, false>(A, lo, hi, base, E, s0, first, last);
-            else ntt_group<1, false>(A, lo, hi, base, E, s0, first, last);
-        }
-        s0 += G;
-        __syncthreads();
-    }
-
-    for (unsigned h = threadIdx.x; h < 2 * E; h += NTT_THREADS) {
-        unsigned e = h >> 1, half = h & 1;
-        unsigned mid = e >> A.logL, l = e & (L - 1);
-        size_t gi = base + ((size_t)mid << A.bit_lo) + l;
-        g[gi * 2 + half] = (half ? hi : lo)[e];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ 29-bit-limb passes
-// Same pass structure with the butterflies in the unsaturated representation of ff29.hpp (Fr29): 1.4x fewer instructions per
-// product, additions without carries.  Elements sit in LDS as 9 limbs (two 16-byte halves + the top limb) between the stage
+// The butterflies run in the unsaturated representation of ff29.hpp (Fr29): 1.4x fewer instructions per product than 8 x 32-bit
+// limbs, additions without carries.  Elements sit in LDS as 9 limbs (two 16-byte halves + the top limb) between the stage
 // groups of a pass and as 8 packed words at its ends; A.tw is the w * 2^261 table.  Schedules and bounds: tools/u29_ntt_model.py.
 __device__ __forceinline__ U29 lds_load9(const uint4* lo, const uint4* hi, const uint32_t* top, unsigned t) {
     uint4 a = lo[t], b = hi[t];
@@ -379,8 +270,8 @@ __device__ __forceinline__ void tile_copy_out(Fr* dst, unsigned logL, unsigned b
     }
 }
 
-// 512 lanes: two workgroups per CU (4 waves per SIMD, <= 128 VGPRs); 256 lanes (radix-8 groups, A/B variant): two waves per SIMD.  The register counts are
-// what -Rpass-analysis=kernel-resource-usage shows (512 lanes: 121, 125 with SUB, 107 for k_ntt_pass29_if); asking for them with __launch_bounds__(512, 4) gives the same
+// The passes are launched with radix-4 groups on 512 lanes: two workgroups per CU (4 waves per SIMD, <= 128 VGPRs).  The register counts are
+// what -Rpass-analysis=kernel-resource-usage shows (121, 125 with SUB, 107 for k_ntt_pass29_if); asking for them with __launch_bounds__(512, 4) gives the same
 // counts and a schedule that is 1.5 % slower on a 2^26-point transform (measured), so the bound stays implicit -- check the remark when touching the kernels.
 #define ZK_NTT_BOUNDS(THREADS) __launch_bounds__(THREADS)
 
@@ -468,7 +359,7 @@ __global__ void k_h_pointwise(Fr* a, const Fr* b, const Fr* c, Fr den, size_t n)
     a[i] = x * den;
 }
 
-// h = (u - c) * den: the last step of computeH when c stays in coefficient form (see compute_h_inplace)
+// h = (u - c) * den: the last step of computeH when c stays in coefficient form (see compute_h_rows_inplace)
 __global__ void k_h_final(Fr* u, const Fr* c, Fr den, size_t n) {
     prio_mid();
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -542,13 +433,9 @@ int get_domain(Slot* s, hipStream_t st, unsigned logn, unsigned need, Domain** o
     return ZK_OK;
 }
 
-// Runs the log2(N) stages of one transform as a sequence of tile passes.
-// radix-4 stage groups with 512 lanes per tile (4 waves per SIMD) instead of radix-8 with 256 (2 waves per SIMD): measured 8 % faster --
-// the waves of a pass spend ~40 % of their time parked on twiddle / tile loads and barriers, which more resident waves hide.
-// ZKMI_NTT_G2=0 selects the radix-8 variant (A/B switch).
-static const bool g_ntt_g2 = (ZK_EXP("ZKMI_NTT_G2", 1) != 0);
-static const bool g_ntt_saturated = ZK_EXP("ZKMI_NTT_SAT", 0) == 1;  // A/B switch: the 8 x 32-bit butterflies
-
+// A transform runs its log2(N) stages as a sequence of tile passes, each with radix-4 stage groups on 512 lanes per tile (4 waves per SIMD): measured
+// 8 % faster than radix-8 groups on 256 lanes (2 waves per SIMD) -- the waves of a pass spend ~40 % of their time parked on twiddle / tile loads and
+// barriers, which more resident waves hide.
 struct PassPlan { unsigned bit_lo, k, logL; };
 // split of the index bits: the lowest kc bits form the contiguous pass (L = 1); the rest go to strided passes (increasing bit order)
 static std::vector<PassPlan> plan_passes(unsigned logn) {
@@ -583,14 +470,14 @@ static int copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, s
     return ZK_OK;
 }
 
-// One pass: k_ntt_pass29_if where A.tw2 is set, else k_ntt_pass29 (or, sat, the saturated k_ntt_pass: one row only).  A launch over one row carries the name the
-// benchmark's roofline prices as one vector per launch; a launch over more rows the `_rows` name.
-static int launch_pass(Slot* s, hipStream_t st, const PassArgs& A_, const RowArgs& R, size_t rows, bool sat) {
+// One pass: k_ntt_pass29_if where A.tw2 is set, else k_ntt_pass29.  A launch over one row carries the name the benchmark's roofline prices as one vector
+// per launch; a launch over more rows the `_rows` name.
+static int launch_pass(Slot* s, hipStream_t st, const PassArgs& A_, const RowArgs& R, size_t rows) {
     static const char* const names[2][3] = {{"ntt_pass_contig", "ntt_pass_strided", "ntt_pass_contig_if"},
                                             {"ntt_pass_contig_rows", "ntt_pass_strided_rows", "ntt_pass_contig_if_rows"}};
     const unsigned E = 1u << (A_.k + A_.logL);
     const unsigned tiles = (unsigned)(((size_t)1 << A_.logn) / E);
-    const unsigned ny = sat ? 1 : 1 + (A_.data2 ? 1 : 0) + (A_.data2 && A_.data3 ? 1 : 0);
+    const unsigned ny = 1 + (A_.data2 ? 1 : 0) + (A_.data2 && A_.data3 ? 1 : 0);
     for (size_t r0 = 0; r0 < rows; r0 += ROWS_PER_LAUNCH) {
         const unsigned nz = (unsigned)std::min(rows - r0, ROWS_PER_LAUNCH);
         const char* name = names[nz > 1][A_.tw2 ? 2 : (A_.logL ? 1 : 0)];
@@ -607,13 +494,9 @@ static int launch_pass(Slot* s, hipStream_t st, const PassArgs& A_, const RowArg
         if (A.pre) A.pre += o;
         if (A.sub) A.sub += o;
         const dim3 grid(tiles, ny, nz);
-        if (sat) ZK_LAUNCH(s, st, name, k_ntt_pass, dim3(tiles), dim3(NTT_THREADS), (size_t)E * 32, A);
-        else if (A.tw2 && g_ntt_g2) ZK_LAUNCH(s, st, name, (k_ntt_pass29_if<2, 512>), grid, dim3(512), (size_t)E * 36, A, R);
-        else if (A.tw2) ZK_LAUNCH(s, st, name, (k_ntt_pass29_if<3, 256>), grid, dim3(NTT_THREADS), (size_t)E * 36, A, R);
-        else if (A.sub && g_ntt_g2) ZK_LAUNCH(s, st, name, (k_ntt_pass29<2, 512, true>), grid, dim3(512), (size_t)E * 36, A, R);
-        else if (A.sub) ZK_LAUNCH(s, st, name, (k_ntt_pass29<3, 256, true>), grid, dim3(NTT_THREADS), (size_t)E * 36, A, R);
-        else if (g_ntt_g2) ZK_LAUNCH(s, st, name, (k_ntt_pass29<2, 512>), grid, dim3(512), (size_t)E * 36, A, R);
-        else ZK_LAUNCH(s, st, name, (k_ntt_pass29<3, 256>), grid, dim3(NTT_THREADS), (size_t)E * 36, A, R);
+        if (A.tw2) ZK_LAUNCH(s, st, name, (k_ntt_pass29_if<2, 512>), grid, dim3(512), (size_t)E * 36, A, R);
+        else if (A.sub) ZK_LAUNCH(s, st, name, (k_ntt_pass29<2, 512, true>), grid, dim3(512), (size_t)E * 36, A, R);
+        else ZK_LAUNCH(s, st, name, (k_ntt_pass29<2, 512>), grid, dim3(512), (size_t)E * 36, A, R);
     }
     return ZK_OK;
 }
@@ -622,17 +505,9 @@ static int launch_pass(Slot* s, hipStream_t st, const PassArgs& A_, const RowArg
 static int run_passes(Slot* s, hipStream_t st, Fr* data, size_t stride, size_t rows, const Domain* dom, int inverse, int dif, const Fr* pre, const Fr* post,
                       const Fr* post_const, const Fr* src = nullptr, const Fr* sub = nullptr, bool row_ops = false) {
     // src (optional): the rows of the input live there, `stride` apart like the data, and stay untouched -- the first pass reads them and writes `data`
-    // sub (29-bit-limb passes only, with `post` AND `post_const`): the last stage leaves (x * post[i] - sub[i]) * post_const
+    // sub (with `post` AND `post_const`): the last stage leaves (x * post[i] - sub[i]) * post_const
     // row_ops: `pre` and `sub` are operands of each row, `stride` apart like the data (else one table for every row)
     const unsigned logn = dom->logn;
-    const bool sat = g_ntt_saturated;
-    if (sat && rows > 1) {  // the saturated kernels (A/B switch) have no row form: row by row
-        const size_t op = row_ops ? stride : 0;
-        for (size_t i = 0; i < rows; i++)
-            ZK_TRY(run_passes(s, st, data + i * stride, 0, 1, dom, inverse, dif, pre ? pre + i * op : nullptr, post, post_const, src ? src + i * stride : nullptr,
-                              sub ? sub + i * op : nullptr));
-        return ZK_OK;
-    }
     if (src == data) src = nullptr;
     if (logn == 0) {  // rows of one element: a transform of one point is its scaling (1/N = 1)
         if ((row_ops && pre) || sub) return set_err(ZK_ERR_ARG, "per-row operands need a domain of at least two points");
@@ -643,11 +518,7 @@ static int run_passes(Slot* s, hipStream_t st, Fr* data, size_t stride, size_t r
         if (post) ZK_LAUNCH(s, st, name, k_scale_table_rows, dim3(grid), dim3(256), 0, data, stride, post, rows);
         return ZK_OK;
     }
-    if (sat && src) {  // the saturated kernels work in place only
-        ZK_TRY(copy_rows(data, stride * sizeof(Fr), src, stride * sizeof(Fr), sizeof(Fr) << logn, rows, hipMemcpyDeviceToDevice, st));
-        src = nullptr;
-    }
-    const Fr* tw = sat ? (inverse ? dom->tw_inv : dom->tw) : (inverse ? dom->tw29_inv : dom->tw29);
+    const Fr* tw = inverse ? dom->tw29_inv : dom->tw29;
     const RowArgs R = {stride, row_ops ? stride : 0};
     std::vector<PassPlan> passes = plan_passes(logn);
     const size_t npass = passes.size();
@@ -660,17 +531,16 @@ static int run_passes(Slot* s, hipStream_t st, Fr* data, size_t stride, size_t r
         A.pre = (idx == 0) ? pre : nullptr;
         A.post = (idx + 1 == npass) ? post : nullptr;
         A.has_post_const = (idx + 1 == npass && post_const && !post) ? 1 : 0;
-        A.sub = (idx + 1 == npass && !sat) ? sub : nullptr;
+        A.sub = (idx + 1 == npass) ? sub : nullptr;
         if (A.has_post_const || A.sub) A.post_const = *post_const; else A.post_const = Fr::zero();
         A.canonical = (idx + 1 == npass) ? 1 : 0;
-        ZK_TRY(launch_pass(s, st, A, R, rows, sat));
+        ZK_TRY(launch_pass(s, st, A, R, rows));
     }
     return ZK_OK;
 }
 
 // FFTInverse(DIF) with `mid` applied at its end (1/N and whatever scaling follows), then FFT(DIT): as run_passes twice, but the two
 // contiguous passes in the middle are ONE kernel (k_ntt_pass29_if).
-static const bool g_ntt_fuse_if = (ZK_EXP("ZKMI_NTT_FUSE", 1) != 0);  // A/B switch
 static int run_inverse_forward(Slot* s, hipStream_t st, Fr* data, size_t stride, size_t rows, const Domain* dom, const Fr* mid, const Fr* src = nullptr,
                                Fr* data2 = nullptr, const Fr* src2 = nullptr, Fr* data3 = nullptr, const Fr* src3 = nullptr, const Fr* end3 = nullptr) {
     // src (optional): the input lives there and stays untouched -- the first pass reads it and writes `data`
@@ -679,23 +549,10 @@ static int run_inverse_forward(Slot* s, hipStream_t st, Fr* data, size_t stride,
     // launches of the inverse half (gridDim.y = 3)
     // rows of data2 / data3 / src* lie `stride` apart like those of `data`
     const unsigned logn = dom->logn;
-    if (g_ntt_saturated || !g_ntt_fuse_if || logn == 0) {
-        if (rows > 1) {  // the unfused A/B variants have no row form: row by row
-            for (size_t i = 0; i < rows; i++) {
-                const size_t d = i * stride;
-                ZK_TRY(run_inverse_forward(s, st, data + d, 0, 1, dom, mid, src ? src + d : nullptr, data2 ? data2 + d : nullptr, src2 ? src2 + d : nullptr,
-                                           data3 ? data3 + d : nullptr, src3 ? src3 + d : nullptr, end3));
-            }
-            return ZK_OK;
-        }
-        if (data2) {  // and take the vectors one after the other
-            ZK_TRY(run_inverse_forward(s, st, data, 0, 1, dom, mid, src));
-            ZK_TRY(run_inverse_forward(s, st, data2, 0, 1, dom, mid, src2));
-            return data3 ? run_passes(s, st, data3, 0, 1, dom, 1, 1, nullptr, nullptr, end3, src3) : ZK_OK;
-        }
-        if (src && src != data) ZK_HIP(hipMemcpyAsync(data, src, sizeof(Fr) << logn, hipMemcpyDeviceToDevice, st));
-        ZK_TRY(run_passes(s, st, data, 0, 1, dom, 1, 1, nullptr, mid, nullptr));
-        return run_passes(s, st, data, 0, 1, dom, 0, 0, nullptr, nullptr, nullptr);
+    if (logn == 0) {  // one point has no passes to fuse: the inverse transform is its scaling by mid[0], the forward one the identity, *end3 is 1/N = 1
+        ZK_TRY(run_passes(s, st, data, stride, rows, dom, 1, 1, nullptr, mid, nullptr, src));
+        if (data2) ZK_TRY(run_passes(s, st, data2, stride, rows, dom, 1, 1, nullptr, mid, nullptr, src2));
+        return (data2 && data3) ? run_passes(s, st, data3, stride, rows, dom, 1, 1, nullptr, nullptr, end3, src3) : ZK_OK;
     }
     const RowArgs R = {stride, 0};
     std::vector<PassPlan> passes = plan_passes(logn);
@@ -712,7 +569,7 @@ static int run_inverse_forward(Slot* s, hipStream_t st, Fr* data, size_t stride,
     for (size_t idx = npass - 1; idx >= 1; idx--) {  // strided passes of the inverse transform, top bits first
         const PassPlan& p = passes[idx];
         A.tw = dom->tw29_inv; A.bit_lo = p.bit_lo; A.k = p.k; A.logL = p.logL; A.dif = 1; A.canonical = 0;
-        ZK_TRY(launch_pass(s, st, A, R, rows, false));
+        ZK_TRY(launch_pass(s, st, A, R, rows));
         A.src = nullptr;
         A.src2 = nullptr;
         A.src3 = nullptr;
@@ -720,7 +577,7 @@ static int run_inverse_forward(Slot* s, hipStream_t st, Fr* data, size_t stride,
     {  // the contiguous passes of both transforms: one launch
         A.tw = dom->tw29_inv; A.tw2 = dom->tw29; A.bit_lo = 0; A.k = passes[0].k; A.logL = 0; A.dif = 1; A.post = mid;
         A.canonical = (npass == 1) ? 1 : 0;
-        ZK_TRY(launch_pass(s, st, A, R, rows, false));
+        ZK_TRY(launch_pass(s, st, A, R, rows));
         A.post = nullptr;
         A.tw2 = nullptr;
         A.src = nullptr;
@@ -731,7 +588,7 @@ static int run_inverse_forward(Slot* s, hipStream_t st, Fr* data, size_t stride,
     for (size_t idx = 1; idx < npass; idx++) {  // strided passes of the forward transform, low bits first
         const PassPlan& p = passes[idx];
         A.tw = dom->tw29; A.bit_lo = p.bit_lo; A.k = p.k; A.logL = p.logL; A.dif = 0; A.canonical = (idx + 1 == npass) ? 1 : 0;
-        ZK_TRY(launch_pass(s, st, A, R, rows, false));
+        ZK_TRY(launch_pass(s, st, A, R, rows));
     }
     return ZK_OK;
 }
@@ -742,12 +599,8 @@ static int ensure_lds_attr() {
     std::lock_guard<std::mutex> lk(g_lds_mu);
     const uint64_t bit = (uint64_t)1 << current_entry();
     if (!(g_lds_attr_set & bit)) {
-        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 32));
-        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29<3, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
         ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29<2, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
-        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29<3, 256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
         ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29<2, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
-        ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_if<3, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
         ZK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ntt_pass29_if<2, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (1 << TILE_LOG) * 36));
         g_lds_attr_set |= bit;
     }
@@ -785,90 +638,30 @@ int bit_reverse_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn) {
     return ZK_OK;
 }
 
-// the A/B switches of computeH's schedule (explained where compute_h_inplace uses them)
-static const bool skip_c = (ZK_EXP("ZKMI_H_SKIP_C", 1) != 0);
-static const bool h_batch = ZK_EXP("ZKMI_H_BATCH", 1) == 1;
-static const bool fuse_pw = ZK_EXP("ZKMI_H_FUSE_PW", 1) == 1;
-// the production schedule, which has a row form (compute_h_rows_inplace); everything else takes one triple at a time (compute_h_inplace)
-static bool h_production(unsigned logN) { return skip_c && h_batch && fuse_pw && !g_ntt_saturated && logN > 0; }
-
-// gnark v0.8.0 computeH on device buffers a (in/out, N), b, c (scratch, N); result left in a, bit-reversed order.
+// gnark v0.8.0 computeH on `rows` triples of device buffers, row i at a / b / c + i * row_stride: a (in/out, N), b, c (scratch, N); h of row i is left in
+// a + i * row_stride, bit-reversed order.
 //   3 x FFTInverse(DIF) ; 3 x FFT(DIT, coset) ; a = (a*b - c) / (g^N - 1) ; FFTInverse(a, DIF, coset)
-// The 1/N of the first inverse and the coset pre-scale g^bitrev(i) of the following forward transform are one
-// table (coset_rev_n) applied while the inverse transform stores its last stage.
-int compute_h_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned logN, const Fr* const* src, const hipStream_t* side) {
-    // src (optional): the three inputs live in src[0..2] (full 2^logN vectors) and are left untouched; a, b, c are then pure outputs / scratch
-    // side (optional): two more streams -- the transforms of b and c run on them, concurrently with a's on `st` (whatever produced the inputs must
-    // be ordered before `st`): every pass is load -> butterflies -> store in lock-step over the whole machine at sizes that fit one round of
-    // workgroups, so three transforms in flight put one array's loads / stores under another's butterflies.
-    if (!side && h_production(logN)) return compute_h_rows_inplace(s, st, a, b, c, logN, 1, 0, src);
+// The 1/N of the first inverse and the coset pre-scale g^bitrev(i) of the following forward transform are one table (coset_rev_n) applied while the
+// inverse transform stores its last stage.  The row is a grid dimension: as many launches as ONE computeH whatever the row count.
+int compute_h_rows_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned logN, size_t rows, size_t row_stride, const Fr* const* src) {
+    // src (optional): the rows of the three inputs live in src[0..2] (full 2^logN vectors, row_stride apart) and are left untouched; a, b, c are then pure
+    // outputs / scratch
+    if (rows == 0) return ZK_OK;
     ZK_TRY(ensure_lds_attr());
     Domain* d;
     ZK_TRY(get_domain(s, st, logN, DOM_TW | DOM_TW_INV | DOM_COSET_REV_N | DOM_COSET_INV_N_REV, &d));
-    size_t N = (size_t)1 << logN;
-    Fr* vs[3] = {a, b, c};
-    // ZKMI_H_SKIP_C=1 without the whole production schedule: c stays in coefficient form (see compute_h_rows_inplace).  ZKMI_H_SKIP_C=0: the literal sequence.
-    if (skip_c && !side && logN > 0) {
-        const Fr cinv = to_dev(d->card_inv);
-        if (h_batch) {  // ZKMI_H_BATCH=0 (A/B switch): one vector per launch
-            ZK_TRY(run_inverse_forward(s, st, a, 0, 1, d, d->coset_rev_n, src ? src[0] : nullptr, b, src ? src[1] : nullptr, c, src ? src[2] : nullptr, &cinv));
-        } else {
-            for (int i = 0; i < 2; i++) ZK_TRY(run_inverse_forward(s, st, vs[i], 0, 1, d, d->coset_rev_n, src ? src[i] : nullptr));
-            ZK_TRY(run_passes(s, st, c, 0, 1, d, 1, 1, nullptr, nullptr, &cinv, src ? src[2] : nullptr));
-        }
-        HFr gN = d->coset;
-        for (unsigned i = 0; i < logN; i++) gN = gN.sqr();
-        const Fr den = to_dev((gN - HFr::one()).inv());
-        // ZKMI_H_FUSE_PW=0 (A/B switch), or the saturated kernels: the product and the closing step as two element-wise kernels
-        if (fuse_pw && !g_ntt_saturated) return run_passes(s, st, a, 0, 1, d, 1, 1, b, d->coset_inv_n_rev, &den, nullptr, c);
-        ZK_LAUNCH(s, st, "fr_mul", k_fr_mul, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, a, (const Fr*)a, (const Fr*)b, N);
-        ZK_TRY(run_passes(s, st, a, 0, 1, d, 1, 1, nullptr, d->coset_inv_n_rev, nullptr));
-        ZK_LAUNCH(s, st, "h_final", k_h_final, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, a, (const Fr*)c, den, N);
-        return ZK_OK;
-    }
-    if (side) {
-        hipEvent_t fork, join[2];
-        ZK_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
-        ZK_HIP(hipEventRecord(fork, st));
-        for (int i = 0; i < 2; i++) {
-            ZK_HIP(hipStreamWaitEvent(side[i], fork, 0));
-            ZK_TRY(run_inverse_forward(s, side[i], vs[i + 1], 0, 1, d, d->coset_rev_n, src ? src[i + 1] : nullptr));
-            ZK_HIP(hipEventCreateWithFlags(&join[i], hipEventDisableTiming));
-            ZK_HIP(hipEventRecord(join[i], side[i]));
-        }
-        ZK_TRY(run_inverse_forward(s, st, vs[0], 0, 1, d, d->coset_rev_n, src ? src[0] : nullptr));
-        for (int i = 0; i < 2; i++) {
-            ZK_HIP(hipStreamWaitEvent(st, join[i], 0));
-            (void)hipEventDestroy(join[i]);
-        }
-        (void)hipEventDestroy(fork);
-    } else {
-        for (int i = 0; i < 3; i++) ZK_TRY(run_inverse_forward(s, st, vs[i], 0, 1, d, d->coset_rev_n, src ? src[i] : nullptr));
-    }
-    // den = 1 / (g^N - 1)
     HFr gN = d->coset;
     for (unsigned i = 0; i < logN; i++) gN = gN.sqr();
-    HFr den = (gN - HFr::one()).inv();
-    ZK_LAUNCH(s, st, "h_pointwise", k_h_pointwise, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, a, (const Fr*)b, (const Fr*)c, to_dev(den), N);
-    ZK_TRY(run_passes(s, st, a, 0, 1, d, 1, 1, nullptr, d->coset_inv_n_rev, nullptr));
-    return ZK_OK;
-}
-
-// computeH's production schedule on `rows` triples, row i at a / b / c + i * row_stride, with the row as a grid dimension: as many launches as ONE computeH whatever
-// the row count.  h of row i is left in a + i * row_stride, bit-reversed.
-int compute_h_rows_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned logN, size_t rows, size_t row_stride, const Fr* const* src) {
-    // src (optional): the rows of the three inputs live in src[0..2] (full 2^logN vectors, row_stride apart) and are left untouched
-    if (rows == 0) return ZK_OK;
-    if (!h_production(logN)) {  // the A/B variants and the one-point domain: row by row
+    const Fr den = to_dev((gN - HFr::one()).inv());
+    if (logN == 0) {  // one point: per-row operands need two, so gnark's literal sequence, a row at a time
         for (size_t i = 0; i < rows; i++) {
-            const Fr* si[3] = {src ? src[0] + i * row_stride : nullptr, src ? src[1] + i * row_stride : nullptr, src ? src[2] + i * row_stride : nullptr};
-            ZK_TRY(compute_h_inplace(s, st, a + i * row_stride, b + i * row_stride, c + i * row_stride, logN, src ? si : nullptr));
+            Fr* v[3] = {a + i * row_stride, b + i * row_stride, c + i * row_stride};
+            for (int j = 0; j < 3; j++) ZK_TRY(run_inverse_forward(s, st, v[j], 0, 1, d, d->coset_rev_n, src ? src[j] + i * row_stride : nullptr));
+            ZK_LAUNCH(s, st, "h_pointwise", k_h_pointwise, dim3(1), dim3(256), 0, v[0], (const Fr*)v[1], (const Fr*)v[2], den, (size_t)1);
+            ZK_TRY(run_passes(s, st, v[0], 0, 1, d, 1, 1, nullptr, d->coset_inv_n_rev, nullptr));
         }
         return ZK_OK;
     }
-    ZK_TRY(ensure_lds_attr());
-    Domain* d;
-    ZK_TRY(get_domain(s, st, logN, DOM_TW | DOM_TW_INV | DOM_COSET_REV_N | DOM_COSET_INV_N_REV, &d));
     // By linearity (exact field arithmetic, so bit for bit for ANY input): FFTInverse(coset)((a'b' - c') den) = den (FFTInverse(coset)(a'b') - FFTInverse(c)),
     // where c' = FFT(coset)(FFTInverse(c)) -- the coset transform of c and its way back cancel.  c therefore only needs its first FFTInverse(DIF)
     // (coefficients, bit-reversed like the result): six transforms instead of gnark's seven.
@@ -877,13 +670,12 @@ int compute_h_rows_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigne
     // launches disappear.
     const Fr cinv = to_dev(d->card_inv);
     ZK_TRY(run_inverse_forward(s, st, a, row_stride, rows, d, d->coset_rev_n, src ? src[0] : nullptr, b, src ? src[1] : nullptr, c, src ? src[2] : nullptr, &cinv));
-    HFr gN = d->coset;
-    for (unsigned i = 0; i < logN; i++) gN = gN.sqr();
-    const Fr den = to_dev((gN - HFr::one()).inv());
     // the product a*b rides on the loads of the closing transform's first stage (`pre` = b) and (x - c) * den on the stores of its last one (`sub` = c)
     // instead of two element-wise kernels (96 B per element each)
     return run_passes(s, st, a, row_stride, rows, d, 1, 1, b, d->coset_inv_n_rev, &den, nullptr, c, true);
 }
+
+int compute_h_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned logN, const Fr* const* src) { return compute_h_rows_inplace(s, st, a, b, c, logN, 1, 0, src); }
 
 int fr_mul_dev(Slot* s, hipStream_t st, Fr* out, const Fr* a, const Fr* b, size_t n) {
     ZK_LAUNCH(s, st, "fr_mul", k_fr_mul, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, out, a, b, n);
@@ -1006,7 +798,7 @@ int compute_h_shard_phase(Slot* s, hipStream_t st, int phase, Fr* a, Fr* b, Fr* 
         }
         case 3:  // block of a: rest of FFTInverse(DIF, coset) -> this rank's block of h (gnark's bit-reversed order)
             return run_passes(s, st, a, 0, 1, dM, 1, 1, nullptr, tb.coset_inv_n_rev, nullptr);
-        // ---- the six-transform schedule (c stays in coefficient form: compute_h_inplace's shortcut, sharded; one transpose and two transforms of c fewer)
+        // ---- the six-transform schedule (c stays in coefficient form: compute_h_rows_inplace's shortcut, sharded; one transpose and two transforms of c fewer)
         case 6: {  // blocks (any subset; the schedule uses it for c): rest of FFTInverse(DIF) with 1/D -> block of the coefficients, bit-reversed order
             const Fr cinv = to_dev(dD->card_inv);
             for (Fr* v : {a, b, c})

@@ -30,7 +30,8 @@ int ntt_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn, int inverse, int de
 // the same on `rows` vectors in one launch per pass: row i at d_a + i * row_stride (in Fr elements, >= 2^logn)
 int ntt_rows_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn, size_t rows, size_t row_stride, int inverse, int decimation, int coset);
 int bit_reverse_dev(Slot* s, hipStream_t st, Fr* d_a, unsigned logn);
-int compute_h_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned logN, const Fr* const* src = nullptr, const hipStream_t* side = nullptr);
+// computeH of one triple: h left in a (bit-reversed), b and c are scratch.  src (optional): the inputs live in src[0..2] and stay untouched
+int compute_h_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned logN, const Fr* const* src = nullptr);
 // computeH of `rows` triples in the launches of one: row i at a / b / c + i * row_stride, h left in the a rows (bit-reversed).  src as in compute_h_inplace, per row
 int compute_h_rows_inplace(Slot* s, hipStream_t st, Fr* a, Fr* b, Fr* c, unsigned logN, size_t rows, size_t row_stride, const Fr* const* src = nullptr);
 int fr_mul_dev(Slot* s, hipStream_t st, Fr* out, const Fr* a, const Fr* b, size_t n);

@@ -443,27 +443,7 @@ struct QuotArgs {
     Fr xn_inv[8];                                                      // 1 / (x^n - 1): x^n takes rho <= 8 values on the coset
     unsigned logN4, log_rho;
 };
-// t(x) = [ gate(x) + alpha * (zs * prod(w + beta s_j + gamma) - z * prod(w + beta u^j x + gamma)) + alpha^2 (z - 1) L1 ] / (x^n - 1)
-// (prove.go: fic / fo / fone / fm, then iop.DivideByXMinusOne); index i is the bit-reversed position of natural index j.
-__global__ __launch_bounds__(256) void k_quotient(QuotArgs A) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t N4 = (size_t)1 << A.logN4;
-    if (i >= N4) return;
-    const unsigned j = brev((unsigned)i, A.logN4);
-    const unsigned rho = 1u << A.log_rho;
-    const unsigned js = (j + rho) & (unsigned)(N4 - 1);  // z(omega * x): omega = W^rho
-    const size_t is = brev(js, A.logN4);
-    Fr l = ld(A.el + i), r = ld(A.er + i), o = ld(A.eo + i), z = ld(A.ez + i), zs = ld(A.ez + is), x = ld(A.id + i);
-    Fr gate = ld(A.ql + i) * l + ld(A.qr + i) * r + ld(A.qm + i) * (l * r) + ld(A.qo + i) * o + ld(A.eqk + i);
-    Fr lg = l + A.gamma, rg = r + A.gamma, og = o + A.gamma;
-    Fr a = (lg + A.beta * x) * (rg + A.beta_u * x) * (og + A.beta_uu * x) * z;
-    Fr b = (lg + A.beta * ld(A.s1 + i)) * (rg + A.beta * ld(A.s2 + i)) * (og + A.beta * ld(A.s3 + i)) * zs;
-    Fr one = (z - Fr::one()) * ld(A.l1 + i);
-    Fr t = ((one * A.alpha + (b - a)) * A.alpha + gate) * A.xn_inv[j & (rho - 1)];
-    A.out[i] = t;
-}
-
-// The same numerator with its 21 products in the 9 x 29-bit representation of ff29.hpp (Fr29: 206 instructions per product instead of ~305; the kernel is bound by
+// The numerator with its 21 products in the 9 x 29-bit representation of ff29.hpp (Fr29: 206 instructions per product instead of ~305; the kernel is bound by
 // them, not by its 8.6 GB).  Values loaded from memory are canonical images V = v 2^256; a product needs ONE operand in the multiplier form V << 5 (= v 2^261):
 // u29r_mul(X, Y << 5) = X Y / 2^261 stays in the 2^256 domain.  So the second and third factor of each permutation product are BUILT in the 2^261 domain --
 // (w << 5) + (gamma << 5) + u29r_mul(x << 5, beta << 5) -- and no in-register shift is ever needed.  Sums are plain limb additions; bounds (units of r; checked with
@@ -507,6 +487,8 @@ __device__ __forceinline__ Fr quotient29_point(const Fr* __restrict__ el, const 
     t = u29r_mul(t, u29r_load5(xn_inv));
     return u29r_pack(u29r_reduce(t), true);
 }
+// t(x) = [ gate(x) + alpha * (zs * prod(w + beta s_j + gamma) - z * prod(w + beta u^j x + gamma)) + alpha^2 (z - 1) L1 ] / (x^n - 1)
+// (prove.go: fic / fo / fone / fm, then iop.DivideByXMinusOne); index i is the bit-reversed position of natural index j.
 __global__ __launch_bounds__(256, 4) void k_quotient29(QuotArgs A) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t N4 = (size_t)1 << A.logN4;
@@ -748,8 +730,7 @@ struct BatchCommit3 {
     Affine<HFp> out[3];
     static int run(uint64_t bases, const Fr* const* polys, size_t len, Affine<HFp>* outs, bool wire_values) {
         const void* sc[3] = {polys[0], polys[1], polys[2]};
-        static const bool sparse = ZK_EXP("ZKMI_PLONK_SPARSE_DIGITS", 1) != 0;  // 0: wire values sorted with their zero digits (A/B)
-        if (wire_values && sparse) return msm_bases_batch_dev_sparse(bases, 0, sc, 3, len, &kMont, outs);
+        if (wire_values) return msm_bases_batch_dev_sparse(bases, 0, sc, 3, len, &kMont, outs);
         return zk_bn254_msm_bases_batch_dev(bases, 0, sc, 3, len, &kMont, outs);
     }
     static bool possible(uint64_t bases, const size_t* lens) {
@@ -770,94 +751,6 @@ struct BatchCommit3 {
     }
     ~BatchCommit3() { if (th.joinable()) th.join(); }
 };
-static const bool g_plonk_batch3 = ZK_EXP("ZKMI_PLONK_BATCH3", 1) != 0;  // 0: three commitments on three threads (A/B)
-
-// The commitments of one proof as a CHAIN (the schedule of Groth16's msm5): every MSM prepares its scalars (digits, radix sort, task plan --
-// bandwidth-bound) on a stream of its own as soon as its polynomial exists, while the accumulate kernels (ALU-bound, each wants the whole
-// machine) run ONE AT A TIME in issue order, gated by the previous one's completion event; the reduction tails and the next preparation run
-// underneath.  Needs the SRS's window table; otherwise the thread-per-commit fallback above is used.
-struct CommitChain {
-    static constexpr int NJ = 3;
-    const PlonkPK* P = nullptr;
-    const void* d_table = nullptr;
-    MsmTable tab;
-    SlotsGuard<NJ> g;
-    MsmPrep prep[NJ];
-    MsmJob job[NJ];
-    bool live[NJ] = {};
-    hipEvent_t last_acc = nullptr;   // completion of the most recently enqueued accumulate (owned by the job that recorded it)
-    bool ok = false;
-
-    int init(const PlonkPK* P_, size_t max_len) {
-        P = P_;
-        size_t n = 0;
-        ZK_TRY(bases_table(P->srs, &d_table, &tab, &n));
-        if (!d_table) return ZK_OK;  // no table: the caller falls back
-        ZK_TRY(acquire_slots(NJ, g.s));
-        size_t np = 0, na = 0;
-        ZK_TRY(msm_prep_need_table(max_len, tab, g.s[0]->stream, &np, &na, nullptr));
-        for (int i = 0; i < NJ; i++) ZK_TRY(g.s[i]->reserve(np + na + 65536));
-        ok = true;
-        return ZK_OK;
-    }
-    // d_p must be complete on `producer` (an event is recorded there and awaited by the commit's stream)
-    int start(int k, hipStream_t producer, const Fr* d_p, size_t len) {
-        Slot* s = g.s[k];
-        s->reset();
-        hipEvent_t ev;
-        ZK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        ZK_HIP(hipEventRecord(ev, producer));
-        static const bool prep_hi = (ZK_EXP("ZKMI_PLONK_PREP_HI", 1) != 0);  // A/B switch
-        hipStream_t sp = prep_hi ? s->hi() : s->stream;  // the preparation at high priority: its sort must get wave slots under a running accumulate
-        ZK_TRY(masked_streams(s));
-        hipStream_t sa = s->stream;
-        if (s->stream_prep) { sp = s->stream_prep; sa = s->stream_acc; }  // experiment ZKMI_CU_SPLIT: disjoint CU sets instead of priorities
-        ZK_HIP(hipStreamWaitEvent(sp, ev, 0));
-        (void)hipEventDestroy(ev);
-        job[k] = MsmJob();
-        ZK_TRY(msm_prepare_scalars_table(s, sp, d_p, len, &kMont, tab, &prep[k]));
-        live[k] = true;
-        job[k].gate_acc = last_acc;
-        job[k].want_done = true;
-        ZK_TRY(msm_g1_accumulate(s, sa, prep[k], d_table, 0, &job[k]));
-        if (job[k].acc_done) last_acc = job[k].acc_done;
-        return ZK_OK;
-    }
-    int finish(int k, Affine<HFp>* out) {
-        XYZZ<HFp> t;
-        int rc = msm_g1_finish(job[k], &t);
-        release(k);
-        ZK_TRY(rc);
-        *out = t.to_affine();
-        return ZK_OK;
-    }
-    void release(int k) {
-        if (!live[k]) return;
-        msm_prep_release(&prep[k]);
-        if (job[k].acc_done) {
-            if (last_acc == job[k].acc_done) last_acc = nullptr;  // the accumulate has completed (finish synchronised): nothing to wait for
-            (void)hipEventDestroy(job[k].acc_done);
-            job[k].acc_done = nullptr;
-        }
-        live[k] = false;
-    }
-    ~CommitChain() {
-        for (int k = 0; k < NJ; k++)
-            if (live[k]) {
-                g.s[k]->sync_hi();
-                (void)hipStreamSynchronize(g.s[k]->stream);
-                if (g.s[k]->stream_prep) { (void)hipStreamSynchronize(g.s[k]->stream_prep); (void)hipStreamSynchronize(g.s[k]->stream_acc); }
-                release(k);
-            }
-    }
-};
-// Measured (round 2, 2^22 gates, one box, alternating runs): chain 88.5 - 91.1 ms against 86.8 - 89.7 ms for the thread-per-commit mode, with the preparation
-// at normal or high priority and with latency- or work-structured tails -- rocPRIM's onesweep sort does not make progress underneath a running accumulate
-// kernel (its look-back tiles spin for wave slots), so "sort under accumulate" buys nothing here and the strict one-at-a-time order costs the overlap the
-// threads get by accident.  Off by default; ZKMI_PLONK_CHAIN=1 selects it.
-static const bool g_plonk_chain = ZK_EXP("ZKMI_PLONK_CHAIN", 0) == 1;
-static const bool g_plonk_serial = ZK_EXP("ZKMI_PLONK_SERIAL", 0) == 1;  // A/B switch: commitments one after the other
-
 // Lagrange (regular) -> canonical (regular) on the small domain, in place: FFTInverse(DIF) + BitReverse, as setup.go / iop.ToCanonical do
 static int to_canonical(Slot* s, hipStream_t st, Fr* d, unsigned logn) {
     ZK_TRY(ntt_dev(s, st, d, logn, 1, ZK_DIF, 0));
@@ -1734,25 +1627,9 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
     Fr* lag3[3] = {l_lag, r_lag, o_lag};
     Fr* can3[3] = {bl_, br_, bo_};
     Affine<HFp> c_lro[3], c_z, c_h[3], c_zopen, c_lin, c_batch;
-    CommitChain chain;
-    if (g_plonk_chain && !g_plonk_serial) ZK_TRY(chain.init(P, n + 3));
     // a group of independent commitments + the work the main stream does meanwhile
-    hipStream_t commit_sync = st;  // the stream the polynomials of the next commit_group are produced on
     auto commit_group = [&](int cnt, const Fr* const* polys, const size_t* lens, Affine<HFp>* outs, const std::function<int()>& meanwhile) -> int {
-        if (chain.ok) {
-            for (int k = 0; k < cnt; k++) ZK_TRY(chain.start(k, st, polys[k], lens[k]));
-            int rc = meanwhile();
-            for (int k = 0; k < cnt; k++) {
-                int r2 = chain.finish(k, &outs[k]);
-                if (rc == ZK_OK) rc = r2;
-            }
-            return rc;
-        }
-        if (g_plonk_serial) {
-            for (int k = 0; k < cnt; k++) ZK_TRY(commit(P, s, st, polys[k], lens[k], &outs[k]));
-            return meanwhile();
-        }
-        if (cnt == 3 && g_plonk_batch3 && BatchCommit3::possible(P->srs, lens)) {
+        if (cnt == 3 && BatchCommit3::possible(P->srs, lens)) {
             BatchCommit3 bc;
             ZK_TRY(slot_sync(s, st));
             bc.start(P->srs, polys, lens[0]);
@@ -1763,7 +1640,7 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
             return rc;
         }
         AsyncCommit ac[3];
-        ZK_TRY(slot_sync(s, commit_sync));
+        ZK_TRY(slot_sync(s, st));
         for (int k = 0; k < cnt; k++) ac[k].start(P, polys[k], lens[k]);
         int rc = meanwhile();
         for (int k = 0; k < cnt; k++) {
@@ -1786,23 +1663,11 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
         }
         return ZK_OK;
     };
-    // the three commitments, while this stream already evaluates l, r, o on the big coset (no challenge needed for that).
-    // Experiment ZKMI_PLONK_DEFER_LRO=1: those three transforms wait for round 2 (one commitment there instead of three here: round 1's three scalar
-    // preparations then do not share the machine with them)
-    static const bool defer_lro = ZK_EXP("ZKMI_PLONK_DEFER_LRO", 0) != 0;
-    static const bool use_lagrange = ZK_EXP("ZKMI_PLONK_LAGRANGE", 1) != 0;  // 0: coefficients against the monomial SRS even when the key has its Lagrange form (A/B)
+    // the three commitments, while this stream already evaluates l, r, o on the big coset (no challenge needed for that)
     const Fr* small5[5] = {bl_, br_, bo_, bz_, qkc};
     const size_t len5[5] = {n + 2, n + 2, n + 2, n + 3, n};
     const size_t lens_lag[3] = {n + 2, n + 2, n + 2};
-    static const bool coset_side = ZK_EXP("ZKMI_PLONK_COSET_SIDE", 0) != 0;
-    struct SideEvents {
-        hipEvent_t e[2] = {nullptr, nullptr};
-        hipStream_t side = nullptr;
-        ~SideEvents() { if (side) (void)hipStreamSynchronize(side); for (auto& x : e) if (x) (void)hipEventDestroy(x); }
-    } side_events;
-    hipEvent_t* side_ev = side_events.e;
-    bool side_pending = false, used_lagrange = false;
-    if (P->lag_srs && use_lagrange && !chain.ok && !g_plonk_serial && BatchCommit3::possible(P->lag_srs, lens_lag)) {
+    if (P->lag_srs && BatchCommit3::possible(P->lag_srs, lens_lag)) {
         // From the WIRE VALUES against the SRS's Lagrange form (lagrange.hip): [l] = sum_i l_i [L_i(tau)] + b0 [tau^n - 1] + b1 [tau^(n+1) - tau] -- the same three
         // points, from scalars that are bits and words instead of uniform coefficients, and without waiting for the inverse transforms (they run meanwhile).
         for (int k = 0; k < 3; k++) {
@@ -1812,21 +1677,10 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
             ZK_LAUNCH(s, st, "plonk_blind_tail", k_blind_tail, dim3(1), dim3(64), 0, lag3[k], (uint32_t)n, B);
         }
         ZK_TRY(slot_sync(s, st));
-        used_lagrange = true;
         BatchCommit3 bc;
         bc.start(P->lag_srs, lag3, n + 2, true);
         int rc = lro_canonical();
-        if (rc == ZK_OK && coset_side && !defer_lro) {  // experiment: the three 4n transforms on the slot's other stream, joined before the quotient kernel
-            hipStream_t side = s->hi();
-            side_events.side = side;
-            if (hipEventCreateWithFlags(&side_ev[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&side_ev[1], hipEventDisableTiming) != hipSuccess ||
-                hipEventRecord(side_ev[0], st) != hipSuccess || hipStreamWaitEvent(side, side_ev[0], 0) != hipSuccess)
-                rc = set_err(ZK_ERR_HIP, "event setup failed");
-            for (int k = 0; k < 3 && rc == ZK_OK; k++) rc = to_big_coset(s, side, P->w_big[k], small5[k], len5[k], P);
-            if (rc == ZK_OK && hipEventRecord(side_ev[1], side) != hipSuccess) rc = set_err(ZK_ERR_HIP, "event record failed");
-            side_pending = rc == ZK_OK;
-        } else if (rc == ZK_OK && !defer_lro)
-            for (int k = 0; k < 3 && rc == ZK_OK; k++) rc = to_big_coset(s, st, P->w_big[k], small5[k], len5[k], P);
+        for (int k = 0; k < 3 && rc == ZK_OK; k++) rc = to_big_coset(s, st, P->w_big[k], small5[k], len5[k], P);
         const int r2 = bc.join();
         if (rc == ZK_OK) rc = r2;
         ZK_TRY(rc);
@@ -1836,7 +1690,6 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
         const Fr* polys[3] = {bl_, br_, bo_};
         const size_t lens[3] = {n + 2, n + 2, n + 2};
         ZK_TRY(commit_group(3, polys, lens, c_lro, [&]() -> int {
-            if (defer_lro) return ZK_OK;
             for (int k = 0; k < 3; k++) ZK_TRY(to_big_coset(s, st, P->w_big[k], small5[k], len5[k], P));
             return ZK_OK;
         }));
@@ -1853,29 +1706,21 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
 
     // ---- z
     const HFr u = P->u, uu = u * u;
-    // experiment (ZKMI_PLONK_Z_SIDE=1, with the Lagrange-form round 1): round 1's coset transforms are still running on the main stream when the challenges arrive;
-    // z's chain (short kernels) on the slot's high-priority stream instead of behind them, and its commitment starts as soon as THAT stream is done
-    static const bool z_side = ZK_EXP("ZKMI_PLONK_Z_SIDE", 0) != 0;
-    hipStream_t zst = (z_side && used_lagrange) ? s->hi() : st;
-    ZK_TRY(z_chain_dev(s, zst, d0->tw, u, P->sig, l_lag, r_lag, o_lag, n, beta, gamma, num, den, W + 14 * S, SB, bz_));
-    ZK_HIP(hipMemsetAsync(bz_ + n, 0, 8 * sizeof(Fr), zst));
-    ZK_TRY(to_canonical(s, zst, bz_, logn));
+    ZK_TRY(z_chain_dev(s, st, d0->tw, u, P->sig, l_lag, r_lag, o_lag, n, beta, gamma, num, den, W + 14 * S, SB, bz_));
+    ZK_HIP(hipMemsetAsync(bz_ + n, 0, 8 * sizeof(Fr), st));
+    ZK_TRY(to_canonical(s, st, bz_, logn));
     {
         BlindArgs B;
         B.k = 3;
         for (int i = 0; i < 3; i++) B.b[i] = to_dev(bl[6 + i]);
-        ZK_LAUNCH(s, zst, "plonk_blind", k_blind, dim3(1), dim3(64), 0, bz_, (uint32_t)n, B);
+        ZK_LAUNCH(s, st, "plonk_blind", k_blind, dim3(1), dim3(64), 0, bz_, (uint32_t)n, B);
     }
     // commitment to z; meanwhile: qk completed with the public inputs (canonical), z and qk on the big coset
-    commit_sync = zst;
     {
         const Fr* polys[1] = {bz_};
         const size_t lens[1] = {n + 3};
         ZK_TRY(commit_group(1, polys, lens, &c_z, [&]() -> int {
-            if (defer_lro)
-                for (int k = 0; k < 3; k++) ZK_TRY(to_big_coset(s, st, P->w_big[k], small5[k], len5[k], P));
-            static const bool qk_ntt = ZK_EXP("ZKMI_PLONK_QK_NTT", 0) == 1;  // A/B switch: the literal sequence
-            if (!qk_ntt && npub <= PLONK_PI_DIRECT_MAX && logN4 >= 2) {
+            if (npub <= PLONK_PI_DIRECT_MAX && logN4 >= 2) {
                 ZK_TRY(to_big_coset(s, st, P->w_big[3], small5[3], len5[3], P));
                 ZK_LAUNCH(s, st, "plonk_qk_coset", k_qk_coset, dim3(grid_of(P->N4)), dim3(256), 0, (const Fr*)P->e_cqk, (const Fr*)P->e[7], (const Fr*)d_sol, (const Fr*)P->lqk,
                           (uint32_t)npub, logN4, P->log_rho, P->w_big[4]);
@@ -1888,7 +1733,6 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
             return ZK_OK;
         }));
     }
-    commit_sync = st;
     lap("plonk.round2_z_committed");
     fs.bind_g1(2, c_z);
     HFr alpha = fs.challenge(2);
@@ -1913,10 +1757,7 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
             cur = cur * Wn;
         }
         for (unsigned j = (1u << P->log_rho); j < 8; j++) A.xn_inv[j] = Fr::zero();
-        if (side_pending) ZK_HIP(hipStreamWaitEvent(st, side_ev[1], 0));
-        static const bool quot29 = ZK_EXP("ZKMI_PLONK_QUOT29", 1) != 0;  // A/B switch: 0 = the saturated 8 x 32-bit form
-        if (quot29) ZK_LAUNCH(s, st, "plonk_quotient", k_quotient29, dim3(grid_of(N4)), dim3(256), 0, A);
-        else ZK_LAUNCH(s, st, "plonk_quotient", k_quotient, dim3(grid_of(N4)), dim3(256), 0, A);
+        ZK_LAUNCH(s, st, "plonk_quotient", k_quotient29, dim3(grid_of(N4)), dim3(256), 0, A);
     }
     Fr* h = P->w_big[4];
     ZK_TRY(ntt_dev(s, st, h, logN4, 1, ZK_DIT, 1));  // LagrangeCoset (bit-reversed) -> canonical (regular)
@@ -1932,7 +1773,6 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
         const Fr* polys[3] = {h, h + (n + 2), h + 2 * (n + 2)};
         const size_t lens[3] = {n + 2, n + 2, n + 2};
         ZK_TRY(commit_group(3, polys, lens, c_h, []() -> int { return ZK_OK; }));
-        if (chain.ok) ZK_TRY(slot_sync(s, st));  // h_flag (chain mode does not synchronise this stream)
     }
     if (h_flag) return set_err(ZK_ERR_ARG, "the solution does not satisfy the constraint system (the quotient is not a polynomial)");
     lap("plonk.round3_quotient_committed");
@@ -1950,9 +1790,7 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
     ZK_HIP(hipMemcpyAsync(ev, d_vals, 6 * sizeof(Fr), hipMemcpyDeviceToHost, st));
     ZK_TRY(slot_sync(s, st));  // ev[] is valid, the quotient of z is complete
     AsyncCommit azo;  // the opening of z: finished / joined at the end of the proof, nothing below depends on it
-    if (chain.ok) ZK_TRY(chain.start(0, st, quo, n + 2));
-    else if (g_plonk_serial) ZK_TRY(commit(P, s, st, quo, n + 2, &c_zopen));
-    else azo.start(P, quo, n + 2);
+    azo.start(P, quo, n + 2);
     const HFr lz = ev[0], rz = ev[1], oz = ev[2], s1z = ev[3], s2z = ev[4], zu = ev[5];
 
     // ---- linearised polynomial
@@ -1976,8 +1814,6 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
     // so commit(lin) = (alpha c_z + lag) [Z] + alpha c_s3 [S3] + lz rz [Qm] + lz [Ql] + rz [Qr] + oz [Qo] + [Qk]: the same group element as gnark's kzg.Commit of the
     // polynomial, for seven scalar multiplications on the host (while the GPU runs the kernels above) instead of an (n + 3)-point MSM.  Only for keys whose
     // digests are known to be consistent: Setup's, or -- for a key read from its wire image -- once a first proof has computed both and found them equal.
-    // ZKMI_PLONK_LIN_MSM=1 forces the literal commitment (A/B switch).
-    static const bool lin_msm = ZK_EXP("ZKMI_PLONK_LIN_MSM", 0) == 1;
     Affine<HFp> c_lin_by_linearity;
     {
         const HFr cz_tot = alpha * lin_cz + lin_lag, cs3_tot = alpha * lin_cs3;
@@ -1987,9 +1823,8 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
         acc.madd(P->vk_qk);
         c_lin_by_linearity = acc.to_affine();
     }
-    const bool lin_direct = P->vk_consistent && !lin_msm;
+    const bool lin_direct = P->vk_consistent;
     if (lin_direct) c_lin = c_lin_by_linearity;
-    else if (chain.ok) ZK_TRY(chain.start(1, st, lin, n + 3));  // finished below, after the folded quotient and the last two evaluations are enqueued
     else ZK_TRY(commit(P, s, st, lin, n + 3, &c_lin));
 
     // ---- folded quotient h1 + zeta^(n+2) h2 + zeta^(2(n+2)) h3 and its digest
@@ -2023,8 +1858,7 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
     ZK_HIP(hipMemcpyAsync(ev + 6, d_vals + 6, 2 * sizeof(Fr), hipMemcpyDeviceToHost, st));
     ZK_TRY(slot_sync(s, st));
     lap("plonk.round4_evaluations_and_linearised");
-    if (chain.ok && !lin_direct) ZK_TRY(chain.finish(1, &c_lin));
-    if (!lin_direct && !lin_msm && c_lin.x == c_lin_by_linearity.x && c_lin.y == c_lin_by_linearity.y)
+    if (!lin_direct && c_lin.x == c_lin_by_linearity.x && c_lin.y == c_lin_by_linearity.y)
         const_cast<PlonkPK*>(P)->vk_consistent = true;  // (the key's workspace mutex is held for the whole proof) from the next proof on: by linearity
     const HFr claimed[7] = {ev[6], ev[7], lz, rz, oz, s1z, s2z};
     const Affine<HFp> digests[7] = {c_fh, c_lin, c_lro[0], c_lro[1], c_lro[2], P->vk_s[0], P->vk_s[1]};
@@ -2048,17 +1882,9 @@ int zk_bn254_plonk_prove(uint64_t handle, const void* solution, size_t n_vars, i
     }
     // dividePolyByXminusA(folded, foldedEvaluations, zeta): the recurrence yields the same quotient (folded(zeta) = sum gamma^i v_i)
     ZK_TRY(poly_divide_dev(s, st, fold, n + 3, zeta, SB, fold, d_vals + 8));
-    if (chain.ok) {
-        ZK_TRY(chain.start(2, st, fold, n + 2));
-        ZK_TRY(chain.finish(0, &c_zopen));
-        ZK_TRY(chain.finish(2, &c_batch));
-    } else {
-        ZK_TRY(commit(P, s, st, fold, n + 2, &c_batch));
-        if (!g_plonk_serial) {
-            ZK_TRY(azo.join());
-            c_zopen = azo.out;
-        }
-    }
+    ZK_TRY(commit(P, s, st, fold, n + 2, &c_batch));
+    ZK_TRY(azo.join());
+    c_zopen = azo.out;
     lap("plonk.round5_openings_committed");
     // ---- Proof.WriteTo
     uint8_t* o = proof_out;

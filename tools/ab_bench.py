@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B driver for the experiment switches (ZK_EXP in csrc/ctx.hpp): runs bench.py once per configuration against libzkmi_exp.so -- the build that reads
-the switches; the shipped libzkmi.so has them compiled out -- and prints one compact JSON line per configuration: Groth16 2^20 / 2^24, PLONK 2^22,
+the switches; the shipped libzkmi.so has them compiled out; DESIGN.md 8 lists the switches that exist -- and prints one compact JSON line per configuration: Groth16 2^20 / 2^24, PLONK 2^22,
 the 2^26 MSM, and the per-kernel milliseconds that matter for the schedule (sort, accumulate, tails, transforms).
 
     python tools/ab_bench.py OUT.jsonl  "name:VAR=1,VAR2=0"  "other:VAR=2" ...        (a bare "base" runs the defaults)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Stand-alone computeH (zk_bn254_groth16_compute_h_dev: three resident input vectors -> h) at 2^20 / 2^22 / 2^24: best and median wall time of 30 synchronous
-calls, one JSON line.  After _lib.use_library(<csrc/build_exp/libzkmi_exp.so>) the experiment switches of ntt.hip (ZKMI_H_BATCH, ZKMI_H_FUSE_PW, ...) apply; the sha of h shows that
-every variant computes the same bytes.
+calls, one JSON line.  After _lib.use_library(<csrc/build_exp/libzkmi_exp.so>) the experiment switches of ntt.hip (ZKMI_NTT_UNIT; ZKMI_NTT_TWMASK is timing only) apply; the sha of h shows
+whether a variant computes the same bytes.
     python tools/compute_h_bench.py [log_n ...]"""
 import ctypes as C
 import hashlib
