@@ -491,6 +491,46 @@ int zk_bn254_plonk_verify_batch_keys_dev(const void *d_proofs, size_t proof_stri
         const void *d_public_inputs, size_t pub_stride,
         uint8_t *accepted, size_t *n_accepted);
 
+/* Batch Groth16 verification against MANY verifying keys in one call (DESIGN 3.9 "Many keys"): row i is a proof for vks[key_of[i]].  Groth16 keys share
+ * nothing -- each has its own alpha, beta, gamma, delta and K table -- so a chunk's check is
+ *   prod_i e(r_i Ar_i, Bs_i)  prod_{k used} e(-c_k0 alpha_k, beta_k) e(-sum_j c_kj K_kj, gamma_k) e(-sum_{i: key_of[i] = k} r_i Krs_i, delta_k) == 1,
+ *   c_kj = sum_{i: key_of[i] = k, i valid} r_i w_ij (w_i0 = 1):
+ * n + 3 K_used Miller loops, one product tree and ONE final exponentiation per chunk instead of one per key.  The per-key sums and the 3 K_used fixed terms
+ * are made on the device; the host only sorts the chunk's lanes by key.  If the check fails, every valid proof gets its own four-pairing check under its key.
+ *   vks, vk_lens       host: n_keys keys, VerifyingKey.WriteTo bytes (vk_is_hex == 0) or their hex text (all keys in the same form).  Keys may differ in
+ *                      n_public and every point; a key no row refers to is parsed and otherwise unused; the same key may be given twice.
+ *   key_of             HOST memory in both forms: n_proofs indices below n_keys.
+ *   public_inputs      row i's inputs are the first n_public(key_of[i]) Montgomery fr.Elements at element i * pub_stride -- host memory, packed with that
+ *   / d_public_inputs  stride, in the first form; device memory in the _dev form.  Nothing beyond them is read, neither for the verdict nor for the
+ *                      coefficients.  May be NULL when every key has n_public 0.
+ *   d_proofs           device: row v's 128 bytes at d_proofs + v * proof_stride, any stride >= 128, any alignment.
+ * accepted[i] equals what zk_bn254_groth16_verify says of (proof i, vks[key_of[i]], its public inputs), except that a malformed proof encoding is a 0 and
+ * touches no other row, as in zk_bn254_groth16_verify_batch; with n_keys == 1 the verdicts are that entry's for the same rows (the coefficients are not).
+ * *n_accepted = the number of ones.
+ * Decided before a device is looked for, each leaving *n_accepted = 0: ZK_ERR_ARG for a null pointer that is read, n_keys == 0 with n_proofs > 0, a
+ * key_of[i] >= n_keys (the message names the row and the value), proof_stride < 128 with more than one row; ZK_ERR_LEN for pub_stride below the largest
+ * n_public among the keys with more than one row; a malformed key j gives the host verifier's code and message with "key j: " in front.  n_proofs == 0 is
+ * ZK_OK: the keys are still parsed, nothing is launched.  Without a GPU: ZK_ERR_NO_DEVICE, after the above.
+ * The coefficients stay derived: r_i = the low 128 bits of SHA-256(prefix || u64 i little-endian), forced non-zero, i counting over the whole call, with
+ *   KD     = SHA-256(u64 n_keys little-endian || SHA-256(vk_0 bytes) || ... || SHA-256(vk_{K-1} bytes) || key_of as n_proofs little-endian u32), "vk bytes" the
+ *            binary image (hex text decoded);
+ *   host form    prefix = "zkmi-groth16-batch-keys" || KD || SHA-256(proofs || row 0's n_public(key_of[0]) public inputs || row 1's || ...) -- the
+ *                Montgomery images as they lie, only the used ones;
+ *   device form  prefix = "zkmi-groth16-batch-keys-rows" || KD || D, D = SHA-256(d_0 || ... || d_{n-1}) on the host and
+ *                d_v = SHA-256(row v's 128 bytes || its 32 * n_public(key_of[v]) public-input bytes as they lie in memory), one lane per row on the device.
+ * Chunks of at most 2^16 proofs; the device workspace is about 6 KB per proof of a chunk, the public inputs of a chunk at their stride in the host form,
+ * 464 bytes per key, 64 bytes per K point of the keys, about 350 bytes per key used in a chunk and 4 (device form: 36) bytes per row of the call. */
+int zk_bn254_groth16_verify_batch_keys(const uint8_t *proofs, size_t n_proofs,
+        const void *const *vks, const size_t *vk_lens, size_t n_keys, int vk_is_hex,
+        const uint32_t *key_of /* host, n_proofs */,
+        const zk_fr *public_inputs, size_t pub_stride,
+        uint8_t *accepted, size_t *n_accepted);
+int zk_bn254_groth16_verify_batch_keys_dev(const void *d_proofs, size_t proof_stride, size_t n_proofs,
+        const void *const *vks, const size_t *vk_lens, size_t n_keys, int vk_is_hex,
+        const uint32_t *key_of /* host */,
+        const void *d_public_inputs, size_t pub_stride,
+        uint8_t *accepted, size_t *n_accepted);
+
 /* The two halves of zk_bn254_groth16_prove, exposed so that one proof can be range-sharded over several GPUs
  * (one process per GPU): every rank runs the five MSMs on ITS slice of the bases / wire values / h, the un-normalised
  * XYZZ sums (4 x G1 = 64 limbs, then G2 = 32 limbs; order A, B1, K, Z, B2) are all-gathered, and any rank finishes.

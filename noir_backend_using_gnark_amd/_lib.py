@@ -159,6 +159,7 @@ SYMBOLS = [
     "zk_bn254_felts_public_hex_rows_dev", "zk_plonk_verify_batch_with_vk", "zk_groth16_verify_batch_with_vk",
     "zk_bn254_kzg_open", "zk_bn254_kzg_batch_open_single_point", "zk_bn254_kzg_verify", "zk_bn254_kzg_fold_proof", "zk_bn254_kzg_batch_verify_single_point", "zk_bn254_kzg_verify_batch",
     "zk_bn254_plonk_verify_batch_keys", "zk_bn254_plonk_verify_batch_keys_dev",
+    "zk_bn254_groth16_verify_batch_keys", "zk_bn254_groth16_verify_batch_keys_dev",
     "zk_bn254_hscan_inspect", "zk_bn254_lagrange_inspect",
 ]
 
@@ -181,6 +182,9 @@ ARGTYPES = {
     # PLONK against many keys: proofs, n | vks, vk_lens, n_keys, is_hex | srs_g2, key_of | public inputs, pub_stride | accepted, n_accepted
     "zk_bn254_plonk_verify_batch_keys": [_VP, _SZ, _VP, _VP, _SZ, C.c_int, _VP, _VP, _VP, _SZ, _VP, _VP],
     "zk_bn254_plonk_verify_batch_keys_dev": [_VP, _SZ, _SZ, _VP, _VP, _SZ, C.c_int, _VP, _VP, _VP, _SZ, _VP, _VP],
+    # Groth16 against many keys: the same without srs_g2
+    "zk_bn254_groth16_verify_batch_keys": [_VP, _SZ, _VP, _VP, _SZ, C.c_int, _VP, _VP, _SZ, _VP, _VP],
+    "zk_bn254_groth16_verify_batch_keys_dev": [_VP, _SZ, _SZ, _VP, _VP, _SZ, C.c_int, _VP, _VP, _SZ, _VP, _VP],
 }
 # status of a row of those entries (include/zkmi.h: ZK_ROW_*)
 ROW_OK, ROW_UNSATISFIED, ROW_BAD_HEX, ROW_NOT_CANONICAL, ROW_BAD_COUNT, ROW_BAD_PROOF_HEX = 0, 1, 2, 3, 4, 5

@@ -12,6 +12,9 @@
 // What each adds (the kernels say the rest):
 //   groth16 (one lane per proof)   k_vb_gather (the proof's three slots into the decompressors' arrays); k_g1_decompress / k_g2_decompress with a flag per invalid point; k_vb_prep: r_i Ar_i, r_i Krs_i, r_i (1, w_i1, ..); check: n' + 3
 //       lanes, prod e(r_i Ar_i, Bs_i) e(-c_0 alpha, beta) e(-sum c_j K_j, gamma) e(-sum r_i Krs_i, delta) == 1; fallback: k_vb_single, 3 n + 1 lanes (the last: e(alpha, beta))
+//   groth16, a key per row (groth16_verify_rows_keys; DESIGN §3.9 "Many keys")   the host sorts the chunk's lanes by key (integers only); k_vbk_prep; per-key
+//       sums over tiles of 16 sorted items (k_vbk_g1_fold, k_vbk_coef, k_vbk_fr_fold); the fixed terms on the device (k_vbk_fixed, k_vbk_tail); check:
+//       n' + 3 K_used lanes; fallback: k_vbk_single, 4 n lanes, every Q the lane's key's
 //   plonk (one lane per proof)   k_pv_gather, k_g1_decompress, k_pv_transcript, k_pv_scalars, k_pv_smul + k_pv_digests, k_pv_kzg, k_pv_smul +
 //       k_pv_combine (A_i, B_i); check: 2 lanes, e(sum A + the G, S1, S2 terms, [1]2) e(-sum B, [alpha]2) == 1; fallback: k_pv_smul + k_pv_single, 2 n lanes
 //   plonk, a key per row (plonk_verify_rows_keys)   the k_pvk_* twins of those kernels read the lane's key from a table in HBM (PvKeyRow, key_of); c_S1 S1 and
@@ -20,6 +23,8 @@
 #include <string.h>
 
 #include <algorithm>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include "ctx.hpp"
@@ -215,6 +220,141 @@ __global__ __launch_bounds__(128) void k_vb_single(const Affine<Fp>* __restrict_
     for (size_t j = 0; j < np; j++) {
         const Fr w = pub[i * ps + j].from_mont();
         ic.add(scalar_mul(kpts[1 + j], w.l));
+    }
+    P[n + i] = ic.to_affine();
+}
+
+// ---- Groth16 against many keys (DESIGN 3.9 "Many keys"): row i is a proof for vks[key_of[i]].  The keys share nothing, so a chunk's lanes are sorted by
+// key on the host (integers only: perm, the used keys' segments, tile tables) and every per-key sum is a segmented sum over tiles of at most GK_T
+// consecutive sorted items that never cross a key: one partial per tile and level, as many levels as GK_T^levels >= the chunk asks for, whatever the keys are.
+struct GkKeyRow {
+    Affine<Fp> alpha;
+    Affine<Fp2> beta, gamma, delta;
+    uint32_t np, koff;  // n_public; where K_0 .. K_np lie in the ragged array of all keys' K points
+    uint32_t pad[2];
+};
+// a key used in the chunk: its index in the table, where its np + 1 coefficients c_{k,j} (and fixed terms) lie
+struct GkSeg {
+    uint32_t key, coff;
+};
+// one tile of one level: the items [start, start + len) of the level's input give item (the tile's index) of its output.  For the Fr sums the tile is a
+// len x cols matrix at fin (levels above the first) and a row of cols at fout
+struct GkTile {
+    uint32_t start, len, cols, fin, fout;
+};
+constexpr uint32_t GK_T = 16;
+
+// d_v = SHA-256(row v's 128 bytes || its 32 n_public(key_of[v]) public-input bytes): k_rows_digest_keys over the Groth16 table
+__global__ __launch_bounds__(64) void k_vbk_rows_digest(const uint8_t* __restrict__ a, size_t a_len, size_t a_stride, const uint8_t* __restrict__ b, size_t b_stride,
+                                                        const GkKeyRow* __restrict__ tab, const uint32_t* __restrict__ key_of, size_t rows,
+                                                        uint8_t* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    rows_digest_lane(i, a, a_len, a_stride, b, (size_t)tab[key_of[i]].np * 32, b_stride, out);
+}
+// k_vb_prep per sorted position p (lane i = perm[p]): valid[i] and r_i Ar_i stay in lane order beside Bs_i; r_i Krs_i and r_i (Montgomery; zero when the
+// lane is invalid) land in key-sorted order.  The public inputs are read by k_vbk_coef, which knows each key's n_public from its tiles
+__global__ __launch_bounds__(128) void k_vbk_prep(const Affine<Fp>* __restrict__ ar, const Affine<Fp>* __restrict__ krs, const uint8_t* __restrict__ bad,
+                                                  const uint32_t* __restrict__ rr, const uint32_t* __restrict__ perm, size_t n, uint8_t* __restrict__ valid,
+                                                  Affine<Fp>* __restrict__ p_out, XYZZ<Fp>* __restrict__ rk_out, Fr* __restrict__ rm_out) {
+    const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const size_t i = perm[p];
+    const bool ok = !(bad[i] | bad[n + i] | bad[2 * n + i]);
+    valid[i] = ok ? 1 : 0;
+    const uint32_t k[8] = {rr[4 * i], rr[4 * i + 1], rr[4 * i + 2], rr[4 * i + 3], 0, 0, 0, 0};
+    Fr rm = Fr::zero();
+    for (int j = 0; j < 4; j++) rm.l[j] = k[j];
+    rm_out[p] = ok ? rm.to_mont() : Fr::zero();
+    if (!ok) {
+        p_out[i] = Affine<Fp>::inf();
+        rk_out[p] = XYZZ<Fp>::inf();
+        return;
+    }
+    p_out[i] = scalar_mul(ar[i], k).to_affine();
+    rk_out[p] = scalar_mul(krs[i], k);
+}
+// one level of the segmented G1 sums: out[t] = sum of in over tile t
+__global__ __launch_bounds__(64) void k_vbk_g1_fold(const XYZZ<Fp>* __restrict__ in, const GkTile* __restrict__ tiles, size_t n_tiles, XYZZ<Fp>* __restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tiles) return;
+    const GkTile T = tiles[t];
+    XYZZ<Fp> a = in[T.start];
+    for (uint32_t q = 1; q < T.len; q++) a.add(in[T.start + q]);
+    out[t] = a;
+}
+// the first level of c_{k,j} = sum_i r_i w_ij (w_i0 = 1), one workgroup per tile and one lane per j <= n_public(k): the tile's rows of `pub` are read
+// through the permutation, and nothing behind a row's own n_public
+__global__ __launch_bounds__(64) void k_vbk_coef(const Fr* __restrict__ rm, const uint32_t* __restrict__ perm, const Fr* __restrict__ pub, size_t ps,
+                                                 const GkTile* __restrict__ tiles, Fr* __restrict__ out) {
+    const GkTile T = tiles[blockIdx.x];
+    for (uint32_t j = threadIdx.x; j < T.cols; j += blockDim.x) {
+        Fr a = Fr::zero();
+        for (uint32_t q = T.start; q < T.start + T.len; q++) a = a + (j ? rm[q] * pub[(size_t)perm[q] * ps + (j - 1)] : rm[q]);
+        out[T.fout + j] = a;
+    }
+}
+// the levels above: column sums of the tile's len x cols partial sums
+__global__ __launch_bounds__(64) void k_vbk_fr_fold(const Fr* __restrict__ in, const GkTile* __restrict__ tiles, Fr* __restrict__ out) {
+    const GkTile T = tiles[blockIdx.x];
+    for (uint32_t j = threadIdx.x; j < T.cols; j += blockDim.x) {
+        Fr a = in[T.fin + j];
+        for (uint32_t q = 1; q < T.len; q++) a = a + in[T.fin + (size_t)q * T.cols + j];
+        out[T.fout + j] = a;
+    }
+}
+// the fixed terms, one workgroup per used key u and one lane per term: fx[coff + j] = c_{k,j} K_{k,j} for j <= n_public(k) (full 256-bit scalars), and
+// fa[u] = c_{k,0} alpha_k
+__global__ __launch_bounds__(64) void k_vbk_fixed(const Fr* __restrict__ c, const GkSeg* __restrict__ segs, const GkKeyRow* __restrict__ tab,
+                                                  const Affine<Fp>* __restrict__ kpts, XYZZ<Fp>* __restrict__ fx, XYZZ<Fp>* __restrict__ fa) {
+    const GkSeg S = segs[blockIdx.x];
+    const uint32_t cols = tab[S.key].np + 1, koff = tab[S.key].koff;
+    for (uint32_t j = threadIdx.x; j <= cols; j += blockDim.x) {
+        const Fr s = c[S.coff + (j < cols ? j : 0)].from_mont();
+        const Affine<Fp> pt = j < cols ? kpts[koff + j] : tab[S.key].alpha;
+        const XYZZ<Fp> v = scalar_mul(pt, s.l);
+        if (j < cols) fx[S.coff + j] = v;
+        else fa[blockIdx.x] = v;
+    }
+}
+// per used key u: the Miller lanes n + 3 u .. of the combined check, P = (-c_{k,0} alpha_k, -IC_k, -sum r_i Krs_i), Q = (beta_k, gamma_k, delta_k)
+__global__ __launch_bounds__(64) void k_vbk_tail(const XYZZ<Fp>* __restrict__ fa, const XYZZ<Fp>* __restrict__ ic, const XYZZ<Fp>* __restrict__ rk,
+                                                 const GkSeg* __restrict__ segs, const GkKeyRow* __restrict__ tab, size_t n_segs, Affine<Fp>* __restrict__ P,
+                                                 Affine<Fp2>* __restrict__ qfix) {
+    const size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n_segs) return;
+    const GkKeyRow* K = tab + segs[u].key;
+    P[3 * u] = fa[u].to_affine().neg();
+    P[3 * u + 1] = ic[u].to_affine().neg();
+    P[3 * u + 2] = rk[u].to_affine().neg();
+    qfix[3 * u] = K->beta;
+    qfix[3 * u + 1] = K->gamma;
+    qfix[3 * u + 2] = K->delta;
+}
+// fallback, per proof under its own key k: P = (-Ar_i, IC_i, Krs_i, alpha_k) against Q = (Bs_i -- in place already --, gamma_k, delta_k, beta_k), row r of
+// both at [r n + i].  Its launch name, vbk_single, is what says "the per-lane fallback ran"
+__global__ __launch_bounds__(128) void k_vbk_single(const Affine<Fp>* __restrict__ ar, const Affine<Fp>* __restrict__ krs, const uint8_t* __restrict__ valid,
+                                                    const Fr* __restrict__ pub, size_t ps, const GkKeyRow* __restrict__ tab,
+                                                    const Affine<Fp>* __restrict__ kpts, const uint32_t* __restrict__ key_of, size_t n,
+                                                    Affine<Fp>* __restrict__ P, Affine<Fp2>* __restrict__ Q) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const GkKeyRow* K = tab + key_of[i];
+    Q[n + i] = K->gamma;
+    Q[2 * n + i] = K->delta;
+    Q[3 * n + i] = K->beta;
+    if (!valid[i]) {
+        P[i] = P[n + i] = P[2 * n + i] = P[3 * n + i] = Affine<Fp>::inf();
+        return;
+    }
+    P[i] = ar[i].neg();
+    P[2 * n + i] = krs[i];
+    P[3 * n + i] = K->alpha;
+    const Affine<Fp>* kp = kpts + K->koff;
+    XYZZ<Fp> ic = XYZZ<Fp>::from_affine(kp[0]);
+    for (size_t j = 0; j < K->np; j++) {
+        const Fr w = pub[i * ps + j].from_mont();
+        ic.add(scalar_mul(kp[1 + j], w.l));
     }
     P[n + i] = ic.to_affine();
 }
@@ -948,6 +1088,235 @@ int groth16_verify_rows(const Groth16Vk& v, const RowsIn& in, size_t n_proofs, s
     return ZK_OK;
 }
 
+// The tile tables of one segmented sum: segment u has len[u] >= 1 items (consecutive, in segment order) and cols[u] Fr columns.  Level l folds the level
+// below in tiles of at most GK_T items of one segment; after `levels` levels (GK_T^levels >= the longest segment possible) one item per segment is left, and
+// the Fr rows of the last level lie at the prefix sums of cols.  lev[l] = (first tile, tiles) of level l; fr_elems: the largest Fr output of a level
+struct GkLevels {
+    std::vector<GkTile> tiles;
+    std::vector<std::pair<size_t, size_t>> lev;
+    size_t fr_elems = 0, items1 = 0;  // items1: the tiles of the first level
+    bool build(const std::vector<uint32_t>& len, const std::vector<uint32_t>& cols, int levels) {
+        std::vector<uint64_t> m(len.begin(), len.end());
+        tiles.clear();
+        lev.clear();
+        for (int l = 0; l < levels; l++) {
+            uint64_t item = 0, fin = 0, fout = 0;
+            const size_t first = tiles.size();
+            for (size_t u = 0; u < m.size(); u++) {
+                const uint64_t out = (m[u] + GK_T - 1) / GK_T;
+                for (uint64_t b = 0; b < out; b++)
+                    tiles.push_back(GkTile{(uint32_t)(item + b * GK_T), (uint32_t)std::min<uint64_t>(GK_T, m[u] - b * GK_T), cols[u],
+                                           (uint32_t)(fin + b * GK_T * cols[u]), (uint32_t)(fout + b * cols[u])});
+                item += m[u];
+                fin += m[u] * cols[u];
+                fout += out * cols[u];
+                m[u] = out;
+            }
+            if (fin >> 31) return false;
+            lev.emplace_back(first, tiles.size() - first);
+            fr_elems = std::max<size_t>(fr_elems, fout);
+            if (l == 0) items1 = tiles.size();
+        }
+        return true;
+    }
+};
+int gk_level_count(size_t longest) {
+    int l = 1;
+    for (size_t r = GK_T; r < longest; r *= GK_T) l++;
+    return l;
+}
+// a chunk's lanes grouped by key (a stable counting sort: O(n + K) integer work, no field or curve arithmetic)
+struct GkChunk {
+    std::vector<uint32_t> perm;  // perm[p]: the lane at sorted position p
+    std::vector<GkSeg> segs;     // the keys used, in key order
+    GkLevels rows, fixed;        // the sums over a key's lanes; the sums over a key's np + 1 fixed terms
+    size_t n_cols = 0;           // sum over the used keys of np + 1
+};
+
+// groth16_verify_rows with a key per row.  pre: tag || KD || 32 bytes of data digest || 8 for the index; the data digest is the entry's in the host form and
+// made here in the device form (k_vbk_rows_digest needs the key table).  No host curve arithmetic: the 3 K_used fixed terms are made on the device
+int groth16_verify_rows_keys(const std::vector<Groth16Vk>& vs, const RowsIn& in, size_t n_proofs, const uint32_t* key_of, std::vector<uint8_t>& pre,
+                             uint8_t* accepted, size_t* n_accepted) {
+    const PairConsts PK = pair_consts();
+    const size_t nk = vs.size(), ps = in.pub_stride, ch = std::min(n_proofs, CHUNK);
+    std::vector<GkKeyRow> tab(nk);
+    std::vector<Affine<HFp>> kpts;
+    size_t max_np = 0;
+    for (size_t j = 0; j < nk; j++) {
+        GkKeyRow& R = tab[j];
+        memset(&R, 0, sizeof R);
+        R.alpha = bit_cast_img<Affine<Fp>>(vs[j].alpha);
+        R.beta = bit_cast_img<Affine<Fp2>>(vs[j].beta);
+        R.gamma = bit_cast_img<Affine<Fp2>>(vs[j].gamma);
+        R.delta = bit_cast_img<Affine<Fp2>>(vs[j].delta);
+        R.np = (uint32_t)(vs[j].K.size() - 1);
+        R.koff = (uint32_t)kpts.size();
+        max_np = std::max(max_np, (size_t)R.np);
+        kpts.insert(kpts.end(), vs[j].K.begin(), vs[j].K.end());
+        if (kpts.size() >> 31) return set_err(ZK_ERR_LEN, "the keys hold %zu K points", kpts.size());
+    }
+    // every chunk's grouping first: the workspace is sized by the largest
+    const int fixed_levels = gk_level_count(max_np + 1);
+    std::vector<GkChunk> plan((n_proofs + ch - 1) / ch);
+    size_t max_segs = 0, max_cols = 0, max_tiles = 0, max_fr = 1, max_rows1 = 1, max_fixed1 = 1;
+    {
+        std::vector<uint32_t> cnt(nk + 1), len, cols;
+        for (size_t c = 0; c < plan.size(); c++) {
+            const size_t c0 = c * ch, n = std::min(ch, n_proofs - c0);
+            GkChunk& C = plan[c];
+            std::fill(cnt.begin(), cnt.end(), 0);
+            for (size_t i = 0; i < n; i++) cnt[key_of[c0 + i] + 1]++;
+            len.clear();
+            cols.clear();
+            for (size_t k = 0; k < nk; k++) {
+                if (cnt[k + 1]) {
+                    C.segs.push_back(GkSeg{(uint32_t)k, (uint32_t)C.n_cols});
+                    len.push_back(cnt[k + 1]);
+                    cols.push_back(tab[k].np + 1);
+                    C.n_cols += tab[k].np + 1;
+                }
+                cnt[k + 1] += cnt[k];
+            }
+            C.perm.resize(n);
+            for (size_t i = 0; i < n; i++) C.perm[cnt[key_of[c0 + i]]++] = (uint32_t)i;
+            if (!C.rows.build(len, cols, gk_level_count(n)) || !C.fixed.build(cols, std::vector<uint32_t>(cols.size(), 0), fixed_levels))
+                return set_err(ZK_ERR_LEN, "the chunk at row %zu sums more than 2^31 public-input terms", c0);
+            max_segs = std::max(max_segs, C.segs.size());
+            max_cols = std::max(max_cols, C.n_cols);
+            max_tiles = std::max(max_tiles, C.rows.tiles.size() + C.fixed.tiles.size());
+            max_fr = std::max(max_fr, C.rows.fr_elems);
+            max_rows1 = std::max(max_rows1, C.rows.items1);
+            max_fixed1 = std::max(max_fixed1, C.fixed.items1);
+        }
+    }
+    // a chunk's public inputs as they come up in the host form: whole rows of the caller's stride but for the last, which ends with its own n_public
+    const size_t pub_elems = max_np ? (ch - 1) * ps + max_np : 0;
+
+    SlotGuard g;
+    ZK_TRY(acquire_slot(&g.s));
+    Slot* s = g.s;
+    hipStream_t st = s->stream;
+    PairCheck pc(s, PK, ch);
+    const size_t m_lanes = std::max(4 * ch, ch + 3 * max_segs);
+    uint8_t *d_stage, *d_bad, *d_rowdig;
+    uint32_t *d_raw, *d_rr, *d_key_of, *d_perm;
+    Affine<Fp> *d_ar, *d_krs, *d_p, *d_kpts;
+    Affine<Fp2> *d_q, *d_fix;  // d_q: Bs per lane, and the fallback's gamma, delta, beta per lane behind them
+    Fr *d_pub, *d_rm, *d_c[2];
+    XYZZ<Fp> *d_rk, *d_rkf[2], *d_fx, *d_fxf[2], *d_fa;
+    GkKeyRow* d_tab;
+    GkSeg* d_segs;
+    GkTile* d_tiles;
+    int* d_status;
+    ZK_TRY(plan_workspace(s, "groth16_verify_batch_keys", [&](ArenaPlan& p) {
+        p.take(in.on_device ? 1 : ch * 128, d_stage);
+        p.take(ch * 32, d_raw);
+        p.take(ch, d_ar, d_krs, d_rk, d_rm, d_perm);
+        p.take(ch * 4, d_q);
+        p.take(ch * 3, d_bad);
+        p.take(ch * 4, d_rr);
+        p.take(in.on_device ? 1 : std::max(pub_elems, (size_t)1), d_pub);
+        p.take(max_rows1, d_rkf[0], d_rkf[1]);
+        p.take(max_fr, d_c[0], d_c[1]);
+        p.take(std::max(max_cols, (size_t)1), d_fx);
+        p.take(max_fixed1, d_fxf[0], d_fxf[1]);
+        p.take(std::max(max_segs, (size_t)1), d_fa, d_segs);
+        p.take(std::max(max_tiles, (size_t)1), d_tiles);
+        p.take(m_lanes, d_p);
+        pc.layout(p, m_lanes);
+        p.take(3 * std::max(max_segs, (size_t)1), d_fix);
+        p.take(nk, d_tab);
+        p.take(std::max(kpts.size(), (size_t)1), d_kpts);
+        p.take(n_proofs, d_key_of);
+        p.take(in.on_device ? n_proofs * 32 : 1, d_rowdig);
+        p.take(16, d_status);
+        p.later(ch * G2_DECOMPRESS_SCRATCH);  // g2_decompress_dev's, per chunk
+    }));
+    ZK_HIP(hipMemcpyAsync(d_tab, tab.data(), nk * sizeof(GkKeyRow), hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_kpts, kpts.data(), kpts.size() * 64, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_key_of, key_of, n_proofs * 4, hipMemcpyHostToDevice, st));
+    if (in.on_device) {
+        // D = SHA-256(d_0 || .. || d_{n-1}) over the whole call, d_v = SHA-256(row v's proof || its own 32 n_public(key_of[v]) public-input bytes as they lie)
+        ZK_LAUNCH(s, st, "vbk_rows_digest", k_vbk_rows_digest, dim3(blocks(n_proofs, 64)), dim3(64), 0, in.proofs, (size_t)128, in.proof_stride,
+                  (const uint8_t*)in.pub, ps * 32, (const GkKeyRow*)d_tab, (const uint32_t*)d_key_of, n_proofs, d_rowdig);
+        std::vector<uint8_t> dig(n_proofs * 32);
+        ZK_HIP(hipMemcpyAsync(dig.data(), d_rowdig, dig.size(), hipMemcpyDeviceToHost, st));
+        ZK_TRY(slot_sync(s, st));
+        sha(pre.data() + pre.size() - 40, dig.data(), dig.size());
+    }
+    const size_t arena_mark = s->arena_off;  // g2_decompress_dev takes its scratch from the arena per call: give it back per chunk
+
+    std::vector<uint32_t> rr(ch * 4);
+    for (size_t c0 = 0; c0 < n_proofs; c0 += ch) {
+        const size_t n = std::min(ch, n_proofs - c0);
+        const GkChunk& C = plan[c0 / ch];
+        const size_t U = C.segs.size();
+        s->arena_off = arena_mark;
+        RowsIn at;
+        if (in.on_device) {
+            at = RowsIn{in.proofs + c0 * in.proof_stride, in.proof_stride, max_np ? in.pub + c0 * ps : nullptr, ps, true};
+        } else {
+            ZK_HIP(hipMemcpyAsync(d_stage, in.proofs + c0 * 128, n * 128, hipMemcpyHostToDevice, st));
+            const size_t last = vs[key_of[c0 + n - 1]].K.size() - 1;
+            if (max_np && (n - 1) * ps + last) ZK_HIP(hipMemcpyAsync(d_pub, in.pub + c0 * ps, ((n - 1) * ps + last) * 32, hipMemcpyHostToDevice, st));
+            at = RowsIn{d_stage, 128, d_pub, ps, true};
+        }
+        batch_coeffs(pre.data(), pre.size(), pre.size() - 8, c0, n, rr.data());
+        ZK_HIP(hipMemcpyAsync(d_rr, rr.data(), n * 16, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemcpyAsync(d_perm, C.perm.data(), n * 4, hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemcpyAsync(d_segs, C.segs.data(), U * sizeof(GkSeg), hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemcpyAsync(d_tiles, C.rows.tiles.data(), C.rows.tiles.size() * sizeof(GkTile), hipMemcpyHostToDevice, st));
+        const GkTile* d_ftiles = d_tiles + C.rows.tiles.size();
+        ZK_HIP(hipMemcpyAsync((void*)d_ftiles, C.fixed.tiles.data(), C.fixed.tiles.size() * sizeof(GkTile), hipMemcpyHostToDevice, st));
+        ZK_HIP(hipMemsetAsync(d_bad, 0, n * 3, st));
+        ZK_HIP(hipMemsetAsync(d_status, 0, 4, st));
+        ZK_LAUNCH(s, st, "vb_gather", k_vb_gather, dim3(blocks(n, 256)), dim3(256), 0, at.proofs, at.proof_stride, n, d_raw);
+        const uint8_t* raw = (const uint8_t*)d_raw;
+        ZK_TRY(g1_decompress_dev(s, st, raw, n, d_ar, d_status, d_bad));
+        ZK_TRY(g2_decompress_dev(s, st, raw + n * 32, n, d_q, d_status, d_bad + n));
+        ZK_TRY(g1_decompress_dev(s, st, raw + n * 96, n, d_krs, d_status, d_bad + 2 * n));
+        ZK_LAUNCH(s, st, "vbk_prep", k_vbk_prep, dim3(blocks(n, 128)), dim3(128), 0, (const Affine<Fp>*)d_ar, (const Affine<Fp>*)d_krs, (const uint8_t*)d_bad,
+                  (const uint32_t*)d_rr, (const uint32_t*)d_perm, n, pc.d_valid, d_p, d_rk, d_rm);
+        // per key: sum r_i Krs_i and the c_{k,j}, level by level
+        const XYZZ<Fp>* rk_in = d_rk;
+        const Fr* c_in = nullptr;
+        for (size_t l = 0; l < C.rows.lev.size(); l++) {
+            const GkTile* t = d_tiles + C.rows.lev[l].first;
+            const size_t nt = C.rows.lev[l].second;
+            ZK_LAUNCH(s, st, "vbk_g1_fold", k_vbk_g1_fold, dim3(blocks(nt, 64)), dim3(64), 0, rk_in, t, nt, d_rkf[l & 1]);
+            if (l == 0)
+                ZK_LAUNCH(s, st, "vbk_coef", k_vbk_coef, dim3((unsigned)nt), dim3(64), 0, (const Fr*)d_rm, (const uint32_t*)d_perm, at.pub, at.pub_stride, t,
+                          d_c[0]);
+            else
+                ZK_LAUNCH(s, st, "vbk_fr_fold", k_vbk_fr_fold, dim3((unsigned)nt), dim3(64), 0, c_in, t, d_c[l & 1]);
+            rk_in = d_rkf[l & 1];
+            c_in = d_c[l & 1];
+        }
+        // the fixed terms c_{k,j} K_{k,j} and c_{k,0} alpha_k, the sums IC_k of the former, and the 3 K_used lanes behind the chunk's n
+        ZK_LAUNCH(s, st, "vbk_fixed", k_vbk_fixed, dim3((unsigned)U), dim3(64), 0, c_in, (const GkSeg*)d_segs, (const GkKeyRow*)d_tab, (const Affine<Fp>*)d_kpts,
+                  d_fx, d_fa);
+        const XYZZ<Fp>* ic_in = d_fx;
+        for (size_t l = 0; l < C.fixed.lev.size(); l++) {
+            const size_t nt = C.fixed.lev[l].second;
+            ZK_LAUNCH(s, st, "vbk_g1_fold", k_vbk_g1_fold, dim3(blocks(nt, 64)), dim3(64), 0, ic_in, d_ftiles + C.fixed.lev[l].first, nt, d_fxf[l & 1]);
+            ic_in = d_fxf[l & 1];
+        }
+        ZK_LAUNCH(s, st, "vbk_tail", k_vbk_tail, dim3(blocks(U, 64)), dim3(64), 0, (const XYZZ<Fp>*)d_fa, ic_in, rk_in, (const GkSeg*)d_segs,
+                  (const GkKeyRow*)d_tab, U, d_p + n, d_fix);
+        ZK_TRY(pc.sync_valid(n, accepted + c0));
+        if (pc.decided) continue;
+        ZK_TRY(pc.combined(d_p, n + 3 * U, d_q, n, d_fix, n, accepted + c0));
+        if (pc.decided) continue;
+        // fallback: every valid proof on its own, four pairings under its own key (no e(alpha, beta) lane is shared across keys)
+        ZK_LAUNCH(s, st, "vbk_single", k_vbk_single, dim3(blocks(n, 128)), dim3(128), 0, (const Affine<Fp>*)d_ar, (const Affine<Fp>*)d_krs,
+                  (const uint8_t*)pc.d_valid, at.pub, at.pub_stride, (const GkKeyRow*)d_tab, (const Affine<Fp>*)d_kpts, (const uint32_t*)(d_key_of + c0), n, d_p,
+                  d_q);
+        ZK_TRY(pc.per_lane(d_p, n, 4, d_q, 4 * n, nullptr, false, accepted + c0));
+    }
+    *n_accepted = pc.total;
+    return ZK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1037,6 +1406,99 @@ int zk_bn254_groth16_verify_batch_dev(const void* d_proofs, size_t proof_stride,
     // r_i = low 128 bits of SHA-256(tag || SHA-256(vk) || SHA-256(d_0 || .. || d_{n-1}) || u64 i), d_v the rows' digests made on the device
     ZK_TRY(rows_digest_of_call(in, 128, n_proofs, n_public, pre.data() + pre.size() - 40));
     return groth16_verify_rows(v, in, n_proofs, n_public, pre, accepted, n_accepted);
+}
+
+// ---- Groth16 against many keys (DESIGN 3.9 "Many keys"): row i is a proof for vks[key_of[i]]
+// What both forms decide before a device is looked for: the keys parse (a malformed key j: the host verifier's code and message, "key j" in front), every
+// key_of[i] names a key, pub_stride holds the widest key's public inputs.  pre = tag || KD || 32 bytes for the data digest || 8 for the index, KD as in zkmi.h
+static int groth16_keys_head(size_t n_proofs, const void* const* vks, const size_t* vk_lens, size_t n_keys, int vk_is_hex, const uint32_t* key_of,
+                             const void* pub, size_t pub_stride, const char* tag, std::vector<Groth16Vk>* vs, std::vector<uint8_t>* pre) {
+    if (n_keys == 0 && n_proofs > 0) return set_err(ZK_ERR_ARG, "n_keys == 0 with %zu proofs", n_proofs);
+    vs->resize(n_keys);
+    size_t max_np = 0;
+    Sha256 kd;
+    uint8_t d[32];
+    const uint64_t nk = n_keys;
+    for (int b = 0; b < 8; b++) d[b] = (uint8_t)(nk >> (8 * b));
+    kd.update(d, 8);
+    // a key is about 0.7 ms of host decompression (three G2 subgroup checks among it) and the keys are independent: up to 16 threads, every n-th key each.
+    // The error text is per thread, so a worker keeps its key's; the first malformed key in key order is the one reported
+    std::vector<int> rcs(n_keys, ZK_OK);
+    std::vector<std::string> msgs(n_keys);
+    const size_t n_thr = std::min<size_t>(std::min<size_t>(16, n_keys), std::max(1u, std::thread::hardware_concurrency()));
+    auto parse = [&](size_t first) {
+        for (size_t j = first; j < n_keys; j += n_thr) {
+            if (!vks[j]) {
+                rcs[j] = ZK_ERR_ARG;
+                msgs[j] = "null pointer";
+                continue;
+            }
+            rcs[j] = groth16_vk_parse(vks[j], vk_lens[j], vk_is_hex, &(*vs)[j]);
+            if (rcs[j] != ZK_OK) msgs[j] = zk_last_error();
+        }
+    };
+    {
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < n_thr; t++) pool.emplace_back(parse, t);
+        if (n_thr) parse(0);
+        for (std::thread& t : pool) t.join();
+    }
+    for (size_t j = 0; j < n_keys; j++) {
+        if (rcs[j] != ZK_OK) return set_err(rcs[j], "key %zu: %s", j, msgs[j].c_str());
+        if ((*vs)[j].K.empty()) return set_err(ZK_ERR_LEN, "key %zu: no K point", j);
+        max_np = std::max(max_np, (*vs)[j].K.size() - 1);
+        sha(d, (*vs)[j].bytes.data(), (*vs)[j].bytes.size());
+        kd.update(d, 32);
+    }
+    for (size_t i = 0; i < n_proofs; i++) {
+        if (key_of[i] >= n_keys) return set_err(ZK_ERR_ARG, "key_of[%zu] = %u is not below n_keys = %zu", i, key_of[i], n_keys);
+        for (int b = 0; b < 4; b++) d[b] = (uint8_t)(key_of[i] >> (8 * b));
+        kd.update(d, 4);
+    }
+    if (n_proofs > 1 && pub_stride < max_np)
+        return set_err(ZK_ERR_LEN, "pub_stride = %zu is below the %zu public inputs of the widest key", pub_stride, max_np);
+    if (n_proofs && max_np && !pub) return set_err(ZK_ERR_ARG, "null pointer");
+    const size_t tl = strlen(tag);
+    pre->assign(tl + 32 + 32 + 8, 0);
+    memcpy(pre->data(), tag, tl);
+    kd.final(pre->data() + tl);
+    return ZK_OK;
+}
+
+int zk_bn254_groth16_verify_batch_keys(const uint8_t* proofs, size_t n_proofs, const void* const* vks, const size_t* vk_lens, size_t n_keys, int vk_is_hex,
+                                       const uint32_t* key_of, const zk_fr* public_inputs, size_t pub_stride, uint8_t* accepted, size_t* n_accepted) {
+    if (n_accepted) *n_accepted = 0;
+    if (!n_accepted || (n_keys && (!vks || !vk_lens)) || (n_proofs && (!proofs || !accepted || !key_of))) return set_err(ZK_ERR_ARG, "null pointer");
+    std::vector<Groth16Vk> vs;
+    std::vector<uint8_t> pre;
+    ZK_TRY(groth16_keys_head(n_proofs, vks, vk_lens, n_keys, vk_is_hex, key_of, public_inputs, pub_stride, "zkmi-groth16-batch-keys", &vs, &pre));
+    if (n_proofs == 0) return ZK_OK;
+    ZK_TRY(ensure_init());
+    // r_i = the low 128 bits of SHA-256(tag || KD || SHA-256(proofs || each row's own public inputs) || u64 i), forced non-zero
+    Sha256 h;
+    h.update(proofs, n_proofs * 128);
+    for (size_t i = 0; i < n_proofs; i++) {
+        const size_t np = vs[key_of[i]].K.size() - 1;
+        if (np) h.update(public_inputs + i * pub_stride, np * 32);
+    }
+    h.final(pre.data() + pre.size() - 40);
+    return groth16_verify_rows_keys(vs, RowsIn{proofs, 128, (const Fr*)public_inputs, pub_stride, false}, n_proofs, key_of, pre, accepted, n_accepted);
+}
+
+int zk_bn254_groth16_verify_batch_keys_dev(const void* d_proofs, size_t proof_stride, size_t n_proofs, const void* const* vks, const size_t* vk_lens,
+                                           size_t n_keys, int vk_is_hex, const uint32_t* key_of, const void* d_public_inputs, size_t pub_stride,
+                                           uint8_t* accepted, size_t* n_accepted) {
+    if (n_accepted) *n_accepted = 0;
+    if (!n_accepted || (n_keys && (!vks || !vk_lens)) || (n_proofs && (!d_proofs || !accepted || !key_of))) return set_err(ZK_ERR_ARG, "null pointer");
+    std::vector<Groth16Vk> vs;
+    std::vector<uint8_t> pre;
+    ZK_TRY(groth16_keys_head(n_proofs, vks, vk_lens, n_keys, vk_is_hex, key_of, d_public_inputs, pub_stride, "zkmi-groth16-batch-keys-rows", &vs, &pre));
+    if (n_proofs > 1 && proof_stride < 128) return set_err(ZK_ERR_ARG, "proof_stride = %zu is below the %zu bytes of a proof", proof_stride, (size_t)128);
+    if (n_proofs == 0) return ZK_OK;
+    ZK_TRY(ensure_init());
+    // the same with D = SHA-256(d_0 || .. || d_{n-1}) for the data digest, made by the core once the key table is in HBM
+    const RowsIn in{(const uint8_t*)d_proofs, proof_stride, (const Fr*)d_public_inputs, pub_stride, true};
+    return groth16_verify_rows_keys(vs, in, n_proofs, key_of, pre, accepted, n_accepted);
 }
 
 // what both forms of the PLONK entry decide before a device is looked for; pre = tag || SHA-256(vk) || SHA-256(srs_g2) || 32 bytes for the data digest

@@ -182,6 +182,51 @@ def plonk_verify_batch_keys_dev(d_proofs, proof_stride: int, n_proofs: int, vks,
     return _verdicts(rc, acc, n_proofs)
 
 
+def _padded_rows(public_inputs, n: int) -> np.ndarray:
+    """(n, pub_stride, 4) uint64 of the many-key entries: an array as it is, or per-row arrays of each row's own length padded to the longest"""
+    if isinstance(public_inputs, (list, tuple)):
+        rows = [np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4) for r in public_inputs]
+        if len(rows) != n:
+            raise ValueError("one row of public inputs per proof")
+        pub = np.zeros((n, max([len(r) for r in rows] + [0]), 4), np.uint64)
+        for i, r in enumerate(rows):
+            pub[i, :len(r)] = r
+        return pub
+    pub = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+    return pub.reshape(n, -1, 4) if pub.size else np.zeros((n, 0, 4), np.uint64)
+
+
+def groth16_verify_batch_keys(proofs, vks, key_of, public_inputs) -> np.ndarray:
+    """groth16_verify_batch against MANY verifying keys in one device call (zk_bn254_groth16_verify_batch_keys): proof i is verified against
+    vks[key_of[i]], every key's pairings in one product with one final exponentiation.  vks: a sequence of keys (all bytes or all hex str); key_of: n_proofs
+    key indices; public_inputs: (n_proofs, pub_stride, 4) Montgomery limbs, of which row i's first n_public(key_of[i]) elements are read, or a list of per-row
+    arrays of each row's own length, which is padded here.  The verdicts are groth16_verify's per row, a malformed proof being False instead of an error."""
+    blob = bytes(proofs) if isinstance(proofs, (bytes, bytearray)) else b"".join(bytes(x) for x in proofs)
+    if len(blob) % 128:
+        raise ValueError("a Groth16 proof is 128 bytes (Proof.WriteTo)")
+    n = len(blob) // 128
+    raw, ptrs, lens, n_keys, is_hex, ko = _keys_args(vks, key_of, n)
+    pub = _padded_rows(public_inputs, n)
+    acc = np.zeros(max(n, 1), np.uint8)
+    n_acc = C.c_size_t(0)
+    rc = lib().zk_bn254_groth16_verify_batch_keys(blob, n, ptrs, lens, n_keys, is_hex, vp(ko) if n else None, vp(pub) if pub.size else None, pub.shape[1],
+                                                  vp(acc), C.addressof(n_acc))
+    return _verdicts(rc, acc, n)
+
+
+def groth16_verify_batch_keys_dev(d_proofs, proof_stride: int, n_proofs: int, vks, key_of, d_public_inputs, pub_stride: int) -> np.ndarray:
+    """groth16_verify_batch_keys for rows that already lie in HBM (zk_bn254_groth16_verify_batch_keys_dev): proof v is the 128 bytes at
+    d_proofs + v * proof_stride, its public inputs the first n_public(key_of[v]) Montgomery elements at element v * pub_stride of d_public_inputs (None when
+    no key has any); vks and key_of are host data."""
+    raw, ptrs, lens, n_keys, is_hex, ko = _keys_args(vks, key_of, n_proofs)
+    p, q = _dev_rows(d_proofs, d_public_inputs, None)
+    acc = np.zeros(max(n_proofs, 1), np.uint8)
+    n_acc = C.c_size_t(0)
+    rc = lib().zk_bn254_groth16_verify_batch_keys_dev(p, proof_stride, n_proofs, ptrs, lens, n_keys, is_hex, vp(ko) if n_proofs else None, q or None,
+                                                      pub_stride, vp(acc), C.addressof(n_acc))
+    return _verdicts(rc, acc, n_proofs)
+
+
 def _dev_rows(proofs, public_inputs, n_public: int | None):
     """(device pointer or DeviceBuffer, rows) pair of arguments of the device forms -> raw pointers (0 for no public inputs)"""
     p = proofs.ptr if isinstance(proofs, _lib.DeviceBuffer) else int(proofs)
